@@ -6,10 +6,14 @@ One "step" = one pass of the hot path over one synthetic batch that is already r
 Precision: fp32 end to end (dtype "fp32": the parity mode, conv on v_mfma_f32_32x32x2_f32; roofline peak 157.3 TFLOP/s).
 Weak scaling: 32 images per GPU, global batch 32*N.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--size 640] [--model s] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--size 640] [--model s] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Extra objects:
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, runs W untimed and K timed steps and prints the headline
+figure (`value`, `ms_per_step` = wall clock of one timed step).  --dump-outputs DIR writes what the last timed step returned (loss, loss
+items, a fixed seeded sample of the model's and the EMA's state after the step) as DIR/<name>.npy.  --full adds everything else, with
+the steps of their own it takes after the timed ones - the oracle loss check of the batch, the extra objects below, `nms`, `predict`,
+`other_configs`:
   roofline      dominant kernel class = the implicit-GEMM conv kernel (forward + data gradient launches): algorithmic
                 FLOPs (2*M*N*K of the real problem) / HIP-event time of those launches, measured live in the timed steps
                 on the launch stream; peak = fp32 MFMA 157.3 TFLOP/s (MI355X_MICROARCH.md).  `wgrad` gives the same
@@ -57,6 +61,30 @@ def synthetic_batch(batch, size, seed, device):
     x = torch.rand(batch, 3, size, size, generator=g)
     t = synthetic_targets(batch, seed=seed, kmax=20, size=size, num_classes=80)
     return x.to(device), t.to(device)
+
+
+DUMP_SAMPLE = 1 << 22  # elements kept of a larger state: 16 MB per float32 file
+
+
+def state_sample(sd, n=DUMP_SAMPLE):
+    """A state_dict's tensors (parameters and buffers, in state_dict order) flattened into one float32 vector; beyond `n` elements a fixed,
+    seeded sample of `n` of them (the same indices in every run of the same model)."""
+    import torch
+
+    flat = torch.cat([v.detach().reshape(-1).float() for v in sd.values()])
+    if flat.numel() > n:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.asarray(a, dtype=np.float32))
 
 
 def cpu_baseline(model, size, batch=32, seconds_budget=45.0, family="yolo_nas"):
@@ -426,9 +454,20 @@ def resnet50_main(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = 64 * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().float().reshape(1).cpu(), "model_state": state_sample(net.state_dict())})
+    from super_gradients_amd import kernels as K
+
+    rec = {"metric": "images/sec ResNet-50 224x224 fwd+bwd", "value": round(value, 2), "unit": "images/s", "n_gpus": 1, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": dtype_label(K), "data": "synthetic",
+           "config": {"workload": "ResNet-50 synthetic ImageNet-shape 224x224, bs=64, forward+backward only, random-init weights",
+                      "final_loss": round(float(loss), 5), "conv_math": K.get_conv_math()}}
+    if not args.full:
+        print(json.dumps(rec), flush=True)
+        return
     # kernel-level roofline: the same steps once more with a HIP event pair around every conv launch on its launch stream (as the
     # detection workloads do): class 0 = fp32-MFMA forward / data gradient, 2 = the bf16x3 patch kernel, 1 = weight gradients
-    from super_gradients_amd import kernels as K
     from super_gradients_amd._lib import lib
 
     K.prof_enable(True)
@@ -443,31 +482,27 @@ def resnet50_main(args):
     K.prof_enable(False)
     ig_tf = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
     wg_tf = wg_fl / (wg_ms * 1e-3) / 1e12 if wg_ms > 0 else 0.0
-    print(json.dumps({"metric": "images/sec ResNet-50 224x224 fwd+bwd", "value": round(value, 2), "unit": "images/s", "n_gpus": 1, "steps": args.steps,
-                      "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-                      "vs_baseline": None, "dtype": dtype_label(K), "data": "synthetic",
-                      "config": {"workload": "ResNet-50 synthetic ImageNet-shape 224x224, bs=64, forward+backward only, random-init weights",
-                                 "final_loss": round(float(loss), 5), "conv_math": K.get_conv_math()},
-                      "roofline": {"bound": "mfma", "kernel": "igemm_kernel / pconv_kernel (conv forward + data gradient)", "achieved": round(ig_tf, 2),
-                                   "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(ig_tf / PEAK_FP32_MFMA_TFLOPS, 4), "traffic": None,
-                                   "timed_over": f"{args.steps} further steps with a HIP event pair around every launch of the kernel on its launch stream",
-                                   "launches_per_step": ig_n // max(args.steps, 1), "kernel_ms_per_step": round(ig_ms / args.steps, 3),
-                                   "algorithmic_bytes_per_launch": round(ig_bytes / max(ig_n, 1)),
-                                   "fp32_pipe": {"achieved": round((ig_fl - pc_fl) / ((ig_ms - pc_ms) * 1e-3) / 1e12, 2) if ig_ms > pc_ms else None,
-                                                 "peak": PEAK_FP32_MFMA_TFLOPS, "launches_per_step": (ig_n - pc_n) // max(args.steps, 1),
-                                                 "kernel_ms_per_step": round((ig_ms - pc_ms) / args.steps, 3)},
-                                   "bf16_pipe": None if pc_n == 0 else {"achieved": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12, 1), "peak": PEAK_BF16_MFMA_TFLOPS,
-                                                                        "frac": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
-                                                                        "launches_per_step": pc_n // max(args.steps, 1),
-                                                                        "kernel_ms_per_step": round(pc_ms / args.steps, 3),
-                                                                        "note": "executed bf16 MFMA FLOPs = 6 x algorithmic"},
-                                   "per_launch_bound": {"frac": round(ig_bound_ms / ig_ms, 4) if ig_ms > 0 else None,
-                                                        "note": f"sum over launches of max(FLOPs / the peak of the pipe the launch executes on ({PEAK_FP32_MFMA_TFLOPS} TFLOP/s fp32 MFMA; {PEAK_BF16X3_EQUIV_TFLOPS:.1f} = {PEAK_BF16_MFMA_TFLOPS:.0f} / 6 for bf16x3 launches), algorithmic bytes / {HBM_ACHIEVABLE_TBS} TB/s) / measured kernel time"},
-                                   "wgrad": {"achieved": round(wg_tf, 2), "frac": round(wg_tf / PEAK_FP32_MFMA_TFLOPS, 4), "launches_per_step": wg_n // max(args.steps, 1),
-                                             "kernel_ms_per_step": round(wg_ms / args.steps, 3),
-                                             "math": {0: "fp32", 1: "bf16x3", 2: "bf16x3+patch"}[int(lib().sgx_conv_get_wgrad_math())]},
-                                   "step_mfma_frac": round(value * 24.54 / 1e3 / PEAK_FP32_MFMA_TFLOPS, 4),
-                                   "note": "step_mfma_frac: images/s x 24.54 GFLOP (SURVEY 8d) / peak"}}), flush=True)
+    rec["roofline"] = {"bound": "mfma", "kernel": "igemm_kernel / pconv_kernel (conv forward + data gradient)", "achieved": round(ig_tf, 2),
+                       "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(ig_tf / PEAK_FP32_MFMA_TFLOPS, 4), "traffic": None,
+                       "timed_over": f"{args.steps} further steps with a HIP event pair around every launch of the kernel on its launch stream",
+                       "launches_per_step": ig_n // max(args.steps, 1), "kernel_ms_per_step": round(ig_ms / args.steps, 3),
+                       "algorithmic_bytes_per_launch": round(ig_bytes / max(ig_n, 1)),
+                       "fp32_pipe": {"achieved": round((ig_fl - pc_fl) / ((ig_ms - pc_ms) * 1e-3) / 1e12, 2) if ig_ms > pc_ms else None,
+                                     "peak": PEAK_FP32_MFMA_TFLOPS, "launches_per_step": (ig_n - pc_n) // max(args.steps, 1),
+                                     "kernel_ms_per_step": round((ig_ms - pc_ms) / args.steps, 3)},
+                       "bf16_pipe": None if pc_n == 0 else {"achieved": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12, 1), "peak": PEAK_BF16_MFMA_TFLOPS,
+                                                            "frac": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
+                                                            "launches_per_step": pc_n // max(args.steps, 1),
+                                                            "kernel_ms_per_step": round(pc_ms / args.steps, 3),
+                                                            "note": "executed bf16 MFMA FLOPs = 6 x algorithmic"},
+                       "per_launch_bound": {"frac": round(ig_bound_ms / ig_ms, 4) if ig_ms > 0 else None,
+                                            "note": f"sum over launches of max(FLOPs / the peak of the pipe the launch executes on ({PEAK_FP32_MFMA_TFLOPS} TFLOP/s fp32 MFMA; {PEAK_BF16X3_EQUIV_TFLOPS:.1f} = {PEAK_BF16_MFMA_TFLOPS:.0f} / 6 for bf16x3 launches), algorithmic bytes / {HBM_ACHIEVABLE_TBS} TB/s) / measured kernel time"},
+                       "wgrad": {"achieved": round(wg_tf, 2), "frac": round(wg_tf / PEAK_FP32_MFMA_TFLOPS, 4), "launches_per_step": wg_n // max(args.steps, 1),
+                                 "kernel_ms_per_step": round(wg_ms / args.steps, 3),
+                                 "math": {0: "fp32", 1: "bf16x3", 2: "bf16x3+patch"}[int(lib().sgx_conv_get_wgrad_math())]},
+                       "step_mfma_frac": round(value * 24.54 / 1e3 / PEAK_FP32_MFMA_TFLOPS, 4),
+                       "note": "step_mfma_frac: images/s x 24.54 GFLOP (SURVEY 8d) / peak"}
+    print(json.dumps(rec), flush=True)
 
 
 def main():
@@ -478,6 +513,9 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--model", default="s", choices=["s", "m", "l", "x"], help="x: PP-YOLOE only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the oracle loss check, the roofline / exclusive / host-enqueue "
+                    "steps, the CPU baseline, the NMS and predict() legs and the other configurations (the options below shape these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ema", action="store_true")
     ap.add_argument("--no-nms", action="store_true")
@@ -493,6 +531,8 @@ def main():
     ap.add_argument("--workload", default="yolo_nas", choices=["yolo_nas", "resnet50", "ppyoloe"],
                     help="yolo_nas = BASELINE.json's headline config; resnet50 = configs[1]; ppyoloe = SURVEY 8f-1 (same loss / step, CSPResNet model)")
     args = ap.parse_args()
+    if not args.full and (args.other_configs == "on" or args.loss_check_only):
+        ap.error("--other-configs on / --loss-check-only shape the legs of --full")
     if args.only_nms:
         import torch
 
@@ -537,9 +577,9 @@ def main():
     ema = None if args.no_ema else ModelEMA.from_params(net, decay=0.9997, decay_type="threshold")
     x, targets = synthetic_batch(args.batch, args.size, 42 + rank, device)
 
-    # parity of the benchmarked workload itself (rank 0 of a single-GPU run; skipped together with the CPU baseline)
+    # parity of the benchmarked workload itself (rank 0 of a single-GPU --full run; skipped together with the CPU baseline)
     loss_check = None
-    if world == 1 and (args.loss_check_only or not args.no_cpu_baseline):
+    if args.full and world == 1 and (args.loss_check_only or not args.no_cpu_baseline):
         loss_check = oracle_loss_check(net, crit, x, targets, args.model, "ppyoloe" if args.workload == "ppyoloe" else "yolo_nas")
 
     state = {"step": 0}
@@ -548,14 +588,14 @@ def main():
         if world > 1:
             reducer.broadcast_buffers(0)  # what DDP(broadcast_buffers=True), the reference's wrapping, does at every forward
         out = net(x)
-        loss, _ = crit(out, targets)
+        loss, items = crit(out, targets)
         loss.backward()
         opt.step(grad_scale=reducer.grad_scale if world > 1 else None)
         opt.zero_grad()
         if ema is not None:
             ema.update(net, state["step"], 100000)
         state["step"] += 1
-        return loss
+        return loss, items
 
     def fence():
         dist_barrier()
@@ -567,70 +607,76 @@ def main():
     allocs0 = torch.cuda.memory_stats().get("num_device_alloc", 0)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, items = step()
     fence()
     dt = time.perf_counter() - t0
     allocs_timed = torch.cuda.memory_stats().get("num_device_alloc", 0) - allocs0
     free_b, total_b = torch.cuda.mem_get_info()
-    # Roofline leg: the SAME K steps once more with a HIP event pair around every conv launch on its launch stream.  Recording ~900 events
-    # per step costs ~3 % of the step (r2f: 577 vs 558 images/s), so it is kept out of the K steps `value` is measured on; the per-kernel
-    # durations are what rocprofv3 --kernel-trace reports for the same command (profiles/).
-    skip = set((os.environ.get("SGX_BENCH_SKIP") or "").split(","))  # diagnosis aid: legs left out ("prof", "host")
-    K.prof_enable(True)
-    for _ in range(0 if "prof" in skip else args.steps):
-        step()
-    fence()
-    # class 0 = fp32-MFMA implicit GEMM, class 2 = the bf16x3 patch kernel, class 3 = the implicit GEMM in bf16x3 arithmetic (conv math
-    # "patch_bf3": the deep problems the patch kernel does not take): forward / data gradient together
-    pc_ms, pc_fl, pc_n = K.prof_summary(2)
-    g3_ms, g3_fl, g3_n = K.prof_summary(3)
-    bf_ms, bf_fl, bf_n = pc_ms + g3_ms, pc_fl + g3_fl, pc_n + g3_n  # everything on the bf16 matrix pipe
-    ig_bytes, wg_bytes = K.prof_bytes(0) + K.prof_bytes(2) + K.prof_bytes(3), K.prof_bytes(1)
-    ig_ms, ig_fl, ig_n = (a + b for a, b in zip(K.prof_summary(0), (bf_ms, bf_fl, bf_n)))
-    wg_ms, wg_fl, wg_n = K.prof_summary(1)
-    # per-launch roofline time: max(FLOPs / MFMA peak, algorithmic bytes / achievable HBM rate) summed over the same launches
-    ig_bound_ms = conv_bound_ms(K)
-    wg_bound_ms = K.prof_bound_ms(1, (PEAK_BF16X3_EQUIV_TFLOPS if lib().sgx_conv_get_wgrad_math() else PEAK_FP32_MFMA_TFLOPS) * 1e12, HBM_ACHIEVABLE_TBS * 1e12)
-    K.prof_enable(False)
-    # The per-launch figures above are taken while the weight-gradient kernels run concurrently on the side HIP stream (they share the
-    # CUs, which is what makes the step faster but stretches every launch).  For the kernel's own efficiency: 3 extra, untimed steps
-    # with the side stream off (every kernel has the GPU to itself), same HIP-event timing.
-    fence()
-    # (round 6: the branch stream - sub-chains of the model on lanes beside the main chain, modules/engine.py fork_branch - stretches the
-    # launches the same way; `single_chain` = 3 extra steps with the lanes off and the side stream on, the concurrency rounds 1 - 5's `frac`
-    # was measured under, for the trend across rounds; `exclusive` has lanes AND side stream off)
-    branch_mode = getattr(net, "branch_mode", 0)
-    sc_ms = sc_fl = scw_ms = scw_fl = 0.0
-    if branch_mode:
-        net.branch_mode = 0
+    if args.dump_outputs and rank == 0:
+        outs = {"loss": loss.detach().float().reshape(1).cpu(), "loss_items": items.detach().float().cpu(), "model_state": state_sample(net.state_dict())}
+        if ema is not None:
+            outs["ema_state"] = state_sample(ema.state_dict())
+        dump_outputs(args.dump_outputs, outs)
+    if args.full:
+        # Roofline leg: the SAME K steps once more with a HIP event pair around every conv launch on its launch stream.  Recording ~900 events
+        # per step costs ~3 % of the step (r2f: 577 vs 558 images/s), so it is kept out of the K steps `value` is measured on; the per-kernel
+        # durations are what rocprofv3 --kernel-trace reports for the same command (profiles/).
+        skip = set((os.environ.get("SGX_BENCH_SKIP") or "").split(","))  # diagnosis aid: legs left out ("prof", "host")
+        K.prof_enable(True)
+        for _ in range(0 if "prof" in skip else args.steps):
+            step()
+        fence()
+        # class 0 = fp32-MFMA implicit GEMM, class 2 = the bf16x3 patch kernel, class 3 = the implicit GEMM in bf16x3 arithmetic (conv math
+        # "patch_bf3": the deep problems the patch kernel does not take): forward / data gradient together
+        pc_ms, pc_fl, pc_n = K.prof_summary(2)
+        g3_ms, g3_fl, g3_n = K.prof_summary(3)
+        bf_ms, bf_fl, bf_n = pc_ms + g3_ms, pc_fl + g3_fl, pc_n + g3_n  # everything on the bf16 matrix pipe
+        ig_bytes, wg_bytes = K.prof_bytes(0) + K.prof_bytes(2) + K.prof_bytes(3), K.prof_bytes(1)
+        ig_ms, ig_fl, ig_n = (a + b for a, b in zip(K.prof_summary(0), (bf_ms, bf_fl, bf_n)))
+        wg_ms, wg_fl, wg_n = K.prof_summary(1)
+        # per-launch roofline time: max(FLOPs / MFMA peak, algorithmic bytes / achievable HBM rate) summed over the same launches
+        ig_bound_ms = conv_bound_ms(K)
+        wg_bound_ms = K.prof_bound_ms(1, (PEAK_BF16X3_EQUIV_TFLOPS if lib().sgx_conv_get_wgrad_math() else PEAK_FP32_MFMA_TFLOPS) * 1e12, HBM_ACHIEVABLE_TBS * 1e12)
+        K.prof_enable(False)
+        # The per-launch figures above are taken while the weight-gradient kernels run concurrently on the side HIP stream (they share the
+        # CUs, which is what makes the step faster but stretches every launch).  For the kernel's own efficiency: 3 extra, untimed steps
+        # with the side stream off (every kernel has the GPU to itself), same HIP-event timing.
+        fence()
+        # (round 6: the branch stream - sub-chains of the model on lanes beside the main chain, modules/engine.py fork_branch - stretches the
+        # launches the same way; `single_chain` = 3 extra steps with the lanes off and the side stream on, the concurrency rounds 1 - 5's `frac`
+        # was measured under, for the trend across rounds; `exclusive` has lanes AND side stream off)
+        branch_mode = getattr(net, "branch_mode", 0)
+        sc_ms = sc_fl = scw_ms = scw_fl = 0.0
+        if branch_mode:
+            net.branch_mode = 0
+            K.prof_enable(True)
+            for _ in range(0 if args.no_exclusive else 3):
+                step()
+            fence()
+            sc_ms, sc_fl = (sum(K.prof_summary(c)[i] for c in (0, 2, 3)) for i in (0, 1))
+            scw_ms, scw_fl, _ = K.prof_summary(1)
+            K.prof_enable(False)
+        side, net.side_stream = getattr(net, "side_stream", None), None
         K.prof_enable(True)
         for _ in range(0 if args.no_exclusive else 3):
             step()
         fence()
-        sc_ms, sc_fl = (sum(K.prof_summary(c)[i] for c in (0, 2, 3)) for i in (0, 1))
-        scw_ms, scw_fl, _ = K.prof_summary(1)
+        expc_ms, expc_fl, expc_n = K.prof_summary(2)
+        exg3_ms, exg3_fl, exg3_n = K.prof_summary(3)
+        ex_ms, ex_fl, ex_n = (a + b + c for a, b, c in zip(K.prof_summary(0), (expc_ms, expc_fl, expc_n), (exg3_ms, exg3_fl, exg3_n)))
+        exw_ms, exw_fl, exw_n = K.prof_summary(1)
+        ex_bound_ms = conv_bound_ms(K)
         K.prof_enable(False)
-    side, net.side_stream = getattr(net, "side_stream", None), None
-    K.prof_enable(True)
-    for _ in range(0 if args.no_exclusive else 3):
-        step()
-    fence()
-    expc_ms, expc_fl, expc_n = K.prof_summary(2)
-    exg3_ms, exg3_fl, exg3_n = K.prof_summary(3)
-    ex_ms, ex_fl, ex_n = (a + b + c for a, b, c in zip(K.prof_summary(0), (expc_ms, expc_fl, expc_n), (exg3_ms, exg3_fl, exg3_n)))
-    exw_ms, exw_fl, exw_n = K.prof_summary(1)
-    ex_bound_ms = conv_bound_ms(K)
-    K.prof_enable(False)
-    net.side_stream = side
-    if branch_mode:
-        net.branch_mode = branch_mode
-    # host side of one step: enqueue time of a step with the device idle at the start (no sync inside)
-    fence()
-    h0 = time.perf_counter()
-    for _ in range(0 if "host" in skip else 2):
-        step()
-    host_ms = (time.perf_counter() - h0) / 2 * 1e3
-    fence()
+        net.side_stream = side
+        if branch_mode:
+            net.branch_mode = branch_mode
+        # host side of one step: enqueue time of a step with the device idle at the start (no sync inside)
+        fence()
+        h0 = time.perf_counter()
+        for _ in range(0 if "host" in skip else 2):
+            step()
+        host_ms = (time.perf_counter() - h0) / 2 * 1e3
+        fence()
     tmax = torch.tensor([dt], device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -640,16 +686,10 @@ def main():
     if rank == 0:
         imgs = args.batch * world * args.steps
         value = imgs / dt
-        ig_tf = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
-        wg_tf = wg_fl / (wg_ms * 1e-3) / 1e12 if wg_ms > 0 else 0.0
-        per_gpu = value / world
-        # the committed PMC passes were taken on the headline workload only
-        pmc = measured_traffic() if (args.workload == "yolo_nas" and args.model == "s") else {}
-        traffic, traffic_src = pmc.get("bytes_per_launch"), pmc.get("source", "no PMC pass committed for this workload")
         rec = {
             "metric": f"images/sec/node {family}-{args.model.upper()} {args.size}x{args.size} train-step",
             "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "host_enqueue_ms_per_step": round(host_ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": dtype_label(K), "data": "synthetic",
             "config": {"workload": f"{family}-{args.model.upper()} synthetic COCO {args.size}x{args.size}, bs={args.batch}/GPU, PPYoloELoss(TAL)+AdamW"
                                    + ("" if args.no_ema else "+EMA") + ", random-init weights",
@@ -665,99 +705,107 @@ def main():
                        # hipMalloc calls of torch's caching allocator inside the timed steps (0 once the pool has its steady shape) and the device's memory
                        "device_allocs_in_timed_steps": allocs_timed,
                        "hbm_gb": {"reserved_by_this_process": round(torch.cuda.memory_reserved() / 2**30, 1), "free_on_device": round(free_b / 2**30, 1),
-                                  "total": round(total_b / 2**30, 1)}},
-            "roofline": {"bound": "mfma", "kernel": "igemm_kernel (implicit-GEMM conv forward + data gradient, "
-                                                    + ("v_mfma_f32_32x32x2_f32)" if K.get_conv_math() == "fp32" else
-                                                       "v_mfma_f32_32x32x2_f32) + pconv_kernel (3x3 problems from an LDS patch, v_mfma_f32_32x32x16_bf16 x6)" if K.get_conv_math() == "patch"
-                                                       else "v_mfma_f32_32x32x16_bf16 x6 where taps x channels >= 192, v_mfma_f32_32x32x2_f32 below) + pconv_kernel (3x3 stride-1 "
-                                                            "problems from an LDS patch, v_mfma_f32_32x32x16_bf16 x6)" if K.get_conv_math() == "patch_bf3"
-                                                       else "v_mfma_f32_32x32x16_bf16 x6 / v_mfma_f32_32x32x2_f32 per problem)"),
-                         "achieved": round(ig_tf, 2), "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(ig_tf / PEAK_FP32_MFMA_TFLOPS, 4),
-                         # the same launches priced on the pipe most of them EXECUTE on: bf16 MFMA FLOPs issued (6 x algorithmic) / the dense bf16 peak
-                         "frac_of_executed_pipe": None if bf_n == 0 else round(6.0 * bf_fl / (bf_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
-                         "frac_note": "frac = algorithmic fp32 FLOPs / the fp32-MFMA peak BASELINE.md prices the target against; "
-                                      "frac_of_executed_pipe = the bf16x3 launches (most of the step) against the bf16 pipe they run on.  Launch durations are "
-                                      "taken in the benchmarked configuration, i.e. with the weight-gradient stream and (round 6) the branch-stream lanes sharing the "
-                                      "chip - see single_chain (lanes off: the conditions of earlier rounds' frac) and exclusive (nothing concurrent); the step-level "
-                                      "figure that follows the wall clock is step_mfma_frac",
-                         "timed_over": f"{args.steps} further steps of the same loop with a HIP event pair around every launch of the kernel on its launch stream",
-                         "traffic": traffic, "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src, "traffic_measured_in_this_run": False,
-                         # the two matrix pipes apart (round 4): launches on the fp32 pipe against the fp32 peak, launches of the bf16x3 patch kernel
-                         # by the bf16 MFMA work they EXECUTE (six products per algorithmic one) against the dense bf16 peak; `achieved` above is
-                         # the combined fp32-equivalent figure
-                         "fp32_pipe": {"achieved": round((ig_fl - bf_fl) / ((ig_ms - bf_ms) * 1e-3) / 1e12, 2) if ig_ms > bf_ms else None, "peak": PEAK_FP32_MFMA_TFLOPS,
-                                       "frac": round((ig_fl - bf_fl) / ((ig_ms - bf_ms) * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if ig_ms > bf_ms else None,
-                                       "launches_per_step": (ig_n - bf_n) // max(args.steps, 1), "kernel_ms_per_step": round((ig_ms - bf_ms) / args.steps, 3)},
-                         "bf16_pipe": None if bf_n == 0 else {"achieved": round(6.0 * bf_fl / (bf_ms * 1e-3) / 1e12, 1), "peak": PEAK_BF16_MFMA_TFLOPS,
-                                                              "frac": round(6.0 * bf_fl / (bf_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
-                                                              "launches_per_step": bf_n // max(args.steps, 1), "kernel_ms_per_step": round(bf_ms / args.steps, 3),
-                                                              "note": "patch kernel + implicit-GEMM launches in bf16x3 arithmetic; executed bf16 MFMA FLOPs = 6 x algorithmic"},
-                         # the implicit GEMM's launches that run in bf16x3 arithmetic (conv math "patch_bf3": stride-2 3x3, deep 1x1, QARepVGG two-branch forms)
-                         "gemm_bf16x3": None if g3_n == 0 else {
-                             "launches_per_step": g3_n // max(args.steps, 1), "kernel_ms_per_step": round(g3_ms / args.steps, 3),
-                             "algorithmic_tflops": round(g3_fl / (g3_ms * 1e-3) / 1e12, 2), "executed_bf16_tflops": round(6.0 * g3_fl / (g3_ms * 1e-3) / 1e12, 1),
-                             "frac_of_bf16_mfma_peak": round(6.0 * g3_fl / (g3_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
-                             "exclusive_algorithmic_tflops": round(exg3_fl / (exg3_ms * 1e-3) / 1e12, 2) if exg3_ms > 0 else None},
-                         "algorithmic_bytes_per_launch": round(ig_bytes / max(ig_n, 1)), "launches_per_step": ig_n // max(args.steps, 1), "avg_launch_us": round(ig_ms * 1e3 / max(ig_n, 1), 2),
-                         "gflop_per_launch": round(ig_fl / max(ig_n, 1) / 1e9, 3), "kernel_ms_per_step": round(ig_ms / args.steps, 3),
-                         # the launch mix against the bound that applies to EACH launch's shape (shallow 1x1 layers are nearer the HBM bound than the MFMA one)
-                         "per_launch_bound": {"bound_ms_per_step": round(ig_bound_ms / args.steps, 3), "frac": round(ig_bound_ms / ig_ms, 4) if ig_ms > 0 else None,
-                                              "exclusive_frac": round(ex_bound_ms / ex_ms, 4) if ex_ms > 0 else None,
-                                              "wgrad_frac": round(wg_bound_ms / wg_ms, 4) if wg_ms > 0 else None,
-                                              "note": f"sum over launches of max(FLOPs / the peak of the pipe the launch executes on ({PEAK_FP32_MFMA_TFLOPS} TFLOP/s fp32 MFMA; {PEAK_BF16X3_EQUIV_TFLOPS:.1f} = {PEAK_BF16_MFMA_TFLOPS:.0f} / 6 for bf16x3 launches), algorithmic bytes / {HBM_ACHIEVABLE_TBS} TB/s) / measured kernel time"},
-                         "exclusive": {"achieved": round(ex_fl / (ex_ms * 1e-3) / 1e12, 2) if ex_ms > 0 else None,
-                                       "frac": round(ex_fl / (ex_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if ex_ms > 0 else None,
-                                       "wgrad_achieved": round(exw_fl / (exw_ms * 1e-3) / 1e12, 2) if exw_ms > 0 else None,
-                                       "note": "same kernels and launches with the side HIP stream and the branch-stream lanes disabled (every kernel has the "
-                                               "chip to itself): 3 extra untimed steps after the timed region"},
-                         "single_chain": None if sc_ms <= 0 else {
-                             "achieved": round(sc_fl / (sc_ms * 1e-3) / 1e12, 2), "frac": round(sc_fl / (sc_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-                             "wgrad_achieved": round(scw_fl / (scw_ms * 1e-3) / 1e12, 2) if scw_ms > 0 else None,
-                             "note": "same kernels and launches with the branch-stream lanes off and the side stream on - the concurrency `frac` was measured under "
-                                     "in rounds 1 - 5 (3 extra untimed steps).  `frac` itself is taken in the benchmarked configuration: since round 6 sub-chains of "
-                                     "the model run on two more HIP streams beside the main chain, which shortens the step and stretches every launch that shares "
-                                     "the chip with them (sum of kernel durations per step up, wall clock per step down)"},
-                         "wgrad": {"achieved": round(wg_tf, 2), "frac": round(wg_tf / PEAK_FP32_MFMA_TFLOPS, 4), "launches_per_step": wg_n // max(args.steps, 1),
-                                   "kernel_ms_per_step": round(wg_ms / args.steps, 3),
-                                   # arithmetic of the weight gradient (sgx_conv_get_wgrad_math: 0 fp32 pipe, 1 bf16x3 slab loop, 2 + patch kernel): in
-                                   # modes 1 / 2 the algorithmic FLOPs run as six bf16 MFMA products each - priced against the dense bf16 peak too
-                                   "math": {0: "fp32", 1: "bf16x3", 2: "bf16x3+patch"}[int(lib().sgx_conv_get_wgrad_math())],
-                                   "executed_bf16_tflops": round(6.0 * wg_tf, 1) if lib().sgx_conv_get_wgrad_math() else None,
-                                   "frac_of_bf16_mfma_peak": round(6.0 * wg_tf / PEAK_BF16_MFMA_TFLOPS, 4) if lib().sgx_conv_get_wgrad_math() else None,
-                                   "traffic": pmc.get("wgrad_bytes_per_launch"), "traffic_unit": "bytes/launch (HBM, PMC; a launch = one group of weight gradients)",
-                                   "algorithmic_bytes_per_launch": round(wg_bytes / max(wg_n, 1)), "gflop_per_launch": round(wg_fl / max(wg_n, 1) / 1e9, 3)},
-                         # the patch kernel alone, priced against BOTH pipes: algorithmic (fp32-equivalent) FLOPs against the fp32 matrix peak, and the
-                         # bf16 MFMA FLOPs it actually executes (six products per algorithmic one) against the dense bf16 peak
-                         "patch_kernel": None if pc_n == 0 else {
-                             "launches_per_step": pc_n // max(args.steps, 1), "kernel_ms_per_step": round(pc_ms / args.steps, 3),
-                             "algorithmic_tflops": round(pc_fl / (pc_ms * 1e-3) / 1e12, 2), "frac_of_fp32_mfma_peak": round(pc_fl / (pc_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-                             "executed_bf16_tflops": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12, 1), "frac_of_bf16_mfma_peak": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
-                             "exclusive_algorithmic_tflops": round(expc_fl / (expc_ms * 1e-3) / 1e12, 2) if expc_ms > 0 else None},
-                         "loaded_clock_ghz": pmc.get("loaded_clock_ghz"),
-                         # whole-step MFMA utilisation: algorithmic conv FLOPs of one step (model table; measured launches for PP-YOLOE) / step time
-                         "step_mfma_frac": round((per_gpu * TRAIN_GFLOP_PER_IMG[args.model] * (args.size / 640.0) ** 2 / 1e3 if args.workload == "yolo_nas"
-                                                  else (ig_fl + wg_fl) / args.steps / (dt / args.steps) / 1e12) / PEAK_FP32_MFMA_TFLOPS, 4)},
+                                  "total": round(total_b / 2**30, 1)}}
         }
-        if loss_check is not None:
-            rec["config"]["loss_check_vs_oracle"] = loss_check
-        if not args.no_cpu_baseline and world == 1:
-            rec["cpu_baseline"] = cpu_baseline(args.model, args.size, batch=args.batch, family="ppyoloe" if args.workload == "ppyoloe" else "yolo_nas")
-        if not args.no_nms and world == 1:
-            rec["nms"] = nms_leg(device)
-        if not args.no_predict and world == 1 and args.workload == "yolo_nas":
-            rec["predict"] = predict_leg(device, args.model, min(args.batch, 32))
-        # the other BASELINE.json configurations under the same clock (headline invocation only: S at the default shape on one GPU)
-        headline = world == 1 and args.workload == "yolo_nas" and args.model == "s" and args.size == 640 and args.batch == 32
-        if args.other_configs == "on" or (args.other_configs == "auto" and headline and not args.no_cpu_baseline):
-            # the headline model is done: its network, optimizer state, saved activations and the allocator's cached blocks (56 GB after the S
-            # steps) are released before the larger configurations take their 50 - 90 GB each
-            import gc
+        if args.full:
+            ig_tf = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
+            wg_tf = wg_fl / (wg_ms * 1e-3) / 1e12 if wg_ms > 0 else 0.0
+            per_gpu = value / world
+            # the committed PMC passes were taken on the headline workload only
+            pmc = measured_traffic() if (args.workload == "yolo_nas" and args.model == "s") else {}
+            traffic, traffic_src = pmc.get("bytes_per_launch"), pmc.get("source", "no PMC pass committed for this workload")
+            rec["host_enqueue_ms_per_step"] = round(host_ms, 3)
+            rec["roofline"] = {"bound": "mfma", "kernel": "igemm_kernel (implicit-GEMM conv forward + data gradient, "
+                                                          + ("v_mfma_f32_32x32x2_f32)" if K.get_conv_math() == "fp32" else
+                                                             "v_mfma_f32_32x32x2_f32) + pconv_kernel (3x3 problems from an LDS patch, v_mfma_f32_32x32x16_bf16 x6)" if K.get_conv_math() == "patch"
+                                                             else "v_mfma_f32_32x32x16_bf16 x6 where taps x channels >= 192, v_mfma_f32_32x32x2_f32 below) + pconv_kernel (3x3 stride-1 "
+                                                                  "problems from an LDS patch, v_mfma_f32_32x32x16_bf16 x6)" if K.get_conv_math() == "patch_bf3"
+                                                             else "v_mfma_f32_32x32x16_bf16 x6 / v_mfma_f32_32x32x2_f32 per problem)"),
+                               "achieved": round(ig_tf, 2), "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(ig_tf / PEAK_FP32_MFMA_TFLOPS, 4),
+                               # the same launches priced on the pipe most of them EXECUTE on: bf16 MFMA FLOPs issued (6 x algorithmic) / the dense bf16 peak
+                               "frac_of_executed_pipe": None if bf_n == 0 else round(6.0 * bf_fl / (bf_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
+                               "frac_note": "frac = algorithmic fp32 FLOPs / the fp32-MFMA peak BASELINE.md prices the target against; "
+                                            "frac_of_executed_pipe = the bf16x3 launches (most of the step) against the bf16 pipe they run on.  Launch durations are "
+                                            "taken in the benchmarked configuration, i.e. with the weight-gradient stream and (round 6) the branch-stream lanes sharing the "
+                                            "chip - see single_chain (lanes off: the conditions of earlier rounds' frac) and exclusive (nothing concurrent); the step-level "
+                                            "figure that follows the wall clock is step_mfma_frac",
+                               "timed_over": f"{args.steps} further steps of the same loop with a HIP event pair around every launch of the kernel on its launch stream",
+                               "traffic": traffic, "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src, "traffic_measured_in_this_run": False,
+                               # the two matrix pipes apart (round 4): launches on the fp32 pipe against the fp32 peak, launches of the bf16x3 patch kernel
+                               # by the bf16 MFMA work they EXECUTE (six products per algorithmic one) against the dense bf16 peak; `achieved` above is
+                               # the combined fp32-equivalent figure
+                               "fp32_pipe": {"achieved": round((ig_fl - bf_fl) / ((ig_ms - bf_ms) * 1e-3) / 1e12, 2) if ig_ms > bf_ms else None, "peak": PEAK_FP32_MFMA_TFLOPS,
+                                             "frac": round((ig_fl - bf_fl) / ((ig_ms - bf_ms) * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if ig_ms > bf_ms else None,
+                                             "launches_per_step": (ig_n - bf_n) // max(args.steps, 1), "kernel_ms_per_step": round((ig_ms - bf_ms) / args.steps, 3)},
+                               "bf16_pipe": None if bf_n == 0 else {"achieved": round(6.0 * bf_fl / (bf_ms * 1e-3) / 1e12, 1), "peak": PEAK_BF16_MFMA_TFLOPS,
+                                                                    "frac": round(6.0 * bf_fl / (bf_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
+                                                                    "launches_per_step": bf_n // max(args.steps, 1), "kernel_ms_per_step": round(bf_ms / args.steps, 3),
+                                                                    "note": "patch kernel + implicit-GEMM launches in bf16x3 arithmetic; executed bf16 MFMA FLOPs = 6 x algorithmic"},
+                               # the implicit GEMM's launches that run in bf16x3 arithmetic (conv math "patch_bf3": stride-2 3x3, deep 1x1, QARepVGG two-branch forms)
+                               "gemm_bf16x3": None if g3_n == 0 else {
+                                   "launches_per_step": g3_n // max(args.steps, 1), "kernel_ms_per_step": round(g3_ms / args.steps, 3),
+                                   "algorithmic_tflops": round(g3_fl / (g3_ms * 1e-3) / 1e12, 2), "executed_bf16_tflops": round(6.0 * g3_fl / (g3_ms * 1e-3) / 1e12, 1),
+                                   "frac_of_bf16_mfma_peak": round(6.0 * g3_fl / (g3_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
+                                   "exclusive_algorithmic_tflops": round(exg3_fl / (exg3_ms * 1e-3) / 1e12, 2) if exg3_ms > 0 else None},
+                               "algorithmic_bytes_per_launch": round(ig_bytes / max(ig_n, 1)), "launches_per_step": ig_n // max(args.steps, 1), "avg_launch_us": round(ig_ms * 1e3 / max(ig_n, 1), 2),
+                               "gflop_per_launch": round(ig_fl / max(ig_n, 1) / 1e9, 3), "kernel_ms_per_step": round(ig_ms / args.steps, 3),
+                               # the launch mix against the bound that applies to EACH launch's shape (shallow 1x1 layers are nearer the HBM bound than the MFMA one)
+                               "per_launch_bound": {"bound_ms_per_step": round(ig_bound_ms / args.steps, 3), "frac": round(ig_bound_ms / ig_ms, 4) if ig_ms > 0 else None,
+                                                    "exclusive_frac": round(ex_bound_ms / ex_ms, 4) if ex_ms > 0 else None,
+                                                    "wgrad_frac": round(wg_bound_ms / wg_ms, 4) if wg_ms > 0 else None,
+                                                    "note": f"sum over launches of max(FLOPs / the peak of the pipe the launch executes on ({PEAK_FP32_MFMA_TFLOPS} TFLOP/s fp32 MFMA; {PEAK_BF16X3_EQUIV_TFLOPS:.1f} = {PEAK_BF16_MFMA_TFLOPS:.0f} / 6 for bf16x3 launches), algorithmic bytes / {HBM_ACHIEVABLE_TBS} TB/s) / measured kernel time"},
+                               "exclusive": {"achieved": round(ex_fl / (ex_ms * 1e-3) / 1e12, 2) if ex_ms > 0 else None,
+                                             "frac": round(ex_fl / (ex_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if ex_ms > 0 else None,
+                                             "wgrad_achieved": round(exw_fl / (exw_ms * 1e-3) / 1e12, 2) if exw_ms > 0 else None,
+                                             "note": "same kernels and launches with the side HIP stream and the branch-stream lanes disabled (every kernel has the "
+                                                     "chip to itself): 3 extra untimed steps after the timed region"},
+                               "single_chain": None if sc_ms <= 0 else {
+                                   "achieved": round(sc_fl / (sc_ms * 1e-3) / 1e12, 2), "frac": round(sc_fl / (sc_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
+                                   "wgrad_achieved": round(scw_fl / (scw_ms * 1e-3) / 1e12, 2) if scw_ms > 0 else None,
+                                   "note": "same kernels and launches with the branch-stream lanes off and the side stream on - the concurrency `frac` was measured under "
+                                           "in rounds 1 - 5 (3 extra untimed steps).  `frac` itself is taken in the benchmarked configuration: since round 6 sub-chains of "
+                                           "the model run on two more HIP streams beside the main chain, which shortens the step and stretches every launch that shares "
+                                           "the chip with them (sum of kernel durations per step up, wall clock per step down)"},
+                               "wgrad": {"achieved": round(wg_tf, 2), "frac": round(wg_tf / PEAK_FP32_MFMA_TFLOPS, 4), "launches_per_step": wg_n // max(args.steps, 1),
+                                         "kernel_ms_per_step": round(wg_ms / args.steps, 3),
+                                         # arithmetic of the weight gradient (sgx_conv_get_wgrad_math: 0 fp32 pipe, 1 bf16x3 slab loop, 2 + patch kernel): in
+                                         # modes 1 / 2 the algorithmic FLOPs run as six bf16 MFMA products each - priced against the dense bf16 peak too
+                                         "math": {0: "fp32", 1: "bf16x3", 2: "bf16x3+patch"}[int(lib().sgx_conv_get_wgrad_math())],
+                                         "executed_bf16_tflops": round(6.0 * wg_tf, 1) if lib().sgx_conv_get_wgrad_math() else None,
+                                         "frac_of_bf16_mfma_peak": round(6.0 * wg_tf / PEAK_BF16_MFMA_TFLOPS, 4) if lib().sgx_conv_get_wgrad_math() else None,
+                                         "traffic": pmc.get("wgrad_bytes_per_launch"), "traffic_unit": "bytes/launch (HBM, PMC; a launch = one group of weight gradients)",
+                                         "algorithmic_bytes_per_launch": round(wg_bytes / max(wg_n, 1)), "gflop_per_launch": round(wg_fl / max(wg_n, 1) / 1e9, 3)},
+                               # the patch kernel alone, priced against BOTH pipes: algorithmic (fp32-equivalent) FLOPs against the fp32 matrix peak, and the
+                               # bf16 MFMA FLOPs it actually executes (six products per algorithmic one) against the dense bf16 peak
+                               "patch_kernel": None if pc_n == 0 else {
+                                   "launches_per_step": pc_n // max(args.steps, 1), "kernel_ms_per_step": round(pc_ms / args.steps, 3),
+                                   "algorithmic_tflops": round(pc_fl / (pc_ms * 1e-3) / 1e12, 2), "frac_of_fp32_mfma_peak": round(pc_fl / (pc_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
+                                   "executed_bf16_tflops": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12, 1), "frac_of_bf16_mfma_peak": round(6.0 * pc_fl / (pc_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4),
+                                   "exclusive_algorithmic_tflops": round(expc_fl / (expc_ms * 1e-3) / 1e12, 2) if expc_ms > 0 else None},
+                               "loaded_clock_ghz": pmc.get("loaded_clock_ghz"),
+                               # whole-step MFMA utilisation: algorithmic conv FLOPs of one step (model table; measured launches for PP-YOLOE) / step time
+                               "step_mfma_frac": round((per_gpu * TRAIN_GFLOP_PER_IMG[args.model] * (args.size / 640.0) ** 2 / 1e3 if args.workload == "yolo_nas"
+                                                        else (ig_fl + wg_fl) / args.steps / (dt / args.steps) / 1e12) / PEAK_FP32_MFMA_TFLOPS, 4)}
+            if loss_check is not None:
+                rec["config"]["loss_check_vs_oracle"] = loss_check
+            if not args.no_cpu_baseline and world == 1:
+                rec["cpu_baseline"] = cpu_baseline(args.model, args.size, batch=args.batch, family="ppyoloe" if args.workload == "ppyoloe" else "yolo_nas")
+            if not args.no_nms and world == 1:
+                rec["nms"] = nms_leg(device)
+            if not args.no_predict and world == 1 and args.workload == "yolo_nas":
+                rec["predict"] = predict_leg(device, args.model, min(args.batch, 32))
+            # the other BASELINE.json configurations under the same clock (headline invocation only: S at the default shape on one GPU)
+            headline = world == 1 and args.workload == "yolo_nas" and args.model == "s" and args.size == 640 and args.batch == 32
+            if args.other_configs == "on" or (args.other_configs == "auto" and headline and not args.no_cpu_baseline):
+                # the headline model is done: its network, optimizer state, saved activations and the allocator's cached blocks (56 GB after the S
+                # steps) are released before the larger configurations take their 50 - 90 GB each
+                import gc
 
-            step = fence = None
-            del net, reducer, crit, opt, ema, x, targets, loss, side
-            gc.collect()
-            torch.cuda.empty_cache()
-            rec["other_configs"] = other_configs_leg(device, loss_check=not args.no_cpu_baseline or args.loss_check_only)
+                step = fence = None
+                del net, reducer, crit, opt, ema, x, targets, loss, side
+                gc.collect()
+                torch.cuda.empty_cache()
+                rec["other_configs"] = other_configs_leg(device, loss_check=not args.no_cpu_baseline or args.loss_check_only)
         print(json.dumps(rec), flush=True)
     if dist.is_initialized():  # (world > 1, or the one-rank communicator of SGX_DIST_SINGLE_RANK_COLLECTIVES=1)
         dist_barrier()

@@ -63,6 +63,20 @@ def detection_targets(batch, size, seed, kmax=4, num_classes=80, empty_last=True
     return torch.tensor(rows, dtype=torch.float32).reshape(-1, 6)
 
 
+def reference_outputs(name, compute):
+    """What the reference's own code returns for a test's seeded inputs.  Where the reference tree exists (oracle/ref_shim.py) `compute()`
+    runs it live, and with SGX_WRITE_GOLDEN=1 stores the result as tests/golden/<name>.pt; everywhere else that stored result is read."""
+    from oracle import ref_shim
+
+    path = os.path.join(GOLDEN_DIR, f"{name}.pt")
+    if not ref_shim.available():
+        return torch.load(path, weights_only=True)
+    out = compute()
+    if os.environ.get("SGX_WRITE_GOLDEN"):
+        torch.save(out, path)
+    return out
+
+
 # the fixed target tensor of the reference's own loss unit test (tests/unit_tests/ppyoloe_unit_test.py:59-72)
 REFERENCE_UNIT_TEST_TARGETS = torch.tensor(
     [

@@ -170,31 +170,40 @@ def test_qarepvgg_block_learnable_alpha(backend, stride):
     assert_close(to_nchw_cpu(got), want, 1e-4, "fused forward with alpha")
 
 
-@pytest.mark.skipif(not __import__("oracle.ref_shim", fromlist=["x"]).available(), reason="/root/reference not present (GPU box)")
 @pytest.mark.parametrize("stride", [1, 2])
 def test_oracle_qarepvgg_alpha_live(stride):
-    """oracle.QARep(use_alpha=True) against the reference's own QARepVGGBlock source executed through the import shim."""
+    """oracle.QARep(use_alpha=True) against the reference's own QARepVGGBlock source executed through the import shim (where the reference
+    tree exists; its stored state, output and gradients elsewhere)."""
+    from oracle import golden_util as G
     from oracle import ref_shim
     from oracle.yolo_nas import QARep
 
-    ref_shim.install()
-    from super_gradients.modules.qarepvgg_block import QARepVGGBlock as RefBlock
-
     c, co = 8, 8 * stride
-    torch.manual_seed(3)
-    r = RefBlock(c, co, stride=stride, use_alpha=True, use_residual_connection=stride == 1).train()
-    o = QARep(c, co, stride, residual=stride == 1, use_alpha=True).train()
-    r.alpha.data.fill_(0.6)
-    missing = o.load_state_dict(r.state_dict(), strict=False)
-    assert not missing.missing_keys
     x = torch.randn(2, c, 6, 5, generator=torch.Generator().manual_seed(1))
-    xr, xo = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
-    yr, yo = r(xr), o(xo)
-    assert torch.equal(yr, yo)
-    g = torch.randn(yr.shape, generator=torch.Generator().manual_seed(2))
-    yr.backward(g)
+
+    def reference():
+        ref_shim.install()
+        from super_gradients.modules.qarepvgg_block import QARepVGGBlock as RefBlock
+
+        torch.manual_seed(3)
+        r = RefBlock(c, co, stride=stride, use_alpha=True, use_residual_connection=stride == 1).train()
+        r.alpha.data.fill_(0.6)
+        state = {k: v.clone() for k, v in r.state_dict().items()}
+        xr = x.clone().requires_grad_(True)
+        yr = r(xr)
+        yr.backward(torch.randn(yr.shape, generator=torch.Generator().manual_seed(2)))
+        return dict(state=state, y=yr.detach(), x_grad=xr.grad, alpha_grad=r.alpha.grad)
+
+    ref = G.reference_outputs(f"qarepvgg_alpha_stride{stride}_reference", reference)
+    o = QARep(c, co, stride, residual=stride == 1, use_alpha=True).train()
+    missing = o.load_state_dict(ref["state"], strict=False)
+    assert not missing.missing_keys
+    xo = x.clone().requires_grad_(True)
+    yo = o(xo)
+    assert torch.equal(ref["y"], yo)
+    g = torch.randn(yo.shape, generator=torch.Generator().manual_seed(2))
     yo.backward(g)
-    assert torch.equal(xr.grad, xo.grad) and torch.equal(r.alpha.grad, o.alpha.grad)
+    assert torch.equal(ref["x_grad"], xo.grad) and torch.equal(ref["alpha_grad"], o.alpha.grad)
 
 
 @pytest.mark.parametrize("k,s", [(1, 1), (3, 2)])
@@ -422,28 +431,37 @@ def test_repvgg_block_learnable_alpha(backend):
         assert_close(to_nchw_cpu(blk.fwd(to_nhwc(x, backend))), ref(x), 2e-5, "fused forward")
 
 
-@pytest.mark.skipif(not __import__("oracle.ref_shim", fromlist=["x"]).available(), reason="/root/reference not present (GPU box)")
 def test_oracle_repvgg_alpha_live():
-    """oracle.pp_yolo_e.RepVGGBlock(use_alpha=True) against the reference's own RepVGGBlock source executed through the import shim."""
+    """oracle.pp_yolo_e.RepVGGBlock(use_alpha=True) against the reference's own RepVGGBlock source executed through the import shim (where
+    the reference tree exists; its stored state, output and gradients elsewhere)."""
+    from oracle import golden_util as G
     from oracle import ref_shim
     from oracle.pp_yolo_e import RepVGGBlock as O
 
-    ref_shim.install()
-    from super_gradients.modules.repvgg_block import RepVGGBlock as RefBlock
-
     c = 8
-    r = RefBlock(c, c, activation_type=nn.SiLU, use_residual_connection=False, use_alpha=True).train()
-    o = O(c, c, nn.SiLU, use_alpha=True).train()
-    _randomize(r, 3)
-    _randomize(o, 3)  # (the same BatchNorm eps / momentum on both sides; the parameters are then copied from the reference block)
-    o.load_state_dict(r.state_dict(), strict=True)
     x = torch.randn(2, c, 6, 6, generator=torch.Generator().manual_seed(1))
-    xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
-    ya, yb = r(xa), o(xb)
-    assert torch.equal(ya, yb)
-    ya.sum().backward()
+
+    def reference():
+        ref_shim.install()
+        from super_gradients.modules.repvgg_block import RepVGGBlock as RefBlock
+
+        r = RefBlock(c, c, activation_type=nn.SiLU, use_residual_connection=False, use_alpha=True).train()
+        _randomize(r, 3)
+        state = {k: v.clone() for k, v in r.state_dict().items()}
+        xa = x.clone().requires_grad_(True)
+        ya = r(xa)
+        ya.sum().backward()
+        return dict(state=state, y=ya.detach(), x_grad=xa.grad, alpha_grad=r.alpha.grad)
+
+    ref = G.reference_outputs("repvgg_alpha_reference", reference)
+    o = O(c, c, nn.SiLU, use_alpha=True).train()
+    _randomize(o, 3)  # (the same BatchNorm eps / momentum on both sides; the parameters are then copied from the reference block)
+    o.load_state_dict(ref["state"], strict=True)
+    xb = x.clone().requires_grad_(True)
+    yb = o(xb)
+    assert torch.equal(ref["y"], yb)
     yb.sum().backward()
-    assert torch.equal(xa.grad, xb.grad) and torch.equal(r.alpha.grad, o.alpha.grad)
+    assert torch.equal(ref["x_grad"], xb.grad) and torch.equal(ref["alpha_grad"], o.alpha.grad)
 
 
 def test_effective_se_block(backend):

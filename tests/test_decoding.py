@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import decoding as odec
+from oracle import golden_util as G
 from oracle import ref_shim
 
 
@@ -25,20 +26,24 @@ def _case(B, L, C, seed, ties=False):
     return boxes, scores
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present (GPU box)")
 @pytest.mark.parametrize("family", ["yolo_nas", "ppyoloe"])
 def test_oracle_decoding_live(family):
-    ref_shim.install()
-    if family == "yolo_nas":
-        from super_gradients.training.models.detection_models.yolo_nas.yolo_nas_variants import YoloNASDecodingModule as Ref
-    else:
-        from super_gradients.training.models.detection_models.pp_yolo_e.pp_yolo_e import PPYoloEDecodingModule as Ref
-    for B, L, C, k in ((2, 300, 7, 50), (1, 8400, 80, 1000), (3, 64, 1, 64)):
+    """The oracle against the reference's decoding module: run live where the reference tree exists, its stored results elsewhere."""
+    shapes = ((2, 300, 7, 50), (1, 8400, 80, 1000), (3, 64, 1, 64))
+
+    def reference():
+        ref_shim.install()
+        if family == "yolo_nas":
+            from super_gradients.training.models.detection_models.yolo_nas.yolo_nas_variants import YoloNASDecodingModule as Ref
+        else:
+            from super_gradients.training.models.detection_models.pp_yolo_e.pp_yolo_e import PPYoloEDecodingModule as Ref
+        return [(*Ref(k)((_case(B, L, C, seed=L), None)), Ref(k).get_num_pre_nms_predictions()) for B, L, C, k in shapes]
+
+    for (B, L, C, k), (rb, rs, n_pre) in zip(shapes, G.reference_outputs(f"decoding_{family}_reference", reference), strict=True):
         boxes, scores = _case(B, L, C, seed=L)
-        rb, rs = Ref(k)(((boxes, scores), None))
         ob, os_, _ = odec.decode_topk(boxes, scores, k)
         assert torch.equal(rb, ob) and torch.equal(rs, os_)
-        assert Ref(k).get_num_pre_nms_predictions() == k
+        assert n_pre == k
 
 
 @pytest.mark.parametrize("shape", [(2, 300, 7, 50), (2, 2100, 80, 1000), (1, 64, 1, 64), (2, 500, 5, 300)])

@@ -295,18 +295,32 @@ def test_oracle_model_live(variant):
         assert e < 1e-3, f"{n}: grad rel L2 {e:.2e}"
 
 
-@live
+def _unit_test_case(sizes):
+    """Head outputs and targets of the reference's loss unit test, and the reference's (loss, items) for every (static, batched) pair:
+    live where the reference tree exists, stored elsewhere."""
+    preds = G.synthetic_predictions(4, sizes, 80, 16, seed=21, make_anchors=_oracle_anchors)
+    t = G.REFERENCE_UNIT_TEST_TARGETS * torch.tensor([1, 1, 0.3, 0.3, 0.3, 0.3])
+    flags = [(static, batched) for static in (True, False) for batched in (True, False)]
+
+    def reference():
+        return [tuple(v.detach() for v in ref_shim.reference_ppyolo_loss(num_classes=80, use_static_assigner=static, reg_max=16,
+                                                                          use_batched_assignment=batched)((None, preds), t))
+                for static, batched in flags]
+
+    refs = G.reference_outputs(f"ppyoloe_loss_unit_test_{'x'.join(map(str, sizes))}_reference", reference)
+    return preds, t, dict(zip(flags, refs, strict=True))
+
+
 def test_reference_unit_test_batched_equals_sequential_on_product(backend):
     """tests/unit_tests/ppyoloe_unit_test.py:42-81 transplanted: the product loss (one code path for both flags) against the
     reference's sequential AND batched implementations on the same head outputs, places=4 as the reference asserts."""
     from super_gradients_amd.training.losses import PPYoloELoss
 
-    preds = G.synthetic_predictions(4, [20, 10, 5] if backend.type == "cuda" else [6, 3, 3], 80, 16, seed=21, make_anchors=_oracle_anchors)
-    t = G.REFERENCE_UNIT_TEST_TARGETS * torch.tensor([1, 1, 0.3, 0.3, 0.3, 0.3])
+    preds, t, refs = _unit_test_case([20, 10, 5] if backend.type == "cuda" else [6, 3, 3])
     for static in (True, False):
         ours = PPYoloELoss(80, use_static_assigner=static)((None, tuple(p.to(backend) if torch.is_tensor(p) else p for p in preds)), t.to(backend))
         for batched in (True, False):
-            ref = ref_shim.reference_ppyolo_loss(num_classes=80, use_static_assigner=static, reg_max=16, use_batched_assignment=batched)((None, preds), t)
+            ref = refs[static, batched]
             assert abs(float(ours[0]) - float(ref[0])) < 0.5e-4 * max(1.0, abs(float(ref[0])))
             for i in range(4):
                 assert abs(float(ours[1][i]) - float(ref[1][i])) < 0.5e-4 * max(1.0, abs(float(ref[1][i])))

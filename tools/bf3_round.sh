@@ -5,7 +5,7 @@ TAG=${1:-bf3}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout 200 python -m pytest tests/test_kernels.py -m gpu -q -k "conv_bf16x3" > $OUT/pytest_bf16x3.log 2>&1; tail -2 $OUT/pytest_bf16x3.log
-SGX_CONV_MATH=${MATH:-bf16x3} timeout 200 python bench.py --no-nms --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_bf16x3.log 2> $OUT/bench_bf16x3.err
+SGX_CONV_MATH=${MATH:-bf16x3} timeout 200 python bench.py --full --no-nms --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_bf16x3.log 2> $OUT/bench_bf16x3.err
 python - <<P
 import json
 try:

@@ -16,7 +16,7 @@ rocminfo 2>/dev/null | grep -m3 -E "gfx950|Compute Unit|Max Clock" > "$OUT/rocmi
 nproc > "$OUT/nproc.txt"
 
 if has bench; then
-  timeout 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2> "$OUT/bench.err"
+  timeout 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2> "$OUT/bench.err"
   echo "bench rc=$?" >> "$OUT/bench.err"
   cat "$OUT/bench.log"; tail -3 "$OUT/bench.err"
 fi
@@ -25,7 +25,7 @@ if has convbench; then
   echo "convbench rc=$?" >> "$OUT/conv_bench.log"
   tail -4 "$OUT/conv_bench.log"
 fi
-PROF_CMD="python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-nms --no-predict --no-exclusive"
+PROF_CMD="python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-nms --no-predict --no-exclusive"
 if has stats; then
   cd /tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats" -o bench -- bash -c "cd $REPO && $PROF_CMD" > "$OUT/stats.log" 2>&1
@@ -41,7 +41,7 @@ fi
 if has pmc; then
   # (rocprofv3 --pmc serialises the dispatches: every kernel of these passes has the chip to itself - the per-kernel figures are EXCLUSIVE ones,
   # whatever stream the kernel was launched on; r4zz: a pass with the side stream off measured the same durations)
-  PMC_CMD="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-nms --no-predict --no-exclusive"
+  PMC_CMD="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-nms --no-predict --no-exclusive"
   i=0
   for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE"; do
     i=$((i+1))

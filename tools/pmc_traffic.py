@@ -63,7 +63,7 @@ def main():
         ghz = clock(sys.argv[4])
         if ghz:
             rec["loaded_clock_ghz"] = round(ghz, 3)
-    rec.update({"detail": res, "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python bench.py --steps 1 --warmup 1` ({os.path.basename(fd.rstrip('/'))}, "
+    rec.update({"detail": res, "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python bench.py --full --steps 1 --warmup 1` ({os.path.basename(fd.rstrip('/'))}, "
                                         f"{os.path.basename(wd.rstrip('/'))}); FETCH_SIZE x2 (gfx950), KiB -> bytes"})
     json.dump(rec, open(out, "w"), indent=1)
     print(open(out).read())
