@@ -240,9 +240,9 @@ int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_t njobs, vo
 int32_t sgx_debug_set_wgrad_group(int32_t rounds, int32_t item_mflop, int32_t xcd_order);
 /* Measurement aid: deep_slab bit 0 = 32-pixel slabs in the weight-gradient loop for the tiles whose two slabs fit 32 KB of LDS, bit 1 = ONE
  * slab of global loads in flight instead of two (one register set), bit 2 = the 64x64 tile on two waves instead of four, bit 3 = the
- * bf16x3 loop (three bf16 planes per slab, operands through the LDS transpose read, six bf16 MFMAs per product; the main tile shapes); `ablate` is
- * honoured only by a library built with -DSGX_WGRAD_LAB (tools/wgrad_lab.py: loop ablations, results are wrong by design).          */
-int32_t sgx_debug_set_wgrad_loop(int32_t deep_slab, int32_t ablate);
+ * bf16x3 loop (three bf16 planes per slab, operands through the LDS transpose read, six bf16 MFMAs per product; the main tile shapes).
+ * (The loop-ablation argument was removed; DESIGN.md r3j / r3k keeps its findings.)                                                  */
+int32_t sgx_debug_set_wgrad_loop(int32_t deep_slab);
 /* Arithmetic of the weight gradient (aten::convolution_backward's weight half under sg_trainer.py:611-647), process-wide.
  * 0: the fp32 matrix pipe.  1: the bf16x3 slab loop (three bf16 planes per slab, operands through the LDS transpose read, six bf16 MFMAs per
  * product: fp32-accurate).  2 (DEFAULT): mode 1, and the 3x3 pad-1 problems (stride 1 and 2) run the PATCH kernel - a workgroup owns a
@@ -257,20 +257,9 @@ int32_t sgx_debug_set_wgrad_patch(int32_t item_mflop, int32_t kb, int32_t min_fi
 /* Measurement aid: the reduction depth (taps x channels) from which conv math modes 2 / 4 / 5 run a problem in bf16x3 arithmetic
  * (0 = the default, 192).                                                                                                      */
 int32_t sgx_debug_set_bf3_min_depth(int32_t depth);
-/* measurement switch (round 5): the patch conv kernel's 32-filter tiles request the next tap's fragments ahead of this tap's MFMAs (1, default) or not (0) */
-int32_t sgx_debug_set_pconv_pipe(int32_t on);
-/* LDS (KB per CU, 0..120; 0 = off) the weight-gradient kernels leave free for kernels of other streams: their launches then request
- * dynamic LDS on top of their static allocation so that fewer of their workgroups fit a CU.  The weight gradients run on a side stream
- * under the backward pass; four of their workgroups hold 150 of a CU's 160 KB, and a data-gradient workgroup of the main stream (the
- * step's critical path) cannot start before one of them ends.                                                                */
-int32_t sgx_conv_set_wgrad_lds_reserve(int32_t kb);
-int32_t sgx_conv_get_wgrad_lds_reserve(void);
-/* A HIP stream whose kernels are dispatched to `percent` (10..100) of the device's CUs only, evenly spread over the chip
- * (hipExtStreamCreateWithCUMask).  For the weight gradients' side stream: their long-lived workgroups otherwise take every CU and the short
- * dependent kernels of the main stream - the step's critical path - queue between them.  *stream is a hipStream_t; release it with
- * sgx_stream_destroy.  SGX_ERR_UNSUPPORTED on the host emulation.                                                          */
-int32_t sgx_stream_create_partial(int32_t percent, void** stream);
-int32_t sgx_stream_destroy(void* stream);
+/* Removed measurement switches: the weight-gradient LDS reserve and the CU-masked stream (no gain:
+ * profiles/r4op_*), the patch kernel's fragment-pipelining switch (always on: r5f), the
+ * implicit-GEMM LDS pad (slower: profiles/r6l_occupancy_cap_lab.txt).                                                            */
 
 /* ConvTranspose2d kernel 2, stride 2 (+bias): modules/sampling.py:72-73 via yolo_stages.py:292-294.
  * x [N,H,W,C] -> y [N,2H,2W,K].  It is the adjoint of a 2x2 stride-2 convolution, so it runs on the same
@@ -565,8 +554,6 @@ int32_t sgx_debug_set_nms_split(int32_t on);
 /* Candidate selection of the multi-label path: 1 (default) = one pass over the scores behind a threshold estimated from a 1/32 sample (exact:
  * stage 2 falls back to streaming an image whose list came out short or overflowed), 0 = the exact three-pass histogram selection. */
 int32_t sgx_debug_set_nms_selection(int32_t sampled);
-/* measurement: bytes of dynamic LDS (0 .. 32768) added to every implicit-GEMM launch - an occupancy cap without another kernel build */
-int32_t sgx_debug_set_igemm_lds_pad(int32_t bytes);
 /* Where a multi-label sgx_nms call with a workspace records, per image, that stage 2 fell back from stage 1's candidate list to streaming
  * the image's raw scores (exact rows either way, many times slower): int32 index offset_ints + b * stride_ints of the call's workspace
  * holds 1 / 0 for image b once the call's stream work is complete.  Benches and tests assert it stays 0 on their inputs.     */

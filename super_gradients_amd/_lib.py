@@ -134,19 +134,13 @@ PROTOTYPES = {
     "sgx_conv2d_bwd_weight_group_sizes": (_i32, [POINTER(WgradJob), _i32, POINTER(c_int64), POINTER(c_int64)]),
     "sgx_conv2d_bwd_weight_group": (_i32, [POINTER(WgradJob), _i32, _P, _i64, _P, _i64, _P]),
     "sgx_debug_set_wgrad_group": (_i32, [_i32] * 3),
-    "sgx_debug_set_wgrad_loop": (_i32, [_i32] * 2),
+    "sgx_debug_set_wgrad_loop": (_i32, [_i32]),
     "sgx_conv_set_wgrad_math": (_i32, [_i32]),
     "sgx_conv_get_wgrad_math": (_i32, []),
     "sgx_debug_set_wgrad_patch": (_i32, [_i32] * 3),
     "sgx_debug_set_bf3_min_depth": (_i32, [_i32]),
-    "sgx_debug_set_pconv_pipe": (_i32, [_i32]),
-    "sgx_conv_set_wgrad_lds_reserve": (_i32, [_i32]),
-    "sgx_conv_get_wgrad_lds_reserve": (_i32, []),
-    "sgx_stream_create_partial": (_i32, [_i32, ctypes.POINTER(ctypes.c_void_p)]),
-    "sgx_stream_destroy": (_i32, [ctypes.c_void_p]),
     "sgx_debug_set_nms_split": (_i32, [_i32]),
     "sgx_debug_set_nms_selection": (_i32, [_i32]),
-    "sgx_debug_set_igemm_lds_pad": (_i32, [_i32]),
     "sgx_debug_nms_fallback_slot": (_i32, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
     "sgx_convT2x2_workspace": (_i64, [_i32] * 5),
     "sgx_convT2x2_fwd": (_i32, [_i32] * 5 + [_P, _i64, _i64, _P, _P, _P, _i64, _i64, _P, _i64, _P]),
@@ -253,11 +247,10 @@ def lib():
         wgg = os.environ.get("SGX_WGRAD_GROUP")  # measurement switch of the grouped weight gradient: "rounds,item_mflop,xcd_order" (0 = default)
         if wgg:
             _LIB.sgx_debug_set_wgrad_group(*[int(v) for v in wgg.split(",")])
-        # measurement switches of the weight-gradient loop: 32-pixel slabs (small tiles); ablation bits (honoured by -DSGX_WGRAD_LAB builds only);
-        # one tile shape for every layer "bnk,bj"
-        if os.environ.get("SGX_WGRAD_SLAB") == "32" or os.environ.get("SGX_WGRAD_ABLATE") or os.environ.get("SGX_WGRAD_PF"):
-            _LIB.sgx_debug_set_wgrad_loop(int(os.environ.get("SGX_WGRAD_SLAB") == "32") + 2 * int(os.environ.get("SGX_WGRAD_PF") == "1"),
-                                          int(os.environ.get("SGX_WGRAD_ABLATE", "0")))
+        # measurement switches of the weight-gradient loop: 32-pixel slabs (small tiles), one slab of loads in flight; one tile shape for
+        # every layer "bnk,bj"
+        if os.environ.get("SGX_WGRAD_SLAB") == "32" or os.environ.get("SGX_WGRAD_PF"):
+            _LIB.sgx_debug_set_wgrad_loop(int(os.environ.get("SGX_WGRAD_SLAB") == "32") + 2 * int(os.environ.get("SGX_WGRAD_PF") == "1"))
         wgm = os.environ.get("SGX_WGRAD_MATH")  # "fp32" | "bf16x3" (slab loop only) | "patch" (the default: bf16x3 + the patch kernel)
         if wgm:
             if wgm not in WGRAD_MATH:
@@ -267,10 +260,6 @@ def lib():
             _LIB.sgx_debug_set_bf3_min_depth(int(os.environ["SGX_BF3_MIN_DEPTH"]))
         if os.environ.get("SGX_FILTER_PLANES"):  # measurement: 0 = every bf16x3 launch splits its filter while staging (round 5)
             _LIB.sgx_debug_set_filter_planes(int(os.environ["SGX_FILTER_PLANES"]))
-        if os.environ.get("SGX_PCONV_PIPE"):  # measurement: second fragment set for the patch kernel's 32-filter tiles
-            _LIB.sgx_debug_set_pconv_pipe(int(os.environ["SGX_PCONV_PIPE"]))
-        if os.environ.get("SGX_WGRAD_LDS_RESERVE"):  # KB of every CU's LDS the weight-gradient kernels leave to the main stream
-            _LIB.sgx_conv_set_wgrad_lds_reserve(int(os.environ["SGX_WGRAD_LDS_RESERVE"]))
         if os.environ.get("SGX_WGRAD_PATCH"):  # measurement: "item_mflop,kb,min_fill_pct"
             _LIB.sgx_debug_set_wgrad_patch(*[int(v) for v in os.environ["SGX_WGRAD_PATCH"].split(",")])
         if os.environ.get("SGX_WGRAD_TILE"):

@@ -26,8 +26,6 @@
 #include <mutex>
 #include <unordered_map>
 #include <vector>
-#include <cstdlib>
-#define SGX_CONV_WAVE_PRIO_DEFAULT 0
 
 // ------------------------------------------------------------------------------------------------
 // Optional per-launch timing of the two MFMA kernel classes (bench.py's roofline leg): HIP events recorded on the
@@ -156,14 +154,6 @@ extern "C" int32_t sgx_prof_summary(int32_t, double* ms, double* flops, int64_t*
 //   per load         : one v_add + one v_cndmask (masked lanes get SGX_BUF_OOB and the buffer bounds check returns 0).
 // FLAT (C < 16, the RGB stem): the GEMM-K axis is the flattened (tap, channel) axis, a 16-wide slab spans 16/C taps.
 // ------------------------------------------------------------------------------------------------
-// SGX_WAVE_PRIO (environment, read once) bit 2: the forward / data-gradient kernels run their waves at issue priority 1
-static int conv_wave_prio() {
-    static const int mode = [] {
-        const char* e = getenv("SGX_WAVE_PRIO");
-        return ((e ? atoi(e) : SGX_CONV_WAVE_PRIO_DEFAULT) >> 2) & 1;
-    }();
-    return mode;
-}
 struct IgemmParams {
     const float* A;
     const float* Wt;
@@ -214,8 +204,6 @@ struct IgemmParams {
     // g = v * act'(scale t + shift) from the value v it is about to store and leaves sum g, sum g (t - mean) per column in row block
     // (req_row0 + tile row) of the request's partials - the rows sgx_bn_bwd_reduce would have produced with a pass over dy and t.
     int nreq, req_row0;
-    int lab;  // measurement builds (-DSGX_IGEMM_LAB, tools/conv_lab.py --ablate) only: see IGL below; the product build never reads it
-    int prio;  // raise the waves' issue priority over the side stream's weight-gradient waves (SGX_WAVE_PRIO bit 2; sgx_common.h)
     struct {
         const float* t;
         const float* scale;
@@ -272,21 +260,6 @@ __device__ __forceinline__ void sgx_bnreq_publish(const IgemmParams& p, int col,
         }
 }
 
-// Ablation lab of the implicit-GEMM loop (measurement builds only: -DSGX_IGEMM_LAB; sgx_debug_set_igemm_lab; tools/conv_lab.py --ablate).
-// Bits of IgemmParams::lab - each removes ONE component of the K loop (results are garbage, timings are what the lab is for):
-//   1 no global loads behind the first slab (the first slab's registers are staged again and again)   2 no LDS stores behind the first slab
-//   4 no fragment reads / MFMAs   8 no bf16 split (raw bits are stored: same stores, no vector work)   16 no epilogue (nothing is written)
-// The product build compiles IGL(b) to `false`.
-#ifdef SGX_IGEMM_LAB
-#define IGL(b) ((p.lab & (b)) != 0)
-static std::atomic<int> g_ig_lab{0};
-extern "C" int32_t sgx_debug_set_igemm_lab(int32_t bits) {
-    g_ig_lab = bits;
-    return SGX_OK;
-}
-#else
-#define IGL(b) false
-#endif
 #define IG_BK 16
 #define IG_LD 20
 // ---- "bf16x3" arithmetic (MATH = 1): fp32 operands split into three bf16 pieces (round-to-nearest, each residual exact in fp32), products hi*hi + hi*mid + mid*hi + mid*mid + hi*lo + lo*hi on the bf16 matrix pipe
@@ -319,10 +292,8 @@ extern "C" int32_t sgx_debug_set_igemm_lab(int32_t bits) {
 #ifndef IG_WPR_MIN_WAVES_6464
 #define IG_WPR_MIN_WAVES_6464 4  // (5 - round 5 - spilled 4 dwords)
 #endif
-template <int BM, int BN, int WM, int WN, int MATH, int KD, int PH2, int NBUF, int WPL = 0, int PP = 0>
+template <int BM, int BN, int WM, int WN, int MATH, int KD, int PH2, int NBUF, int WPL = 0>
 constexpr int igemm_min_waves() {
-    // (ping-pong form: 512-thread workgroups, two per CU by their LDS - four waves per SIMD, 128 registers)
-    if (PP) return 4;
     // Round 6: NO instantiation that a launch can select may spill (tools/kernel_regs.py --check, tests/test_tools.py): round 5 shipped the
     // two-source 64x64 form at 96 registers with 7 spilled dwords (6 launches per step), the register-fragment forms with 1-4.  A bound is
     // lowered by one wave wherever the allocation under it spilled.
@@ -334,20 +305,9 @@ constexpr int igemm_min_waves() {
     // (the two-source form carries a second source's offsets and masks: four waves - 128 registers - is what it fits without spilling)
     return (MATH == 1 && KD == 32 && PH2 <= IG_BF3_MIN_WAVES_PH2 && BM / (WM * 32) == 1 && BN / (WN * 32) == 1) ? (PH2 == 1 ? IG_BF3_MIN_WAVES - 1 : IG_BF3_MIN_WAVES) : 1;
 }
-// PP = 1 (round 6, "ping-pong"): a 512-thread workgroup is TWO wave groups of WM x WN waves, each with its own output tile, LDS slabs and
-// epilogue scratch, running the one-buffer loop's two phases of a slab - STAGE (wait for the slab's loads, split, LDS stores, issue the
-// next slab's loads) and COMPUTE (fragment reads + MFMAs) - half a period apart: while group 0 computes slab k, group 1 stages its slab k,
-// and vice versa, one workgroup-wide barrier per phase.  Why: the ablation lab (profiles/r6c_igemm_ablation_*.txt) has the staging-only
-// and the compute-only versions of a launch at ~0.63 of the whole launch EACH - five independent workgroups per CU do not overlap their
-// phases (they convoy: loads return together, everybody splits together, everybody queues for the matrix pipe together); here the
-// complementary pairing (matrix beside memory / vector work on every SIMD, MI355X_MICROARCH.md "Two waves per SIMD") is by construction.
-// Same products in the same order per tile as PP = 0: bit-identical results.
-template <int BM, int BN, int WM, int WN, bool FLAT, int MATH = 0, int KD = IG_BK, int NBUF = 2, int PH2 = 0, int WPL = 0, int PP = 0>
-__global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, BN, WM, WN, MATH, KD, PH2, NBUF, WPL, PP>())) void igemm_kernel(IgemmParams p) {
+template <int BM, int BN, int WM, int WN, bool FLAT, int MATH = 0, int KD = IG_BK, int NBUF = 2, int PH2 = 0, int WPL = 0>
+__global__ __launch_bounds__(WM * WN * 64, (igemm_min_waves<BM, BN, WM, WN, MATH, KD, PH2, NBUF, WPL>())) void igemm_kernel(IgemmParams p) {
     static_assert(!WPL || (MATH == 1 && KD == 32 && NBUF == 1 && !FLAT), "pre-split filter planes: the one-buffer 32-deep bf16x3 loop");
-    static_assert(!PP || (MATH == 1 && KD == 32 && NBUF == 1 && !FLAT && PH2 == 0 && WPL <= 1), "ping-pong: the one-buffer 32-deep bf16x3 loop, one source");
-    if (p.prio) SGX_WAVE_PRIO(1);
-    constexpr int G = PP ? 2 : 1;  // wave groups (tiles) per workgroup
     static_assert((KD == 16 && NBUF == 2) || (KD == 32 && !FLAT && NBUF == 1) || (KD == 32 && !FLAT && NBUF == 2 && MATH == 1) ||
                       (KD == 32 && !FLAT && NBUF == 3 && MATH == 0 && PH2 == 0),
                   "32-deep slabs: channel-chunked K axis; one LDS buffer, (bf16x3) the two-buffer pipelined loop, or (fp32, NBUF = 3) all slabs up front");
@@ -388,33 +348,23 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
     auto swz = [](int row, int dw) { return KD == 16 ? IG_SWZ(row, dw) : (dw ^ (((row >> 2) & 3) << 2)); };
     constexpr int SLABS = LBUF * (BM + (WPR ? 0 : BN)) * ROWW, STAGE = WM * WN * 32 * 32;   // operand slabs; epilogue staging patches (reuse the slabs)
     constexpr int SMEM1 = SLABS > STAGE ? SLABS : STAGE;
-    __shared__ __attribute__((aligned(16))) float smem_s[G * SMEM1];
-    __shared__ long long rowoff_s[G][BM];
+    __shared__ __attribute__((aligned(16))) float smem[SMEM1];
+    __shared__ long long rowoff[BM];
     __shared__ long long rowoff2[PH2 == 1 ? BM : 1];  // offsets into addend2 (two-source data gradient only)
-    __shared__ long long rowoffT_s[G][PH2 == 2 ? 1 : SGX_MAX_BN_REQ][PH2 == 2 ? 1 : BM];  // offsets into the requests' saved conv outputs
-    __shared__ float red_s[G][(PH2 == 2 ? 5 : 2) * WM * BN];
+    __shared__ long long rowoffT[PH2 == 2 ? 1 : SGX_MAX_BN_REQ][PH2 == 2 ? 1 : BM];  // offsets into the requests' saved conv outputs
+    __shared__ float red[(PH2 == 2 ? 5 : 2) * WM * BN];
 
-    // (PP: everything below is written for ONE wave group - `tid`, `wave` count inside the group, the LDS objects are the group's own)
-    const int grp = PP ? (int)threadIdx.x / NTH : 0;
-    const int tid = PP ? (int)threadIdx.x - grp * NTH : (int)threadIdx.x;
+    const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    float* const smem = smem_s + grp * SMEM1;
     float* const As = smem;
     float* const Bs = smem + LBUF * BM * ROWW;
-    long long* const rowoff = rowoff_s[grp];
-    auto rowoffT = rowoffT_s[grp];
-    float* const red = red_s[grp];
 
     // XCD-aware tile assignment (block b runs on XCD b%8; give each XCD a contiguous run of tiles)
     const int bid = blockIdx.x;
-    const int lin0 = ((bid & 7) * p.chunk + (bid >> 3)) * G;
-    if (lin0 >= p.nblk) return;  // whole workgroup leaves together (before any barrier)
-    // (PP: an odd tile count leaves the last workgroup's second group without a tile - it repeats the first group's and writes nothing: the
-    // barriers of both groups must match)
-    const bool active = lin0 + grp < p.nblk;
-    const int lin = active ? lin0 + grp : lin0;
+    const int lin = (bid & 7) * p.chunk + (bid >> 3);
+    if (lin >= p.nblk) return;  // whole workgroup leaves together (before any barrier)
     const int mtile = sgx_fdiv(lin, p.fd_nt), ntile = lin - mtile * p.nt;
     const int m0 = mtile * BM, n0 = ntile * BN;
     const int hw = p.Ha * p.Wa;
@@ -515,7 +465,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
       if (tid < BM) {
         const int m = m0 + tid;
         long long off = -1;
-        if ((!PP || active) && m < p.M) {
+        if (m < p.M) {
             const int img = sgx_fdiv(m, p.fd_hw);
             const int rem = m - img * hw;
             const int a = sgx_fdiv(rem, p.fd_wa);
@@ -554,22 +504,17 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
             const int tapoff = s_ti * rowstep + s_tj * pixstep + s_ck * (KD * 4);
             const int woff = WPL ? s_ck * wp_ckstep + tbit * wp_tapstep : (tbit * p.C + s_ck * KD) * 4;
             const bool cok = live && s_ck * KD + chunk4 < p.C;
-            const bool lab_noload = IGL(1) && s_kt > 0;
-            if (!lab_noload) {
 #pragma unroll
             for (int j = 0; j < AJ; ++j) {
                 const bool ok = cok && ((amask[j] >> (tbit & 63)) & 1ull);
                 ra[j] = sgx_buf_ld4(bufA, ok ? (unsigned)(aoff[j] + tapoff) : SGX_BUF_OOB);
             }
-            }
             // (WPL: C is a multiple of 32 - no ragged channel chunk to mask on the filter side)
             if constexpr (WPR) {
                 wp_woff = woff;  // the fragments of this slab are fetched by load_bfrags, behind the MFMAs that read the current ones
             } else if constexpr (WPL) {
-                if (!lab_noload) {
 #pragma unroll
                 for (int j = 0; j < BJ; ++j) rb[j] = sgx_buf_ld4_so(bufB, live ? wp_voff[(WPL == 1) ? j : 0] : SGX_BUF_OOB, (unsigned)woff);
-                }
             } else {
 #pragma unroll
                 for (int j = 0; j < BJ; ++j) rb[j] = sgx_buf_ld4(bufB, (cok && bok[j]) ? (unsigned)(boff[j] + woff) : SGX_BUF_OOB);
@@ -591,11 +536,6 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
                 const int row = lrow + RPP * j;
                 if (BM % RPP == 0 || row < BM) {
                     uint2 h, m, l;
-                    if (IGL(8)) {
-                        h = make_uint2(sgx_f2u(ra[j].x), sgx_f2u(ra[j].y));
-                        m = make_uint2(sgx_f2u(ra[j].z), sgx_f2u(ra[j].w));
-                        l = h;
-                    } else
                     sgx_split3(ra[j], h, m, l);
                     unsigned* d = reinterpret_cast<unsigned*>(As) + (buf * 3 * BM + row) * LDPW + swz(row, chunk4 >> 1);
                     *reinterpret_cast<uint2*>(d) = h;
@@ -899,30 +839,6 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
             }
             continue;
         }
-        if constexpr (PP != 0) {
-            // ---- round 6: the ping-pong loop.  Phase ph: group g is at q = ph - g of its own sequence STAGE(0) COMPUTE(0) STAGE(1) COMPUTE(1) ...
-            // (even q: stage slab q / 2 out of the registers and issue the loads of slab q / 2 + 1; odd q: the MFMAs of slab q / 2) - the
-            // groups are one phase apart, so every phase pairs one group's matrix work with the other's memory / vector work; one
-            // workgroup-wide barrier per phase orders a group's own LDS hand-overs (stores -> reads -> next stores).  Group 0 idles in the
-            // last phase, group 1 in the first: both then run the epilogue with matching barriers.
-            if (nkt > 0) load_tile();
-            compute_rowoff();
-            const int nph = 2 * nkt + 1;
-            for (int ph = 0; ph < nph; ++ph) {
-                const int q = ph - grp;
-                if (q >= 0 && q < 2 * nkt) {
-                    if ((q & 1) == 0) {
-                        if (!IGL(2) || q == 0) store_tile(0);
-                        if ((q >> 1) + 1 < nkt) load_tile();
-                    } else if (!IGL(4)) {
-                        compute_bf3(0, 0);
-                        compute_bf3(0, 1);
-                    }
-                }
-                __syncthreads();
-            }
-            continue;
-        }
         if (nkt > 0) load_tile();
         if constexpr (WPR) {
             if (nkt > 0) {
@@ -944,17 +860,15 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
                     compute_bf3(0, 1);
                     if (kt + 1 < nkt) load_bfrags(1);
                 } else if (BF3) {
-                    if (!IGL(4)) {
-                        compute_bf3(0, 0);
-                        compute_bf3(0, 1);
-                    }
+                    compute_bf3(0, 0);
+                    compute_bf3(0, 1);
                 } else {
                     compute_f32(0, 0);
                     compute_f32(0, 16);
                 }
                 __syncthreads();
                 if (kt + 1 < nkt) {
-                    if (!IGL(2)) store_tile(0);
+                    store_tile(0);
                     __syncthreads();
                 }
                 continue;
@@ -1084,7 +998,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
             sgx_wave_lds_sync();  // the staging patch is private to the wave
             // (Round 5: the four row offsets and the four staged rows of a block come out of LDS TOGETHER, ahead of the per-row work.  The
             // per-row form read the offset -> waited -> branched -> read the staged row -> waited -> stored, four times over: two exposed
-            // LDS round trips per row, 1000-1500 cycles per block in the stamps of tools/pconv_timing.py, r5t.)
+            // LDS round trips per row, 1000-1500 cycles per block in the stamps of an instrumented build, r5t.)
             long long offq[4];
             float4 vq[4];
 #pragma unroll
@@ -1120,7 +1034,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
                             cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
                             cq.x += v.x * v.x; cq.y += v.y * v.y; cq.z += v.z * v.z; cq.w += v.w * v.w;
                         }
-                        if (!IGL(16)) sgx_st4(yp, make_float4(sgx_act(v.x, p.act), sgx_act(v.y, p.act), sgx_act(v.z, p.act), sgx_act(v.w, p.act)));
+                        sgx_st4(yp, make_float4(sgx_act(v.x, p.act), sgx_act(v.y, p.act), sgx_act(v.z, p.act), sgx_act(v.w, p.act)));
                     } else {
                         float e[4] = {v.x, v.y, v.z, v.w};
                         float* se[4] = {&cs.x, &cs.y, &cs.z, &cs.w};
@@ -1161,7 +1075,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
     }
     if (p.stat_partials || p.nreq > 0) {
         __syncthreads();
-        if (tid < BN && (!PP || active)) {
+        if (tid < BN) {
             int col = n0 + tid;
             if (col < p.Nout) {
                 float s = 0.f, q = 0.f;
@@ -1205,31 +1119,6 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP ? 2 : 1), (igemm_min_waves<BM, B
 // accumulators).  PH2 as in igemm_kernel: 1 = second source (1x1, its own tensor) into the same accumulator - the QARepVGG data
 // gradient; 2 = second filter on the centre tap into a second output - the QARepVGG forward pair, with the five BatchNorm moments.
 // ------------------------------------------------------------------------------------------------
-// Phase timing of the patch kernel (measurement builds only: -DSGX_PCONV_TIMING[=2], tools/pconv_timing.py, tools/visits/r5_visit12.sh): lane 0
-// of wave 0 of every workgroup stamps s_memtime at ten points (=2: a second set inside the two-output epilogue) and leaves the stamps in
-// a caller-provided buffer [workgroups][16].  The product build compiles none of it.
-#ifdef SGX_PCONV_TIMING
-__device__ unsigned long long* g_pc_timing = nullptr;
-extern "C" int32_t sgx_debug_set_pconv_timing(void* buf) {
-    unsigned long long* b = (unsigned long long*)buf;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_pc_timing), &b, sizeof(b)) == hipSuccess ? SGX_OK : SGX_ERR_HIP;
-}
-#define PC_T(i) (pc_ts[i] = __builtin_readcyclecounter())
-#define PC_TOUT()                                                                                      \
-    do {                                                                                               \
-        PC_T(9);                                                                                       \
-        if (threadIdx.x == 0 && g_pc_timing)                                                           \
-            for (int q_ = 0; q_ < 12; ++q_) g_pc_timing[(long)blockIdx.x * 16 + q_] = pc_ts[q_];       \
-    } while (0)
-#else
-#define PC_T(i) ((void)0)
-#define PC_TOUT() ((void)0)
-#endif
-#if defined(SGX_PCONV_TIMING) && SGX_PCONV_TIMING == 2
-#define PC_E(i) (pc_ts[i] = __builtin_readcyclecounter())
-#else
-#define PC_E(i) ((void)0)
-#endif
 #define PC_TH 8
 #define PC_TW 16
 #define PC_PW (PC_TW + 2)              // patch pitch (pixels)
@@ -1238,7 +1127,6 @@ extern "C" int32_t sgx_debug_set_pconv_timing(void* buf) {
 template <int BN, int WM, int WN, int PH2, bool FPIPE = true, bool WPL = false>
 __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(IgemmParams p) {
     static_assert(4 % WM == 0, "WM divides the four 32-row sub-tiles");
-    if (p.prio) SGX_WAVE_PRIO(1);
     constexpr int NTH = WM * WN * 64;
     constexpr int BM = PC_TH * PC_TW;           // 128 output pixels = 4 sub-tiles of 32 MFMA rows
     constexpr int TM = 4 / WM, TN = BN / (32 * WN);
@@ -1270,10 +1158,6 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
     __shared__ float red[(PH2 == 2 ? 5 : 2) * WM * BN];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef SGX_PCONV_TIMING
-    unsigned long long pc_ts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    PC_T(0);
     const int wm = wave / WN, wn = wave % WN;
     const int bid = blockIdx.x;
     const int lin = (bid & 7) * p.chunk + (bid >> 3);
@@ -1505,19 +1389,14 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
             if (!p.A2) break;
             setup_src(p.A2, p.Wt2, p.Hin2, p.Win2, p.Th2, p.Tw2, p.dh02, p.dw02, p.dstep2, p.a2_ld_pix, p.a2_ld_img, p.w2_ld_n, p.a2_bytes, p.w2_bytes, p.Wp2, p.wp2_bytes);
         }
-        if (src == 0) PC_T(1);
         load_chunk(0);
         if (src == 0) compute_rowoff();
-        if (src == 0) PC_T(2);
         for (int chunk = 0; chunk < cpt; ++chunk) {
             // every wave is past its last fragment read of the previous chunk (barrier below); this chunk has been travelling in registers
             store_chunk();
-            if (src == 0 && chunk == 0) PC_T(3);
-            if (src == 0 && chunk == 1) PC_T(7);
             __syncthreads();
-            if (src == 0 && chunk == 0) PC_T(4);
             if (chunk + 1 < cpt) load_chunk(chunk + 1);
-            if constexpr (!FPIPE) {  // measurement variant 8: read - wait - multiply per tap (one fragment set: fewer registers)
+            if constexpr (!FPIPE) {  // read - wait - multiply per tap (one fragment set: fewer registers)
                 Frags f;
                 for (int t = 0; t < ntaps; ++t) {
                     load_frags(f, t, tap_off(t));
@@ -1527,9 +1406,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
                     load_frags(f, NF - 1, PC_PW + 1);
                     mfma_tap(f, accu, accu2);
                 }
-                if (src == 0 && chunk == 0) PC_T(5);
                 __syncthreads();
-                if (src == 0 && chunk == 0) PC_T(6);
                 continue;
             }
             Frags fa, fb;
@@ -1549,12 +1426,9 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
             } else if constexpr (DUAL) {
                 mfma_tap(fa, accu, accu2);
             }
-            if (src == 0 && chunk == 0) PC_T(5);
             __syncthreads();
-            if (src == 0 && chunk == 0) PC_T(6);
         }
     }
-    PC_T(8);
 
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -1566,7 +1440,6 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
                 if (DUAL) accu[DUAL ? i : 0][DUAL ? j : 0][r] += accu2[DUAL ? i : 0][DUAL ? j : 0][r];
             }
     // ---- epilogues: as igemm_kernel's (32x32 accumulators transposed through a per-wave LDS patch -> 16-byte stores) ------------------------
-    PC_T(11);
     float* const stage = smem + wave * (32 * 32);
     const int sr = lane >> 3, sc4 = (lane & 7) * 4;
     const bool full = oy0 + PC_TH <= p.Ha && ox0 + PC_TW <= p.Wa;
@@ -1594,7 +1467,6 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
 #pragma unroll
                 for (int t = 0; t < 5; ++t) red[(t * WM + wm) * BN + wn * TN * 32 + j * 32 + lane] = st[t];
             }
-            PC_E(1);
             const int col = n0 + wn * TN * 32 + j * 32 + sc4;
             const bool colok = col < p.Nout;
             float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1607,7 +1479,6 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
                     for (int r = 0; r < 16; ++r)
                         stage[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = o == 0 ? acc[i][j][r] : accu[DUAL ? i : 0][DUAL ? j : 0][r];
                     sgx_wave_lds_sync();  // the staging patch is private to the wave
-                    if (o == 0) PC_E(2); else PC_E(4);
                     long long offq[4];
                     float4 vq[4];
 #pragma unroll
@@ -1626,12 +1497,10 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
                             sgx_st4((o == 0 ? p.Y : p.Y2) + off + col, v);
                         }
                     }
-                    if (o == 0) PC_E(3); else PC_E(5);
                     sgx_wave_lds_sync();  // the staging patch is private to the wave
                 }
             }
         }
-        PC_T(10);
         __syncthreads();
         if (tid < BN) {
             const int col = n0 + tid;
@@ -1645,7 +1514,6 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
                 }
             }
         }
-        PC_TOUT();
         return;
     }
 #pragma unroll
@@ -1667,7 +1535,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
             sgx_wave_lds_sync();  // the staging patch is private to the wave
             // (Round 5: the four row offsets and the four staged rows of a block come out of LDS TOGETHER, ahead of the per-row work.  The
             // per-row form read the offset -> waited -> branched -> read the staged row -> waited -> stored, four times over: two exposed
-            // LDS round trips per row, 1000-1500 cycles per block in the stamps of tools/pconv_timing.py, r5t.)
+            // LDS round trips per row, 1000-1500 cycles per block in the stamps of an instrumented build, r5t.)
             long long offq[4];
             float4 vq[4];
 #pragma unroll
@@ -1743,7 +1611,6 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
             }
         }
     }
-    PC_TOUT();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1851,7 +1718,7 @@ extern "C" int32_t sgx_conv_tuning_load(const int32_t* entries, int32_t n) {
                               (e[9] == 0) == (e[10] == 0),  // all 16 tiles of {32, 64, 96, 128}^2 are instantiated
                           "conv_tuning_load: entry %d: no weight-gradient kernel (tile %dx%d, split target %d)", i, e[9], e[10], e[11]);
         else
-            SGX_CHECK_ARG((e[9] == 0 || e[9] == 64 || e[9] == 128) && wide && (e[11] == 0 || e[11] == 6 || e[11] == 7 || e[11] == 11 || e[11] == 12 || e[11] == 14),
+            SGX_CHECK_ARG((e[9] == 0 || e[9] == 64 || e[9] == 128) && wide && (e[11] == 0 || e[11] == 6 || e[11] == 7 || e[11] == 11 || e[11] == 12),
                           "conv_tuning_load: entry %d: no kernel (tile %dx%d, variant %d)", i, e[9], e[10], e[11]);
         m[std::array<int, 9>{e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8]}] = TuneVal{e[9], e[10], e[11]};
     }
@@ -1927,28 +1794,17 @@ static bool igemm_deep_slabs(const IgemmParams& p) { return conv_variant() != 7 
         else if (bm == 64 && bn == 32) launch_igemm<64, 32, 2, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);     \
         else SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv (two sources): no tile %dx%d", bm, bn);                                \
     } while (0)
-// measurement: dynamic LDS added to every implicit-GEMM launch (bytes, <= 32 KB) - fewer workgroups per CU without touching the kernel
-static std::atomic<int> g_ig_lds_pad{0};
-extern "C" int32_t sgx_debug_set_igemm_lds_pad(int32_t bytes) {
-    SGX_CHECK_ARG(bytes >= 0 && bytes <= 32768, "igemm LDS pad %d (0 .. 32768 bytes)", bytes);
-    g_ig_lds_pad = bytes;
-    return SGX_OK;
-}
-template <int BM, int BN, int WM, int WN, bool FLAT, int MATH = 0, int KD = IG_BK, int NBUF = 2, int PH2 = 0, int WPL = 0, int PP = 0>
+template <int BM, int BN, int WM, int WN, bool FLAT, int MATH = 0, int KD = IG_BK, int NBUF = 2, int PH2 = 0, int WPL = 0>
 static void launch_igemm(IgemmParams& p, void* stream) {
-    p.prio = conv_wave_prio();
     p.mt = sgx_cdiv(p.M, BM);
     p.nt = sgx_cdiv(p.Nout, BN);
     p.nblk = p.mt * p.nt;
-    p.chunk = sgx_cdiv(PP ? sgx_cdiv(p.nblk, 2) : p.nblk, 8);  // (PP: a workgroup owns two consecutive tiles)
+    p.chunk = sgx_cdiv(p.nblk, 8);
     p.fd_nt = sgx_make_fastdiv(p.nt);
     p.fd_hw = sgx_make_fastdiv(p.Ha * p.Wa);
     p.fd_wa = sgx_make_fastdiv(p.Wa);
     int grid = p.chunk * 8;
-#ifdef SGX_IGEMM_LAB
-    p.lab = g_ig_lab.load(std::memory_order_relaxed);
-#endif
-    SGX_LAUNCH((igemm_kernel<BM, BN, WM, WN, FLAT, MATH, KD, NBUF, PH2, WPL, PP>), dim3(grid), dim3(WM * WN * 64 * (PP ? 2 : 1)), (size_t)g_ig_lds_pad.load(std::memory_order_relaxed), stream, p);
+    SGX_LAUNCH((igemm_kernel<BM, BN, WM, WN, FLAT, MATH, KD, NBUF, PH2, WPL>), dim3(grid), dim3(WM * WN * 64), 0, stream, p);
 }
 
 // ---- pconv dispatch ------------------------------------------------------------------------------------------------------------------
@@ -1976,19 +1832,13 @@ static bool pconv_ok(const IgemmParams& p, int ph2) {
     return true;
 }
 static std::atomic<long> g_fp_hits{0};  // launches that read pre-split filter planes (see fplanes_attach)
-static std::atomic<int> g_pconv_pipe32{1};  // r5f: 716.0 -> 718.8 images/s (twice each, same box)
-extern "C" int32_t sgx_debug_set_pconv_pipe(int32_t on) {  // measurement switch, see launch_pconv
-    g_pconv_pipe32 = on ? 1 : 0;
-    return SGX_OK;
-}
 template <int BN, int WM, int WN, int PH2>
 static void launch_pconv(IgemmParams& p, void* stream) {
     // two fragment sets where they do not cost a wave of occupancy (r3f lab: the 64-filter tile gains 4-6 %, the 32-filter tiles - three
-    // workgroups per CU with one set, two with two - lose 5-15 %); measurement: variant 8 = never, 9 = always
+    // workgroups per CU with one set, two with two - lose 5-15 %); measurement: variant 9 = always
     // (round 5: the 32-filter tiles of the one- / two-source forms take the second fragment set as well - under their launch bound of three
-    // waves per SIMD they fit it without spilling, 137 / 165 registers; the two-output form does not.  sgx_debug_set_pconv_pipe(0): off)
-    const int var = conv_variant();
-    const bool fpipe = var == 9 || (var != 8 && (BN == 64 || (PH2 != 2 && g_pconv_pipe32.load(std::memory_order_relaxed))));
+    // waves per SIMD they fit it without spilling, 137 / 165 registers; the two-output form does not.  r5f: 716.0 -> 718.8 images/s)
+    const bool fpipe = conv_variant() == 9 || BN == 64 || PH2 != 2;
     p.mt = pconv_tiles(p.M / (p.Ha * p.Wa), p.Ha, p.Wa);
     p.nt = sgx_cdiv(p.Nout, BN);
     p.nblk = p.mt * p.nt;
@@ -1997,7 +1847,6 @@ static void launch_pconv(IgemmParams& p, void* stream) {
     p.fd_txy = sgx_make_fastdiv(sgx_cdiv(p.Wa, PC_TW) * sgx_cdiv(p.Ha, PC_TH));
     p.fd_tx = sgx_make_fastdiv(sgx_cdiv(p.Wa, PC_TW));
     p.stat_nblk = p.mt;
-    p.prio = conv_wave_prio();
     // pre-split filter planes (fplanes_attach): every filter of the launch has them, or none is used
     const bool wpl = p.Wp && (!(PH2 && p.A2) || p.Wp2);
     if (wpl) g_fp_hits.fetch_add(1, std::memory_order_relaxed);
@@ -2197,7 +2046,7 @@ static int32_t run_igemm(IgemmParams& p, int bm, int bn, void* stream, int ph2 =
                 // register fragments (mode 2, or variant 12; the tiles of one 32-filter block per wave) - by default the two-output forward
                 // pair takes them (r5ac lab: -6 %) and the two-source data gradient does not (+8 %)
                 const int fpm = g_fp_on.load(std::memory_order_relaxed);
-                const bool wpr = (fpm == 2 || conv_variant() == 12 || (fpm == 1 && ph2 == 2 && conv_variant() != 13)) && bn <= 64;
+                const bool wpr = (fpm == 2 || conv_variant() == 12 || (fpm == 1 && ph2 == 2)) && bn <= 64;
                 if (wpr && ph2 == 1) SGX_IGEMM_TILES_PH2_W(1, 32, 1, 1, 2);
                 else if (wpr) SGX_IGEMM_TILES_PH2_W(1, 32, 1, 2, 2);
                 else if (ph2 == 1) SGX_IGEMM_TILES_PH2_W(1, 32, 1, 1, 1);
@@ -2226,12 +2075,6 @@ static int32_t run_igemm(IgemmParams& p, int bm, int bn, void* stream, int ph2 =
             if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, 1, 32, 2, 0>(p, stream);
             else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, 1, 32, 2, 0>(p, stream);
             else launch_igemm<64, 32, 2, 1, false, 1, 32, 2, 0>(p, stream);
-        } else if (igemm_deep_slabs(p) && p.Wp && conv_variant() == 14 && ((bm == 64 && bn == 64) || (bm == 128 && bn == 32) || (bm == 64 && bn == 32))) {
-            // the ping-pong loop (round 6; variant 14): two tiles per 512-thread workgroup, staging and matrix phases half a period apart
-            g_fp_hits.fetch_add(1, std::memory_order_relaxed);
-            if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, 1, 32, 1, 0, 1, 1>(p, stream);
-            else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, 1, 32, 1, 0, 1, 1>(p, stream);
-            else launch_igemm<64, 32, 2, 1, false, 1, 32, 1, 0, 1, 1>(p, stream);
         } else if (igemm_deep_slabs(p) && p.Wp) {
             g_fp_hits.fetch_add(1, std::memory_order_relaxed);
             // register fragments: mode 2, or the problem's tuning-table variant 12 (tools/conv_tune.py measures both forms per problem)
@@ -2681,11 +2524,6 @@ extern "C" int32_t sgx_conv2d_bwd_data_wt_req(const sgx_conv_desc* d, const floa
 #define WG_BKP 16      // pixels per slab (template parameter BKP of the kernel: 16, or WG_BKP_DEEP for the tiles whose two slabs stay <= 32 KB)
 #define WG_BKP_DEEP 32
 #define WG_MAX_SPLIT 4096
-#ifdef SGX_WGRAD_LAB
-#define WG_AB(bit) (g.lab & (bit))
-#else
-#define WG_AB(bit) false
-#endif
 #define WG_MAX_JOBS 24  // the job table travels as kernel arguments: 24 x (152 + 4) B + 8 B < 4 KB
 
 struct WgJob {
@@ -2702,7 +2540,6 @@ struct WgJob {
 };
 struct WgGroupParams {
     int njobs, xcd_order;
-    int lab;  // measurement builds (-DSGX_WGRAD_LAB) only: ablation bits - 1 no global loads, 2 no LDS stores (after the first slab), 4 no MFMAs, 8 no fold / dW
     int blk0[WG_MAX_JOBS];  // first workgroup of every job, together: the job lookup is a handful of scalar loads, not one per job
     WgJob jobs[WG_MAX_JOBS];
 };
@@ -2957,9 +2794,9 @@ __global__ __launch_bounds__(WK * WC * 64, MATH ? 1 : wg_min_waves((BNK / (WK * 
     if constexpr (PF == 1) {
         for (int kt = 0; kt < nkt; ++kt) {
             const int buf = kt & 1;
-            if (kt + 1 < nkt && !WG_AB(1)) load_tile(rdA, rxA);
-            if (!WG_AB(4)) mfma_slab(buf);
-            if (kt + 1 < nkt && !WG_AB(2)) store_tile(buf ^ 1, rdA, rxA);
+            if (kt + 1 < nkt) load_tile(rdA, rxA);
+            mfma_slab(buf);
+            if (kt + 1 < nkt) store_tile(buf ^ 1, rdA, rxA);
             __syncthreads();
         }
     } else {
@@ -2971,9 +2808,9 @@ __global__ __launch_bounds__(WK * WC * 64, MATH ? 1 : wg_min_waves((BNK / (WK * 
         // ONE step ago as well, which makes the second register set pointless (r3n's build: read off the ISA afterwards).
         auto step = [&](int kt, float4* rd, float4* rx) {
             const int buf = kt & 1;
-            if (!WG_AB(2)) store_tile(buf ^ 1, rd, rx);
-            if (!WG_AB(1)) load_tile(rd, rx);
-            if (!WG_AB(4)) mfma_slab(buf);
+            store_tile(buf ^ 1, rd, rx);
+            load_tile(rd, rx);
+            mfma_slab(buf);
             __syncthreads();
         };
         int kt = 0;
@@ -2990,10 +2827,6 @@ __global__ __launch_bounds__(WK * WC * 64, MATH ? 1 : wg_min_waves((BNK / (WK * 
             for (int j = 0; j < TC; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] += acc2[i][j][r];
-    }
-    if (WG_AB(8)) {  // main loop only (the accumulators stay observable)
-        if (acc[0][0][0] == 1.2345e-30f) p.dw[0] = 1.f;
-        return;
     }
     // ---- fold the pixel splits of this tile: a fixed binary tree over the split index, walked by arrival -------------------------------------
     // Level L pairs node i = split >> L with its sibling i ^ 1.  A workgroup holding a node's value publishes it (device-scope stores into
@@ -3100,10 +2933,8 @@ extern "C" int32_t sgx_debug_set_wgrad_group(int32_t rounds, int32_t item_mflop,
     g_wg_xcd = xcd_order ? 1 : 0;
     return SGX_OK;
 }
-static std::atomic<int> g_wg_lab{0};
-extern "C" int32_t sgx_debug_set_wgrad_loop(int32_t deep_slab, int32_t ablate) {
+extern "C" int32_t sgx_debug_set_wgrad_loop(int32_t deep_slab) {
     g_wg_deep = deep_slab;
-    g_wg_lab = ablate;
     return SGX_OK;
 }
 // Arithmetic of the weight gradient (process-wide, product default 2).  0: the fp32 matrix pipe.  1: the bf16x3 slab loop (round 3: the whole
@@ -3155,7 +2986,7 @@ static int32_t wgrad_group_plan(const sgx_wgrad_job* jobs, int n, std::vector<Wg
     // the patch kernel: product mode 2, no measurement override of the slab loop's tiles / loop in force
     const bool patch_on = g_wg_math.load(std::memory_order_relaxed) == 2 && !g_ovr_wk.load(std::memory_order_relaxed) &&
                           !g_ovr_wj.load(std::memory_order_relaxed) && !g_ovr_split.load(std::memory_order_relaxed) &&
-                          !(g_wg_deep.load(std::memory_order_relaxed) & 16) && !g_wg_lab.load(std::memory_order_relaxed);
+                          !(g_wg_deep.load(std::memory_order_relaxed) & 16);
     for (int i = 0; i < n; ++i) {
         const sgx_conv_desc* d = &jobs[i].d;
         int32_t rc = check_desc(d);
@@ -3262,7 +3093,7 @@ static void launch_wgrad(const WgGroupParams& g, int nblk, void* stream) {
     }
     if constexpr (BNK + BJ <= 128) {  // 32-pixel slabs (half the barriers, twice the bytes in flight per lane) where two of them fit 32 KB
         if (loop & 1) {
-            SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP_DEEP, 1>), grid, block, wg_lds_pad(wgrad_kernel<BNK, BJ, WK, WC, WG_BKP_DEEP, 1>), stream, g);
+            SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP_DEEP, 1>), grid, block, 0, stream, g);
             return;
         }
     }
@@ -3270,13 +3101,13 @@ static void launch_wgrad(const WgGroupParams& g, int nblk, void* stream) {
     // (sgx_conv_set_wgrad_math; r4a: the whole GPU suite green under it, 662 -> 686 images/s), or measurement bit 3; bit 5 forces the fp32 loop
     if constexpr (!(BNK == 64 && BJ == 64 && WK == 1)) {
         if ((loop & 8) || (g_wg_math.load(std::memory_order_relaxed) >= 1 && !(loop & 32))) {
-            SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 2, 1>), grid, block, wg_lds_pad(wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 2, 1>), stream, g);
+            SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 2, 1>), grid, block, 0, stream, g);
             return;
         }
     }
     // two register sets of loads in flight: measured r3n on YOLO-NAS-S, 14.29 -> 13.92 ms of weight-gradient time alone, +0.6 % on the step
-    if (loop & 2) SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 1>), grid, block, wg_lds_pad(wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 1>), stream, g);
-    else SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 2>), grid, block, wg_lds_pad(wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 2>), stream, g);
+    if (loop & 2) SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 1>), grid, block, 0, stream, g);
+    else SGX_LAUNCH((wgrad_kernel<BNK, BJ, WK, WC, WG_BKP, 2>), grid, block, 0, stream, g);
 }
 extern "C" int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_t njobs, void* ws, int64_t ws_bytes, int32_t* tickets,
                                                int64_t ticket_ints, void* stream) {
@@ -3341,7 +3172,6 @@ extern "C" int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_
         WgGroupParams g;
         memset(&g, 0, sizeof(g));
         g.xcd_order = g_wg_xcd.load(std::memory_order_relaxed);
-        g.lab = g_wg_lab.load(std::memory_order_relaxed);
         int nblk = 0;
         double flops = 0.0, bytes = 0.0;
         for (int i = first; i < njobs && g.njobs < WG_MAX_JOBS; ++i) {
@@ -3484,48 +3314,5 @@ extern "C" int32_t sgx_convT2x2_bwd_weight(int32_t N, int32_t H, int32_t W, int3
         if (ws_bytes < sgx_colsum_workspace(M, K)) SGX_FAIL(SGX_ERR_WORKSPACE, "convT bwd_weight: workspace too small");
         return sgx_colsum(dy, dy_ld_pix, M, K, 4L * H * W, dy_ld_img, dbias, 1, (float*)ws, stream);
     }
-    return SGX_OK;
-}
-
-// ---- a HIP stream confined to part of the chip ---------------------------------------------------------------------------------------
-// The weight gradients run on a side stream underneath the backward pass.  Their workgroups live for hundreds of microseconds and take every
-// CU; the short, dependent kernels of the main stream (the critical path of the step) then wait for slots between them - r4t: the
-// BatchNorm-backward sweeps run 7x longer while a weight-gradient kernel is resident, 6.8 ms per step over all main-stream kernels
-// (profiles/r4t_*).  A stream created here dispatches to `cus` of the device's CUs only (spread evenly: every `keep`-th ... CU index is
-// left out), so the rest of the chip always has room for the main stream.
-extern "C" int32_t sgx_conv_set_wgrad_lds_reserve(int32_t kb) {
-    SGX_CHECK_ARG(kb >= 0 && kb <= 120, "wgrad LDS reserve: 0..120 KB");
-    g_wg_lds_reserve = kb * 1024;
-    return SGX_OK;
-}
-extern "C" int32_t sgx_conv_get_wgrad_lds_reserve(void) { return g_wg_lds_reserve.load() / 1024; }
-extern "C" int32_t sgx_stream_create_partial(int32_t percent, void** stream) {
-    SGX_CHECK_ARG(stream && percent >= 10 && percent <= 100, "stream_create_partial: percent of the CUs in 10..100");
-#ifdef SGX_EMU
-    SGX_FAIL(SGX_ERR_UNSUPPORTED, "stream_create_partial: no CU masks on the host emulation");
-#else
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-        SGX_FAIL(SGX_ERR_HIP, "stream_create_partial: cannot query the device");
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    // bit i set <=> floor((i + 1) * percent / 100) > floor(i * percent / 100): `percent` of every run of 100 consecutive CU indices, evenly
-    // spaced - whatever the driver's mapping of mask bits to XCDs is (round-robin or blocked), every XCD keeps the same share
-    int on = 0;
-    for (int i = 0; i < ncu; ++i)
-        if ((long)(i + 1) * percent / 100 > (long)i * percent / 100) {
-            mask[i / 32] |= 1u << (i % 32);
-            ++on;
-        }
-    hipStream_t st = nullptr;
-    hipError_t e = hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data());
-    if (e != hipSuccess) SGX_FAIL(SGX_ERR_HIP, "hipExtStreamCreateWithCUMask(%d of %d CUs): %s", on, ncu, hipGetErrorString(e));
-    *stream = (void*)st;
-    return SGX_OK;
-#endif
-}
-extern "C" int32_t sgx_stream_destroy(void* stream) {
-#ifndef SGX_EMU
-    if (stream && hipStreamDestroy((hipStream_t)stream) != hipSuccess) SGX_FAIL(SGX_ERR_HIP, "hipStreamDestroy failed");
-#endif
     return SGX_OK;
 }

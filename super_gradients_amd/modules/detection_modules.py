@@ -6,7 +6,6 @@ concat -> 1x1).  The SPP concat is one NHWC buffer: cv1 and the three pooling ke
 """
 from typing import List
 
-import os
 
 import torch
 
@@ -18,7 +17,6 @@ from .conv_bn_act_block import Conv
 from .layers import MaxPool, act_name
 
 
-_FOLD_EXT = os.environ.get("SGX_BACKBONE_ADDEND", "1") != "0"  # measurement switch (r6s): 0 = the accumulate passes of rounds 1 - 5
 
 
 @register_detection_module()
@@ -94,15 +92,12 @@ class NStageBackbone(BaseDetectionModule):
         self.stem.replace_input_channels(in_channels=in_channels, compute_new_weights_fn=compute_new_weights_fn)
         self.in_channels = in_channels
 
-    def fwd(self, x, out=None, on_output=None):
-        """on_output(i, tensor): called as soon as output i exists (a neck that starts work on it beside the deeper stages)"""
+    def fwd(self, x, out=None):
         outs = []
         for layer in self._all_layers:
             x = getattr(self, layer).fwd(x)
             if layer in self.out_layers:
                 outs.append(x)
-                if on_output is not None:
-                    on_output(len(outs) - 1, x)
         return outs
 
     def bwd(self, grads: dict, on_layer_done=None, ext_ready=None):
@@ -131,7 +126,7 @@ class NStageBackbone(BaseDetectionModule):
             add = grads.get(nxt) if nxt is not None else None
             if add is not None and ext_ready is not None:
                 ext_ready, _ = None, ext_ready()
-            if add is not None and add.is_contiguous() and add.dtype == torch.float32 and _FOLD_EXT:
+            if add is not None and add.is_contiguous() and add.dtype == torch.float32:
                 kw["addend"] = add
                 folded.add(nxt)
             g = getattr(self, layer).bwd(g, need_dx=layer != self._all_layers[0], **kw)

@@ -197,22 +197,17 @@ class SgxNetwork(nn.Module):
         # Weight gradients are independent of the data-gradient chain: they are forked onto a side HIP stream so that they fill
         # the CUs the (dependent) main-stream kernels leave idle in their tails (most YOLO-NAS layers are 1-2 waves of
         # workgroups).  SGX_SIDE_STREAM=0 disables the fork.
-        self.side_stream = _make_side_stream(device) if (device.type == "cuda" and os.environ.get("SGX_SIDE_STREAM", "1") != "0") else None
-        # Optional (SGX_AUX_STREAM=1): transpose all data-gradient weights on a third stream underneath the forward pass instead of
-        # per call.  Measured neutral-to-negative on YOLO-NAS-S (r1p: 528.7 vs 533.3 images/s): the per-call transposes already hide
-        # under the side-stream weight gradients, so it stays off by default.
-        self.aux_stream = torch.cuda.Stream(device=device) if (self.side_stream is not None and os.environ.get("SGX_AUX_STREAM", "0") == "1") else None
+        self.side_stream = torch.cuda.Stream(device=device) if (device.type == "cuda" and os.environ.get("SGX_SIDE_STREAM", "1") != "0") else None
         # Branch stream (SGX_BRANCH_STREAM: bit 0 forward, bit 1 backward; round 6): a sub-chain of a block that nothing inside the block
         # waits for (YoloNASCSPLayer's conv2: GEMM -> finalize -> sweep, a few dozen microseconds each and dependent on one another) is
         # enqueued on a second in-order stream and joined where its result is consumed, so that its short kernels fill the gaps between the
         # dependent kernels of the main chain instead of lengthening it.
         self.branch_mode = int(os.environ.get("SGX_BRANCH_STREAM", str(BRANCH_STREAM_DEFAULT))) if self.side_stream is not None else 0
-        br_prio = int(os.environ.get("SGX_BRANCH_PRIORITY", "0"))  # (measurement switch, r6z)
-        self.branch_stream = torch.cuda.Stream(device=device, priority=br_prio) if self.branch_mode else None
+        self.branch_stream = torch.cuda.Stream(device=device) if self.branch_mode else None
         # (SGX_BRANCH_LANES: further branch streams for call sites that fork several mutually independent chains - the head levels, the
         # d alpha reductions.  Two by default and no more: main + side + two lanes are four HIP streams on the runtime's four hardware queues;
         # r6ae / r6af: four lanes 2 % slower, and with GPU_MAX_HW_QUEUES=8 30 % slower)
-        self.branch_lanes = [self.branch_stream] + [torch.cuda.Stream(device=device, priority=br_prio) for _ in range(int(os.environ.get("SGX_BRANCH_LANES", str(BRANCH_LANES_DEFAULT))) - 1)] \
+        self.branch_lanes = [self.branch_stream] + [torch.cuda.Stream(device=device) for _ in range(int(os.environ.get("SGX_BRANCH_LANES", str(BRANCH_LANES_DEFAULT))) - 1)] \
             if self.branch_stream is not None else []
         # which call sites fork (SGX_BRANCH_SITES bits: 1 YoloNASCSPLayer conv2, 2 coarse head levels, 4 the up stages' skip branches, 8 the batch
         # re-layout beside the per-step filter preparations, 16 the ResNet blocks' projection shortcuts, 32 the bottlenecks'
@@ -240,7 +235,7 @@ class SgxNetwork(nn.Module):
         # built once - the operands are arena views, their addresses never change) instead of one launch per convolution and parity class
         # inside backward (YOLO-NAS-S: 165 launches of ~10 us per step; SGX_WT_BATCH=0 restores the per-call form), and so do the
         # QARepVGG blocks' per-step filter preparations (W1 + I and its transpose, sgx_qarep_prep_batch).
-        self.wt_batch = os.environ.get("SGX_WT_BATCH", "1") == "1" and self.aux_stream is None
+        self.wt_batch = os.environ.get("SGX_WT_BATCH", "1") == "1"
         for m in self.modules():
             if isinstance(m, SgxBlock):
                 m.on_materialize()
@@ -290,7 +285,7 @@ class SgxNetwork(nn.Module):
                         if v is not None:
                             m.__dict__[name] = v
 
-    _RUNTIME_ATTRS = ("side_stream", "aux_stream", "branch_stream", "branch_lanes", "_wt_jobs", "_qp_jobs", "_dgrad_convs", "_wg_pending", "_fp_jobs", "_fp_dev", "_fp_buf")
+    _RUNTIME_ATTRS = ("side_stream", "branch_stream", "branch_lanes", "_wt_jobs", "_qp_jobs", "_dgrad_convs", "_wg_pending", "_fp_jobs", "_fp_dev", "_fp_buf")
 
     def __deepcopy__(self, memo):
         """copy.deepcopy(model) - what the reference's predict() pipeline does before fusing (pipelines.py:95-100): parameters, buffers and
@@ -326,7 +321,6 @@ class SgxNetwork(nn.Module):
         return new
 
     def prefetch_dgrad_weights(self):
-        aux = getattr(self, "aux_stream", None)
         if getattr(self, "_wt_jobs", None) is not None:
             from .. import kernels as K
 
@@ -337,19 +331,6 @@ class SgxNetwork(nn.Module):
                 K.filter_planes_invalidate(None)  # whatever an earlier step (of any network) left valid is not this step's
                 K.filter_planes_batch(self._fp_jobs, self._fp_dev)
             self._wt_valid = True
-            return
-        if aux is None:
-            return
-        aux.wait_stream(torch.cuda.current_stream())  # after the optimizer step that produced the current weights
-        with torch.cuda.stream(aux):
-            for m in self._dgrad_convs:
-                m.transpose_weights()
-        self._wt_valid = True
-
-    def join_aux(self):
-        aux = getattr(self, "aux_stream", None)
-        if aux is not None and self._wt_valid:
-            torch.cuda.current_stream().wait_stream(aux)
 
     def _apply(self, fn, recurse=True):
         if self._materialized:
@@ -561,8 +542,6 @@ class SgxNetwork(nn.Module):
         return a
 
 
-# Share of the chip's CUs the weight gradients' side stream may use (SGX_SIDE_CUS, percent; 100 = an ordinary stream).
-SIDE_STREAM_CU_PERCENT = 100
 BRANCH_STREAM_DEFAULT = 3
 WGRAD_EAGER_ROWS_DEFAULT = 800000  # (r6z: 800000 +0.4 % on YOLO-NAS-S at batch 32 - its 160 x 160 and 320 x 320 maps; 200000 -0.6 %, 50000 -1.9 %; M, L within noise)
 BRANCH_SITES_DEFAULT = 63
@@ -572,25 +551,6 @@ BRANCH_MAX_TILES_DEFAULT = 1 << 30
 
 def _nothing():
     return None
-
-
-def _make_side_stream(device):
-    """The side HIP stream of the weight gradients.  Below 100 % it is created with a CU mask (sgx_stream_create_partial): the
-    weight-gradient workgroups live for hundreds of microseconds and otherwise occupy every CU, and the short dependent kernels of the main
-    stream - the critical path of the step - then wait between them (r4t: 6.8 ms per step)."""
-    import ctypes
-    import os
-
-    pct = int(os.environ.get("SGX_SIDE_CUS") or SIDE_STREAM_CU_PERCENT)
-    if pct >= 100:
-        # (SGX_SIDE_PRIORITY=-1: a high-priority HIP stream - measurement switch, r6z)
-        return torch.cuda.Stream(device=device, priority=int(os.environ.get("SGX_SIDE_PRIORITY", "0")))
-    from .._lib import check, lib
-
-    handle = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        check(lib().sgx_stream_create_partial(pct, ctypes.byref(handle)), "sgx_stream_create_partial")
-    return torch.cuda.ExternalStream(handle.value, device=device)  # (lives as long as the process: a network's streams are never recycled)
 
 
 class NetFunction(torch.autograd.Function):
@@ -621,7 +581,6 @@ class NetFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         net = ctx.net
-        net.join_aux()
         planes = getattr(net, "_fp_jobs", None) is not None
         if planes:
             from .. import kernels as K

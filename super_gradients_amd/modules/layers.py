@@ -10,7 +10,6 @@ The fused sequences (conv -> BN statistics in the conv epilogue -> one affine+ac
 blocks in conv_bn_act_block.py / qarepvgg_block.py.
 """
 import math
-import os
 
 import torch
 from torch import nn
@@ -65,7 +64,7 @@ class ConvLayer(SgxBlock):
         self._w, self._gw = s.kernel_view, s.grad_kernel_view
         # persistent buffer of the data gradient's transposed weights (filled once per step by the network's batched transpose launch);
         # filter counts that are not a multiple of 4 (class-prediction convs) run their zero-padded backward with per-call transposes
-        pre = (self._net.aux_stream is not None or self._net.wt_batch) and self._w.shape[0] % 4 == 0
+        pre = self._net.wt_batch and self._w.shape[0] % 4 == 0
         self._wt = K.conv2d_wt_buffer(self._w, self._w.device) if pre else None
 
     def transpose_weights(self):
@@ -152,7 +151,7 @@ class ConvTranspose2x2(SgxBlock):
         # the forward IS the data gradient of the adjoint 2x2 stride-2 convolution: its transposed filter rides in the network's per-step
         # transpose batch like every data gradient's (engine.prefetch_dgrad_weights) - four transpose launches per call off the forward chain
         self.stride, self.padding = 2, 0
-        self._wt = K.conv2d_wt_buffer(self._w, self._w.device) if (self._net.wt_batch and os.environ.get("SGX_CONVT_PRETRANSPOSED", "1") != "0") else None  # (0: measurement switch)
+        self._wt = K.conv2d_wt_buffer(self._w, self._w.device) if self._net.wt_batch else None
 
     def transpose_weights(self):
         K.conv2d_transpose_weights(self._w, self._wt, stride=2, pad=0)

@@ -18,7 +18,6 @@ Blocks this form does not cover (learnable alpha, fewer than 16 channels, synchr
   statistics), y = act(scale_p*s + shift_p) (one sweep); backward: post_bn and BN3 backward in place, dx = dgrad3x3 + dgrad1x1 + ds.
 """
 from torch import nn
-import os
 
 import torch
 
@@ -29,9 +28,6 @@ from .layers import BatchNorm, ConvLayer, act_name
 
 class _Branch(nn.Module):
     pass
-
-
-_TAIL_CHUNKS = int(os.environ.get("SGX_STEM_BWD_CHUNKS", "1"))  # measurement switch (r6ad: 2 runs 794.0 against 793.4 images/s, 4 and 8 slower - the backlog behind the last sweep is stage 1's, not the stem's)
 
 
 class QARepVGGBlock(SgxBlock):
@@ -73,8 +69,8 @@ class QARepVGGBlock(SgxBlock):
             return None
         # (round 6: blocks with fewer than 16 input channels - the RGB stem - take the two-output launch too, on the flattened K axis, while
         # their filters fit its 64-wide tiles; they produce no input gradient, so the two-source data gradient is never asked of them)
-        if self.in_channels < 16 and (self.out_channels > 64 or self.use_residual_connection or os.environ.get("SGX_QAREP_STEM_DUAL", "1") == "0"):
-            return None  # (SGX_QAREP_STEM_DUAL=0: measurement switch, the general sequence of rounds 1 - 5)
+        if self.in_channels < 16 and (self.out_channels > 64 or self.use_residual_connection):
+            return None
         K_, C_ = c1._w.shape[0], c1._w.shape[1]
         self._w1p = K.ohwi_empty(K_, C_, 1, 1, c1._w.device)
         self._w1pt = torch.empty(C_, K_, device=c1._w.device, dtype=torch.float32)
@@ -215,17 +211,6 @@ class QARepVGGBlock(SgxBlock):
             accumulate, addend2 = True, None
         if self._ctx[0] == "dual":
             (_, x, y3, u, cf, sv), self._ctx = self._ctx, None
-            if not need_dx and _TAIL_CHUNKS > 1 and x.shape[0] % _TAIL_CHUNKS == 0:
-                # The first block of a network (no data gradient): its two weight gradients are the last work of the step, and the main chain has
-                # nothing left to run beside them - the apply sweep goes out in runs of images, each run's weight gradients behind it, so that
-                # only the last run's are left when the sweep ends (r6fin2's trace: 0.43 ms of stem weight gradients behind the last sweep).
-                def run_done(i, n0, n1):
-                    c1.wgrad(x[n0:n1], u[n0:n1], bias_grad=False)
-                    c3.wgrad(x[n0:n1], y3[n0:n1])
-                    self._net.flush_wgrads()
-
-                K.qarep_bwd(dy, y3, u, cf, sv, bn3, pbn, self.act, chunks=_TAIL_CHUNKS, after_chunk=run_done)
-                return None
             ds, dy3 = K.qarep_bwd(dy, y3, u, cf, sv, bn3, pbn, self.act)   # in place over u / y3
             c1.wgrad(x, ds, bias_grad=False)  # d b1 = sum ds = 0: post_bn's input gradient sums to zero per channel
             c3.wgrad(x, dy3)

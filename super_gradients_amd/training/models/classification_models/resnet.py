@@ -13,7 +13,6 @@ Backward: g = dy * [out > 0] (sgx_relu_bwd: the ReLU follows the residual add, s
 backward sweeps / weight gradients / data gradients of the branch, the shortcut gradient folded into the data-gradient
 epilogue (identity) or produced by the shortcut conv's own backward.
 """
-import os
 from typing import Dict
 
 import torch
@@ -50,7 +49,6 @@ class _ConvBN:
         return (t,) + tuple(bn.scale_shift(None, 0, False))
 
 
-_RELU_REDUCE = os.environ.get("SGX_RESNET_RELU_REDUCE", "1") != "0"  # measurement switch (r6aa): 0 = mask sweep + reduce sweep
 
 
 class _ResBlock(SgxBlock):
@@ -110,7 +108,7 @@ class _ResBlock(SgxBlock):
         # the final ReLU's mask and the reduce of the last BatchNorm's backward in one sweep (sgx_relu_bwd_bn_reduce, round 6: 16 reduce sweeps
         # of a ResNet-50 step gone); SGX_FUSE_BN_REDUCE=0 or a synchronised BatchNorm: the two passes
         parts_last = None
-        if self.final_relu and self._net.fuse_bn_reduce and not branch[-1][1]._synced() and _RELU_REDUCE:
+        if self.final_relu and self._net.fuse_bn_reduce and not branch[-1][1]._synced():
             g, parts_last = K.relu_bwd_bn_reduce(dy, y, saved[-1][1], saved[-1][4])
         else:
             g = K.relu_bwd(dy, y) if self.final_relu else dy

@@ -85,8 +85,7 @@ class CustomizableDetector(DetectionPredictMixin, SgxNetwork):
             xh = self._input_layout(x)
         if self._half_inference and not self.training:
             xh = K.cast_bf16(xh, cpad=8)  # the bf16 batch the first convolution reads (3 -> 8 channels: one 16-byte lane load per pixel)
-        pre = getattr(self.neck, "pre", None) if self.training else None
-        feats = self.backbone.fwd(xh, on_output=pre) if pre is not None else self.backbone.fwd(xh)
+        feats = self.backbone.fwd(xh)
         p = self.neck.fwd(feats)
         boxes, scores, logits, distri, anchors, pts, counts, strides = self.heads.fwd(p)
         self._aux = (anchors, pts, list(counts), strides)  # constants of the feature-map sizes (cached in the heads)

@@ -285,56 +285,24 @@ class YoloNASUpStage(BaseDetectionModule):
     def out_channels(self):
         return self._out_channels
 
-    def pre_skip(self, which: int, s):
-        """Start skip branch `which` (1: reduce_skip1(s), 2: downsample(reduce_skip2(s))) on the branch stream as soon as its input exists -
-        the backbone calls this while its deeper stages, whose launches do not fill the chip, are still to run; fwd() joins.  No-op (fwd()
-        runs the branch) in eval mode or with the branch stream off."""
-        net = getattr(self, "_net", None)
-        n, h, w, _ = s.shape
-        oc = self._oc
-        if net is None or not self.training or not net.branches(4, n * h * w, oc) or os.environ.get("SGX_BRANCH_EARLY_FORK", "0") == "0":
-            return
-        pre = self.__dict__.setdefault("_pre", {})
-
-        def run():
-            if "cat" not in pre:
-                pre["cat"] = _empty(n, h, w, 3 * oc, s) if which == 1 else _empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 3 * oc, s)
-            cat = pre["cat"]
-            if which == 1:
-                self.reduce_skip1.fwd(s, out=cat[..., oc:2 * oc])
-            else:
-                self.downsample.fwd(self.reduce_skip2.fwd(s), out=cat[..., 2 * oc:])
-
-        pre[which] = net.fork_branch(run)[1]
-
     def fwd(self, inputs, out=None):
         x, s1, s2 = inputs
         n, h, w, _ = s1.shape
         oc = self._oc
-        pre, self._pre = getattr(self, "_pre", None) or {}, {}
-        cat = pre["cat"] if "cat" in pre else _empty(n, h, w, 3 * oc, x)
-        if tuple(cat.shape) != (n, h, w, 3 * oc):
-            raise RuntimeError(f"YoloNASUpStage: skip branches were started for a {tuple(cat.shape)} concat, the inputs make {(n, h, w, 3 * oc)}")
+        cat = _empty(n, h, w, 3 * oc, x)
 
         def skips():
-            if 1 not in pre:
-                self.reduce_skip1.fwd(s1, out=cat[..., oc:2 * oc])
-            if 2 not in pre:
-                self.downsample.fwd(self.reduce_skip2.fwd(s2), out=cat[..., 2 * oc:])
+            self.reduce_skip1.fwd(s1, out=cat[..., oc:2 * oc])
+            self.downsample.fwd(self.reduce_skip2.fwd(s2), out=cat[..., 2 * oc:])
 
-        # the two skip branches meet the main one in the concat: branch stream (engine.fork_branch; sized by reduce_skip2's GEMM) - started
-        # by pre_skip() when the backbone produced their inputs, else here
+        # the two skip branches meet the main one in the concat: branch stream (engine.fork_branch; sized by reduce_skip2's GEMM)
         net = getattr(self, "_net", None)
         self._branched = net is not None and self.training and net.branches(4, s2.shape[0] * s2.shape[1] * s2.shape[2], oc)
-        joins = [pre[k] for k in (1, 2) if k in pre]
-        if len(joins) < 2:
-            joins.append(net.fork_branch(skips)[1] if self._branched else skips())
-        self._branched = self._branched or bool(pre)
+        join = net.fork_branch(skips)[1] if self._branched else skips()
         x_inter = self.conv.fwd(x)
         self.upsample.fwd(x_inter, out=cat[..., :oc])
-        for j in joins:
-            if j is not None:
-                j()
+        if join is not None:
+            join()
         return x_inter, self.blocks.fwd(self.reduce_after_concat.fwd(cat), out=out)
 
     def bwd(self, d_inter, d_out, dx=None, ds1=None, ds2=None, late_join=False):

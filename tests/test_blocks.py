@@ -628,6 +628,7 @@ def test_experiment_switches_compose(backend, monkeypatch):
 
     base = run()
     key = dict(N=n, H=h, W=w, C=32, K=32, R=3, stride=1, pad=1)
+    prev = lib().sgx_bn_get_fused_finalize()
     try:
         for variant in (7, 6):
             lib().sgx_debug_set_variant(variant)
@@ -639,7 +640,7 @@ def test_experiment_switches_compose(backend, monkeypatch):
                 assert_close(b, a, 2e-5, f"variant {variant}: {what}")
     finally:
         lib().sgx_debug_set_variant(0)
-        lib().sgx_bn_set_fused_finalize(0)
+        lib().sgx_bn_set_fused_finalize(prev)
         load_conv_tuning([])
 
 

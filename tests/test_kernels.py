@@ -1097,6 +1097,7 @@ def test_fused_finalize(backend, nblk, C):
     mean, invstd = torch.randn(C, generator=g).to(backend), (torch.rand(C, generator=g) + 0.5).to(backend)
     x = torch.randn(2, 40, nblk // 8 + 3, C, generator=g).to(backend)
     res = {}
+    prev = lib().sgx_bn_get_fused_finalize()
     try:
         for fused in (0, 1):
             lib().sgx_bn_set_fused_finalize(fused)
@@ -1111,7 +1112,7 @@ def test_fused_finalize(backend, nblk, C):
             res[fused] = [t.cpu().clone() for t in (*fwd, rm, rv, coef, dg, db, cs)]
         assert lib().sgx_bn_get_fused_finalize() == 1
     finally:
-        lib().sgx_bn_set_fused_finalize(0)
+        lib().sgx_bn_set_fused_finalize(prev)
     for a, b_ in zip(res[0], res[1]):
         assert_close(b_, a, 2e-6, f"fused finalize nblk={nblk} C={C}")
 
@@ -1247,7 +1248,7 @@ def test_wgrad_group(backend, monkeypatch):
         # (the bf16x3 loop has its own test; here it runs on the emulation only - on the chip this case list would reach tile shapes of it
         # that have not met hardware yet)
         for loop, what in ((1, "32-pixel slabs"), (2, "one slab in flight"), (4, "64x64 tile on two waves")) + (() if gpu else ((8, "bf16x3 loop"),)):
-            lib().sgx_debug_set_wgrad_loop(loop, 0)
+            lib().sgx_debug_set_wgrad_loop(loop)
             for e in ents:
                 e[2].zero_()
             K.conv2d_bwd_weight_group(ents)
@@ -1255,7 +1256,7 @@ def test_wgrad_group(backend, monkeypatch):
                 assert_close(e[2].cpu(), ref, TOL, f"grouped wgrad, {what} {shape}")
     finally:
         lib().sgx_debug_set_wgrad_group(0, 0, 1)
-        lib().sgx_debug_set_wgrad_loop(0, 0)
+        lib().sgx_debug_set_wgrad_loop(0)
         if gpu:  # the next use re-binds the library and re-applies the SGX_* environment switches (a gate run sets SGX_WGRAD_MATH suite-wide)
             from super_gradients_amd import _lib as _l
 
@@ -1346,7 +1347,7 @@ def test_wgrad_bf16x3_loop(backend):
                 ent = (to_nhwc(x, backend, ld_pix=c + 4, c_off=4), to_nhwc(dy, backend, ld_pix=k + 4, c_off=0), K.ohwi_empty(k, c, r, r, backend), s_, p_)
                 got = {}
                 for loop in (32, 8):  # bit 5: the fp32 loop, bit 3: the bf16x3 loop (the tile override keeps the patch kernel out)
-                    lib().sgx_debug_set_wgrad_loop(loop, 0)
+                    lib().sgx_debug_set_wgrad_loop(loop)
                     ent[2].zero_()
                     K.conv2d_bwd_weight_group([ent])
                     got[loop] = ent[2].cpu().clone()
@@ -1358,7 +1359,7 @@ def test_wgrad_bf16x3_loop(backend):
     finally:
         lib().sgx_debug_set_tiles(0, 0, 0, 0, 0)
         lib().sgx_debug_set_wgrad_group(0, 0, 1)
-        lib().sgx_debug_set_wgrad_loop(0, 0)
+        lib().sgx_debug_set_wgrad_loop(0)
         if gpu:  # (as in test_wgrad_group)
             from super_gradients_amd import _lib as _l
 
@@ -1476,7 +1477,7 @@ def test_wgrad_patch_kernel(backend, monkeypatch):
         lib().sgx_debug_set_wgrad_patch(1, 0, 1)  # smallest items (8 tiles = 256 pixels), every 3x3 pad-1 job takes the kernel whatever its fill
         got = {}
         for mode, loop in (("patch", 0), ("fp32", 16 + 32)):
-            lib().sgx_debug_set_wgrad_loop(loop, 0)
+            lib().sgx_debug_set_wgrad_loop(loop)
             for e in ents:
                 e[2].fill_(0.25)
             K.conv2d_bwd_weight_group(ents)
@@ -1486,7 +1487,7 @@ def test_wgrad_patch_kernel(backend, monkeypatch):
             e_patch, e_fp32 = float((a - 0.25 - ref).abs().max()) / scale, float((b - 0.25 - ref).abs().max()) / scale
             assert e_patch <= max(2e-6, 4.0 * e_fp32), f"patch wgrad {shape}: error {e_patch:.2e} (fp32 slab loop {e_fp32:.2e})"
         # the other workgroup shapes (two / three filter blocks = six / nine waves; the default policy takes one block below 192 filters)
-        lib().sgx_debug_set_wgrad_loop(0, 0)
+        lib().sgx_debug_set_wgrad_loop(0)
         for kb in (2, 3):
             lib().sgx_debug_set_wgrad_patch(1, kb, 1)
             for e in ents:
@@ -1497,7 +1498,7 @@ def test_wgrad_patch_kernel(backend, monkeypatch):
                 assert err <= 1e-5, f"patch wgrad, {kb} filter blocks {shape}: error {err:.2e}"
         lib().sgx_debug_set_wgrad_patch(1, 0, 1)
         # accumulates; tickets were left zero; another arrival order is bit-identical
-        lib().sgx_debug_set_wgrad_loop(0, 0)
+        lib().sgx_debug_set_wgrad_loop(0)
         if not gpu:
             monkeypatch.setenv("SGX_EMU_SHUFFLE", "4321")
         K.conv2d_bwd_weight_group(ents)
@@ -1519,7 +1520,7 @@ def test_wgrad_patch_kernel(backend, monkeypatch):
     finally:
         lib().sgx_debug_set_wgrad_patch(0, 0, 0)
         lib().sgx_debug_set_wgrad_group(0, 0, 1)
-        lib().sgx_debug_set_wgrad_loop(0, 0)
+        lib().sgx_debug_set_wgrad_loop(0)
 
 
 # (N, H, W, C, K): 3x3 stride-1 pad-1 problems for the patch kernel - ragged 8 x 16 tiles in both directions, both chunk depths (C % 32),
@@ -1662,39 +1663,9 @@ def test_pconv_stride2_data_gradient(backend, case):
         K.set_conv_math(K.DEFAULT_CONV_MATH)
 
 
-@pytest.mark.gpu
-def test_partial_chip_stream(gpu_device):
-    """sgx_stream_create_partial: a HIP stream confined to part of the CUs (the weight gradients' side stream).  Kernels launched on it
-    give the results of the ordinary stream; the mask it was created with has the requested share of bits, evenly spread; bad shares are
-    refused."""
-    import ctypes
-
-    from super_gradients_amd._lib import check, lib
-
-    shape = (2, 40, 40, 32, 64, 3, 1, 1)
-    x, wt, b = _conv_case(shape, seed=3)
-    xd, wd = to_nhwc(x, gpu_device), K.to_ohwi(wt.to(gpu_device))
-    ref = K.conv2d_fwd(xd, wd, bias=b.to(gpu_device), stride=1, pad=1)
-    torch.cuda.synchronize()
-    for pct in (25, 75):
-        h = ctypes.c_void_p()
-        check(lib().sgx_stream_create_partial(pct, ctypes.byref(h)), "sgx_stream_create_partial")
-        assert h.value
-        st = torch.cuda.ExternalStream(h.value, device=gpu_device)
-        with torch.cuda.stream(st):
-            y = K.conv2d_fwd(xd, wd, bias=b.to(gpu_device), stride=1, pad=1)
-        st.synchronize()
-        assert torch.equal(y, ref)
-        del st
-        check(lib().sgx_stream_destroy(h), "sgx_stream_destroy")
-    h = ctypes.c_void_p()
-    assert lib().sgx_stream_create_partial(5, ctypes.byref(h)) == -1 and lib().sgx_stream_create_partial(101, ctypes.byref(h)) == -1
-
-
-def test_round4_measurement_switches(backend):
-    """The measurement switches added in round 4 keep results correct and restore cleanly: the depth from which the per-problem rule runs a
-    problem in bf16x3 arithmetic (sgx_debug_set_bf3_min_depth; 0 = the default 192), and the LDS the weight-gradient launches leave to other
-    streams (sgx_conv_set_wgrad_lds_reserve: a launch-time dynamic-LDS request, no effect on results; 0..120 KB)."""
+def test_bf3_min_depth_switch(backend):
+    """The measurement switch added in round 4 keeps results correct and restores cleanly: the depth from which the per-problem rule runs a
+    problem in bf16x3 arithmetic (sgx_debug_set_bf3_min_depth; 0 = the default 192)."""
     from super_gradients_amd._lib import lib
 
     shape = _sizes(backend, (2, 24, 24, 64, 32, 1, 1, 0), (1, 6, 6, 64, 16, 1, 1, 0))  # depth 64: fp32 pipe under the default rule
@@ -1715,23 +1686,6 @@ def test_round4_measurement_switches(backend):
         lib().sgx_debug_set_bf3_min_depth(0)
         K.clear_desc_cache()
     assert torch.equal(K.conv2d_fwd(xd, wd, bias=b.to(backend), stride=s_, pad=p_), y_default)
-    # LDS reserve: the same weight gradient with and without it
-    wshape = _sizes(backend, (2, 24, 24, 32, 32, 3, 1, 1), (1, 8, 8, 16, 16, 3, 1, 1))
-    n, h, w, c, k, r, s_, p_ = wshape
-    x, wt, _ = _conv_case(wshape, seed=8)
-    dy = torch.randn(n, k, h, w, generator=torch.Generator().manual_seed(9))
-    xd, dyd = to_nhwc(x, backend), to_nhwc(dy, backend)
-    outs = []
-    try:
-        for kb in (0, 48):
-            assert lib().sgx_conv_set_wgrad_lds_reserve(kb) == 0 and lib().sgx_conv_get_wgrad_lds_reserve() == kb
-            dw = K.to_ohwi(torch.zeros(k, c, r, r, device=backend))
-            K.conv2d_bwd_weight_group([(xd, dyd, dw, s_, p_)])
-            outs.append(dw.clone())
-        assert lib().sgx_conv_set_wgrad_lds_reserve(121) == -1 and lib().sgx_conv_set_wgrad_lds_reserve(-1) == -1
-    finally:
-        lib().sgx_conv_set_wgrad_lds_reserve(0)
-    assert torch.equal(outs[0], outs[1])
 
 
 @pytest.mark.parametrize("case", ["random", "crowded", "per_class", "boundary", "few_kept"])
@@ -1845,8 +1799,7 @@ def _wt_filters(w, wtb, stride, pad):
     return [(r.wt, r.C, r.T, r.K) for r in (_lib.WtransJob * n).from_buffer_copy(raw)]
 
 
-@pytest.mark.parametrize("case", ["patch32", "patch64", "gemm1x1", "gemm3x3s2", "qarep_s1", "qarep_s2", "gemm1x1-regs", "gemm3x3s2-regs", "qarep_s2-regs",
-                                  "gemm1x1-pp", "gemm3x3s2-pp"])
+@pytest.mark.parametrize("case", ["patch32", "patch64", "gemm1x1", "gemm3x3s2", "qarep_s1", "qarep_s2", "gemm1x1-regs", "gemm3x3s2-regs", "qarep_s2-regs"])
 def test_filter_planes_launches_are_bit_identical(backend, case):
     """Pre-split filter planes (sgx_filter_planes_batch; round 5): a bf16x3 launch that copies its filter's planes must produce exactly the
     bits of the launch that splits the fp32 filter while staging - forward, data gradient (through the transposed filters' planes) and the
@@ -1857,9 +1810,6 @@ def test_filter_planes_launches_are_bit_identical(backend, case):
     gpu = backend.type == "cuda"
     # "-regs": planes mode 2 - the GEMM loop's one-block-per-wave tiles read their filter fragments straight from the planes into registers
     mode = 2 if case.endswith("-regs") else 1
-    # "-pp" (round 6): conv variant 14 - the ping-pong GEMM loop (two tiles per 512-thread workgroup, staging and matrix phases half a period
-    # apart; both shapes have an ODD tile count: the last workgroup's second wave group runs without a tile of its own)
-    pp = case.endswith("-pp")
     if not gpu and case == "gemm1x1-regs":
         pytest.skip("host emulation: the register-fragment form is covered by the 3x3 stride-2 and two-source cases (CPU suite time)")
     case = case.split("-")[0]
@@ -1896,7 +1846,7 @@ def test_filter_planes_launches_are_bit_identical(backend, case):
         return [y, parts, dx]
 
     K.set_conv_math("patch_bf3")
-    lib().sgx_debug_set_variant(14 if pp else 0 if gpu else 9)  # (host emulation: small maps - variant 9 lifts the patch kernel's 40 x 40 floor)
+    lib().sgx_debug_set_variant(0 if gpu else 9)  # (host emulation: small maps - variant 9 lifts the patch kernel's 40 x 40 floor)
     lib().sgx_debug_set_filter_planes(mode)
     jobs = None
     try:

@@ -1,12 +1,11 @@
 """Weight-gradient lab: replay the grouped weight-gradient launches of one real train step, alone on the chip, under several settings of
 the loop / the grouping - interleaved in ONE process (rounds x configs, median).
 
-    python tools/wgrad_lab.py [--model s] [--batch 32] [--size 640] [--configs base,slab32,ab1,ab3,ab7,ab8,ab15] [--rounds 3] [--iters 5]
+    python tools/wgrad_lab.py [--model s] [--batch 32] [--size 640] [--configs base,slab32,pf1] [--rounds 3] [--iters 5]
 
 A config is a '+'-joined list of:  base (the product default: bf16x3 arithmetic, patch kernel on the 3x3 problems) | nopatch (bf16x3 slab loop
 everywhere) | fp32 (the fp32 slab loop everywhere) | slab32 | pf1 (one slab of loads in flight instead of two) | w2 (64x64 tile on two
-waves) | bf16 (force the bf16x3 slab loop) | abN (ablation bits, needs a library built with -DSGX_WGRAD_LAB: 1 no global loads,
-2 no LDS stores, 4 no MFMAs, 8 no fold / dW) | gR.I.X (sgx_debug_set_wgrad_group rounds.item_mflop.xcd) | tBxJ (tile override of the slab
+waves) | bf16 (force the bf16x3 slab loop) | gR.I.X (sgx_debug_set_wgrad_group rounds.item_mflop.xcd) | tBxJ (tile override of the slab
 loop) | pI.K.F (sgx_debug_set_wgrad_patch: largest item MFLOP . filter blocks . least fill percent).
 Per group (= one K.conv2d_bwd_weight_group call of the step): jobs, GFLOP, then microseconds per config; last line: ms per step and
 algorithmic TFLOP/s.  Measurement tool: product library only.
@@ -57,7 +56,7 @@ def apply_config(cfg, lib):
     lib.sgx_debug_set_wgrad_group(0, 0, 1)
     lib.sgx_debug_set_tiles(0, 0, 0, 0, 0)
     lib.sgx_debug_set_wgrad_patch(0, 0, 0)
-    deep = ab = 0
+    deep = 0
     for part in cfg.split("+"):
         if part == "base":
             pass
@@ -73,8 +72,6 @@ def apply_config(cfg, lib):
             deep |= 4
         elif part == "bf16":
             deep |= 8
-        elif part.startswith("ab"):
-            ab = int(part[2:])
         elif part.startswith("g"):
             r, i, xo = (int(v) for v in part[1:].split("."))
             lib.sgx_debug_set_wgrad_group(r, i, xo)
@@ -85,7 +82,7 @@ def apply_config(cfg, lib):
             lib.sgx_debug_set_tiles(0, 0, b, j, 0)
         else:
             raise SystemExit(f"unknown config part {part!r}")
-    lib.sgx_debug_set_wgrad_loop(deep, ab)
+    lib.sgx_debug_set_wgrad_loop(deep)
 
 
 def main():
