@@ -585,6 +585,25 @@ int32_t sgx_detection_match(const sgx_match_desc* d, const float* preds, const i
 int32_t sgx_detection_unmap(const float* rows, const int32_t* counts, int32_t B, int32_t P, const float* steps, int32_t nsteps, float* out,
                             void* stream);
 
+/* Sliding-window inference (training/models/detection_models/sliding_window_detection_forward_wrapper.py:100-156).
+ * sgx_tile_gather: the tiles of a pre-processed NHWC batch in one launch (_generate_tiles :136-156 + the loops of forward :106-109).
+ * x [B][H][W] pixels of pix_bytes bytes (a multiple of 16: fp32 with channels padded to 4, bf16 with channels padded to 8, or wider),
+ * origins [T][2] = (x_t, y_t) int32 in device memory, y [B*T][tile][tile] pixels: tile t of image b = rows y_t .. y_t + tile, columns
+ * x_t .. x_t + tile of image b, pixels outside H x W all-zero bits (the reference pads with torch.zeros, :145-147).  A bit copy.        */
+int32_t sgx_tile_gather(const void* x, int32_t B, int32_t H, int32_t W, int32_t pix_bytes, const int32_t* origins, int32_t T, int32_t tile,
+                        void* y, void* stream);
+/* sgx_tile_merge: the cross-tile stage of forward (:113-131).  rows [B*T][P][6] / counts [B*T]: what sgx_nms wrote for the tile batch
+ * (tile t of image b at index b*T + t).  Per image the valid rows in the order tile 0 .. T-1, row 0 .. count-1; (x_t, y_t, x_t, y_t) is
+ * added to each box in fp32 (:116); then per-class NMS with the arithmetic of torchvision's CPU batched_nms (:127): the coordinate-
+ * offset form while 4 n <= 4000 (max_coordinate over this image's merged, shifted boxes), the per-class loop above, IoU > iou_threshold
+ * suppresses, candidates ordered by (score desc, merged index asc).  out [B][T*P][6] in that order (rows beyond the count zeroed),
+ * out_count [B]; no max_predictions cut (:131).  Exact up to T * P = SGX_TILE_MERGE_MAX_ROWS merged rows per image; more is
+ * SGX_ERR_BAD_ARG, a missing or short workspace SGX_ERR_WORKSPACE.                                                                    */
+#define SGX_TILE_MERGE_MAX_ROWS 16384
+int64_t sgx_tile_merge_workspace(int32_t B, int32_t T, int32_t P);
+int32_t sgx_tile_merge(const float* rows, const int32_t* counts, const int32_t* origins, int32_t B, int32_t T, int32_t P, float iou_threshold,
+                       float* out, int32_t* out_count, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Half-precision INFERENCE (csrc/half.hip): what `predict(fp16=True)` runs on the fused deployment form of the model
  * (training/pipelines/pipelines.py:76,223,375 wraps the reference's forward in torch.autocast; the fused form is

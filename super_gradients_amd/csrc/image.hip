@@ -96,3 +96,40 @@ extern "C" int32_t sgx_preprocess_u8_hwc(const sgx_image_job* jobs_dev, int32_t 
     SGX_CHECK_LAUNCH("preprocess_u8");
     return SGX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Sliding-window inference: the tiles of a pre-processed batch, cut on the device in ONE launch.
+// The reference (sliding_window_detection_forward_wrapper.py:136-156, _generate_tiles) pads the pre-processed image with torch.zeros up to
+// the tile grid and slices one tile at a time out of it inside a Python loop over images (:106-109).  Here tile t of image b is rows
+// y_t .. y_t + tile, columns x_t .. x_t + tile of image b; a pixel outside H x W is 0 (all bits zero - the reference's torch.zeros, not the
+// processing's pad value).  A pure bit copy in 16-byte lanes: a pixel is `pix_bytes` bytes whatever its element type (the fp32 batch with
+// channels padded to 4, the bf16 batch with channels padded to 8, or any wider NHWC tensor).  origins [T][2] = (x_t, y_t), device memory.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void tile_gather_kernel(const uint4* x, int H, int W, int lanes, const int* origins, int T, int tile, uint4* y) {
+    const int bt = blockIdx.y, b = bt / T, t = bt - b * T;
+    const int ox = origins[2 * t], oy = origins[2 * t + 1];
+    const long per_tile = (long)tile * tile * lanes;
+    const uint4* src = x + (long)b * H * W * lanes;
+    uint4* dst = y + (long)bt * per_tile;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per_tile; i += (long)gridDim.x * 256) {
+        const long pix = i / lanes;
+        const int q = (int)(i - pix * lanes), py = (int)(pix / tile), px = (int)(pix - (long)py * tile);
+        const long sy = (long)oy + py, sx = (long)ox + px;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (sy >= 0 && sy < H && sx >= 0 && sx < W) v = src[(sy * W + sx) * lanes + q];
+        dst[i] = v;
+    }
+}
+extern "C" int32_t sgx_tile_gather(const void* x, int32_t B, int32_t H, int32_t W, int32_t pix_bytes, const int32_t* origins, int32_t T, int32_t tile,
+                                   void* y, void* stream) {
+    SGX_CHECK_ARG(x && y && origins, "tile_gather: null pointer");
+    SGX_CHECK_ARG(B > 0 && H > 0 && W > 0 && T > 0 && tile > 0 && (long)B * T <= 65535, "tile_gather: bad dims (B=%d H=%d W=%d T=%d tile=%d)", B, H, W, T, tile);
+    SGX_CHECK_ARG(pix_bytes > 0 && pix_bytes % 16 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0,
+                  "tile_gather: pixels are copied in 16-byte lanes (pix_bytes=%d, 16-byte aligned tensors)", pix_bytes);
+    const int lanes = pix_bytes / 16;
+    const long per_tile = (long)tile * tile * lanes, blocks = (per_tile + 255) / 256;
+    SGX_LAUNCH(tile_gather_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks), (unsigned)(B * T)), dim3(256), 0, stream, (const uint4*)x, H, W, lanes, origins,
+               T, tile, (uint4*)y);
+    SGX_CHECK_LAUNCH("tile_gather");
+    return SGX_OK;
+}

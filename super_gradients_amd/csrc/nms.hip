@@ -1117,3 +1117,307 @@ extern "C" int32_t sgx_detection_unmap(const float* rows, const int32_t* counts,
     SGX_CHECK_LAUNCH("detection_unmap");
     return SGX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Sliding-window inference: the cross-tile merge (sliding_window_detection_forward_wrapper.py:113-133).
+// The reference shifts every tile's post-NMS rows by the tile's origin (:116, one fp32 add per coordinate), concatenates them per image on
+// the host (:122) and calls torchvision.ops.batched_nms once per image (:127) - always per class, whatever the tile stage did, and without a
+// max_predictions cut (:131).  Here the whole batch stays on the device:
+//   merge_collect_kernel  one workgroup per image: prefix sum of the tile counts, the valid rows in the order tile 0 .. T-1 / row 0 .. count-1
+//                         (the "merged index"), boxes shifted, composite keys (score, merged index), the image's max coordinate
+//   merge_rank_kernel     whole chip: a candidate's place in the (score desc, merged index asc) order is the number of larger keys - keys are
+//                         unique, so the ranks are a permutation; no LDS capacity bounds the count (the per-image kernel above sorts <= 4096
+//                         keys in LDS).  Writes the sorted candidates as the IoU test sees them: torchvision's CPU dispatch, the coordinate-
+//                         offset form while 4 n <= 4000 (max_coordinate over THIS image's merged, shifted boxes), the per-class form above.
+//   merge_mask_kernel     whole chip: the suppression bit matrix (row i, word w: "i suppresses 64 w + j"), the wave-ballot form of
+//                         nms_mask_kernel, in HBM - n^2 / 8 bytes per image
+//   merge_walk_kernel     one workgroup per image, thread w owns flag word w: 64 candidates at a time, the kept -> flags -> next kept chain
+//                         of a word on the scalar unit (as nms_walk_kernel), then every thread ORs the rows of the word's kept candidates
+//                         into its own flag word (loads of one round in flight together); rows written in kept order, no cut.
+// Exact for any merged count up to SGX_TILE_MERGE_MAX_ROWS (a bound on T * P: the counts are device data); no host fallback.
+// ------------------------------------------------------------------------------------------------
+#define MERGE_THREADS 1024
+#define MERGE_RANK_THREADS 256
+#define MERGE_MASK_THREADS 256
+#define MERGE_MASK_WG 4
+#define MERGE_WALK_THREADS (SGX_TILE_MERGE_MAX_ROWS / 64)
+static_assert(MERGE_WALK_THREADS == 256, "merge_walk_kernel: one flag word per thread of a 256-thread workgroup");
+// an image's block of the workspace (byte offsets; rows = T * P rounded up to 64, so every array starts on a 256-byte line):
+// meta int[64] {n, class mode, max coordinate bits} | key u64[rows] | box f32[rows][4] | cls f32[rows] | src int[rows] (unsorted, merged
+// order) | sbox f32[rows][4] | snb f32[rows][4] (as the IoU test sees it) | sarea f32[rows] | scls f32[rows] | ssrc int[rows] (sorted) |
+// mask u64[rows][rows / 64]
+struct merge_layout {
+    long per_image, key, box, cls, src, sbox, snb, sarea, scls, ssrc, mask;
+    int rows, nws;
+};
+static merge_layout merge_make_layout(long TP) {
+    merge_layout L;
+    const long R = (TP + 63) / 64 * 64;
+    L.rows = (int)R;
+    L.nws = (int)(R / 64);
+    long o = 256;
+    L.key = o; o += R * 8;
+    L.box = o; o += R * 16;
+    L.cls = o; o += R * 4;
+    L.src = o; o += R * 4;
+    L.sbox = o; o += R * 16;
+    L.snb = o; o += R * 16;
+    L.sarea = o; o += R * 4;
+    L.scls = o; o += R * 4;
+    L.ssrc = o; o += R * 4;
+    L.mask = o; o += R * L.nws * 8;
+    L.per_image = o;
+    return L;
+}
+// float bits whose unsigned order is the floats' order (-0 counts as +0: equal scores tie on the index)
+__device__ __forceinline__ unsigned merge_score_bits(float s) {
+    if (s == 0.f) s = 0.f;
+    const unsigned u = __float_as_uint(s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ int merge_tile_count(const int* cnt, int t, int P) {
+    const int c = cnt[t];
+    return c < 0 ? 0 : (c > P ? P : c);
+}
+__global__ __launch_bounds__(MERGE_THREADS) void merge_collect_kernel(const float* rows, const int* counts, const int* origins, int T, int P, merge_layout L,
+                                                                      char* ws) {
+    __shared__ int tbase[SGX_TILE_MERGE_MAX_ROWS];  // (T <= T * P <= SGX_TILE_MERGE_MAX_ROWS)
+    __shared__ float wmax[MERGE_THREADS / 64];
+    __shared__ int s_n;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    char* const o = ws + (long)b * L.per_image;
+    int* meta = reinterpret_cast<int*>(o);
+    u64* key = reinterpret_cast<u64*>(o + L.key);
+    float* box = reinterpret_cast<float*>(o + L.box);
+    float* cls = reinterpret_cast<float*>(o + L.cls);
+    int* src = reinterpret_cast<int*>(o + L.src);
+    const int* cnt = counts + (long)b * T;
+    if (tid < 64) {  // wave 0: exclusive prefix sum of the tile counts, 64 tiles per trip
+        int carry = 0;
+        for (int t0 = 0; t0 < T; t0 += 64) {
+            const int t = t0 + lane;
+            const int c = t < T ? merge_tile_count(cnt, t, P) : 0;
+            int v = c;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int u = __shfl_up(v, off);
+                if (lane >= off) v += u;
+            }
+            if (t < T) tbase[t] = carry + v - c;
+            carry += __shfl(v, 63);
+        }
+        if (lane == 0) s_n = carry;
+    }
+    __syncthreads();
+    const int n = s_n;
+    const long TP = (long)T * P;
+    float mymax = -INFINITY;
+    for (long s = tid; s < TP; s += MERGE_THREADS) {
+        const int t = (int)(s / P), r = (int)(s - (long)t * P);
+        if (r >= merge_tile_count(cnt, t, P)) continue;
+        const int m = tbase[t] + r;
+        const float* row = rows + ((long)b * TP + s) * 6;
+        const float fx = (float)origins[2 * t], fy = (float)origins[2 * t + 1];
+        const float x1 = row[0] + fx, y1 = row[1] + fy, x2 = row[2] + fx, y2 = row[3] + fy;
+        box[m * 4 + 0] = x1; box[m * 4 + 1] = y1; box[m * 4 + 2] = x2; box[m * 4 + 3] = y2;
+        cls[m] = row[5];
+        src[m] = (int)s;
+        key[m] = ((u64)merge_score_bits(row[4]) << 32) | (u64)(0xffffffffu - (unsigned)m);
+        mymax = fmaxf(fmaxf(fmaxf(mymax, x1), fmaxf(y1, x2)), y2);
+    }
+    for (int off = 32; off > 0; off >>= 1) mymax = fmaxf(mymax, __shfl_xor(mymax, off));
+    if (lane == 0) wmax[tid >> 6] = mymax;
+    __syncthreads();
+    if (tid == 0) {
+        float m = wmax[0];
+        for (int w = 1; w < MERGE_THREADS / 64; ++w) m = fmaxf(m, wmax[w]);
+        meta[0] = n;
+        meta[1] = 4L * n > 4000 ? 2 : 1;  // torchvision/ops/boxes.py batched_nms on CPU: the coordinate trick while boxes.numel() <= 4000
+        meta[2] = (int)__float_as_uint(m);
+    }
+}
+__global__ __launch_bounds__(MERGE_RANK_THREADS) void merge_rank_kernel(merge_layout L, char* ws) {
+    __shared__ u64 tk[MERGE_RANK_THREADS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    char* const o = ws + (long)b * L.per_image;
+    const int* meta = reinterpret_cast<const int*>(o);
+    const int n = meta[0], class_mode = meta[1];
+    if ((int)blockIdx.x * MERGE_RANK_THREADS >= n) return;  // whole workgroup
+    const u64* key = reinterpret_cast<const u64*>(o + L.key);
+    const int i = blockIdx.x * MERGE_RANK_THREADS + tid;
+    const u64 my = i < n ? key[i] : ~0ull;
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += MERGE_RANK_THREADS) {
+        tk[tid] = j0 + tid < n ? key[j0 + tid] : 0ull;  // (0 is below every real key: their index field is never 0)
+        __syncthreads();
+        const int lim = n - j0 < MERGE_RANK_THREADS ? n - j0 : MERGE_RANK_THREADS;
+        for (int j = 0; j < lim; ++j) rank += tk[j] > my ? 1 : 0;
+        __syncthreads();
+    }
+    if (i >= n) return;
+    const float* box = reinterpret_cast<const float*>(o + L.box);
+    const float c = reinterpret_cast<const float*>(o + L.cls)[i];
+    float* sbox = reinterpret_cast<float*>(o + L.sbox);
+    float* snb = reinterpret_cast<float*>(o + L.snb);
+    // boxes + idxs.to(boxes) * (max_coordinate + 1) (boxes.py), or the boxes themselves in the per-class form
+    const float offv = class_mode == 1 ? c * (__uint_as_float((unsigned)meta[2]) + 1.f) : 0.f;
+    float nb[4];
+    for (int q = 0; q < 4; ++q) {
+        const float v = box[i * 4 + q];
+        sbox[rank * 4 + q] = v;
+        nb[q] = v + offv;
+        snb[rank * 4 + q] = nb[q];
+    }
+    reinterpret_cast<float*>(o + L.sarea)[rank] = (nb[2] - nb[0]) * (nb[3] - nb[1]);
+    reinterpret_cast<float*>(o + L.scls)[rank] = c;
+    reinterpret_cast<int*>(o + L.ssrc)[rank] = reinterpret_cast<const int*>(o + L.src)[i];
+}
+// work item = (strip c of 64 rows, group g of MERGE_MASK_WG words); words left of the strip's diagonal are never read and not built
+__global__ __launch_bounds__(MERGE_MASK_THREADS) void merge_mask_kernel(merge_layout L, char* ws, float iou_threshold, int ngroups) {
+    __shared__ float rnb[64][4], cnb[64 * MERGE_MASK_WG][4];
+    __shared__ float rarea[64], carea[64 * MERGE_MASK_WG], rcls[64], ccls[64 * MERGE_MASK_WG];
+    const int c = blockIdx.x / ngroups, g = blockIdx.x - c * ngroups;
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    char* const o = ws + (long)b * L.per_image;
+    const int* meta = reinterpret_cast<const int*>(o);
+    const int n = meta[0], class_mode = meta[1];
+    const int nw = (n + 63) >> 6;
+    const int w0 = MERGE_MASK_WG * g;
+    const int w1 = w0 + MERGE_MASK_WG < nw ? w0 + MERGE_MASK_WG : nw;
+    if (64 * c >= n || w0 >= nw || w1 <= c) return;  // whole workgroup
+    const float* gnb = reinterpret_cast<const float*>(o + L.snb);
+    const float* garea = reinterpret_cast<const float*>(o + L.sarea);
+    const float* gcls = reinterpret_cast<const float*>(o + L.scls);
+    u64* const mask = reinterpret_cast<u64*>(o + L.mask);
+    if (tid < 64) {
+        const int t = 64 * c + tid;
+        if (t < n) {
+            for (int q = 0; q < 4; ++q) rnb[tid][q] = gnb[t * 4 + q];
+            rarea[tid] = garea[t];
+            rcls[tid] = gcls[t];
+        }
+    }
+    for (int j = tid; j < 64 * (w1 - w0); j += MERGE_MASK_THREADS) {
+        const int t = 64 * w0 + j;
+        if (t < n) {
+            for (int q = 0; q < 4; ++q) cnb[j][q] = gnb[t * 4 + q];
+            carea[j] = garea[t];
+            ccls[j] = gcls[t];
+        }
+    }
+    __syncthreads();
+    for (int r = wave; r < 64; r += MERGE_MASK_THREADS / 64) {
+        const int i = 64 * c + r;
+        if (i >= n) break;  // wave-uniform
+        const float ci0 = rnb[r][0], ci1 = rnb[r][1], ci2 = rnb[r][2], ci3 = rnb[r][3], ai = rarea[r], ic = rcls[r];
+        for (int w = w0 > c ? w0 : c; w < w1; ++w) {
+            const int j = 64 * (w - w0) + lane, t = 64 * w + lane;
+            bool hit = false;
+            if (t > i && t < n && (class_mode != 2 || ccls[j] == ic)) {
+                const float xx1 = fmaxf(ci0, cnb[j][0]), yy1 = fmaxf(ci1, cnb[j][1]);
+                const float xx2 = fminf(ci2, cnb[j][2]), yy2 = fminf(ci3, cnb[j][3]);
+                float ww = xx2 - xx1; ww = ww < 0.f ? 0.f : ww;
+                float hh = yy2 - yy1; hh = hh < 0.f ? 0.f : hh;
+                const float inter = ww * hh;
+                const float ovr = inter / (ai + carea[j] - inter);
+                hit = ovr > iou_threshold;
+            }
+            const u64 bits = __ballot(hit);
+            if (lane == 0) mask[(long)i * L.nws + w] = bits;
+        }
+    }
+}
+__global__ __launch_bounds__(MERGE_WALK_THREADS) void merge_walk_kernel(const float* rows, int T, int P, merge_layout L, const char* ws, float* out,
+                                                                        int* out_count) {
+    __shared__ int keep_list[SGX_TILE_MERGE_MAX_ROWS];
+    __shared__ u64 s_cur, s_kept_bits;
+    __shared__ int s_kept;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const char* const o = ws + (long)b * L.per_image;
+    const int n = reinterpret_cast<const int*>(o)[0];
+    const int nw = (n + 63) >> 6;
+    const long nws = L.nws;
+    const u64* mask = reinterpret_cast<const u64*>(o + L.mask);
+    u64 rem = 0;   // thread w: the suppression flags of word w
+    int kept = 0;  // (wave 0)
+    for (int c = 0; c < nw; ++c) {
+        if (tid == c) s_cur = rem;
+        __syncthreads();
+        if (wave == 0) {
+            u64 cur = s_cur;
+            if (c == nw - 1 && (n & 63)) cur |= ~0ull << (n & 63);  // slots past the last candidate
+            const u64 diag = 64 * c + lane < n ? mask[(long)(64 * c + lane) * nws + c] : 0ull;
+            u64 cur_s = sgx_uniform_u64(cur);
+            u64 avail = ~cur_s, kept_bits = 0;
+            while (avail) {  // wave-uniform
+                const int bit = __ffsll(avail) - 1;
+                if (lane == 0) keep_list[kept] = 64 * c + bit;
+                ++kept;
+                kept_bits |= 1ull << bit;
+                cur_s |= sgx_readlane_u64(diag, bit);
+                avail = ~cur_s & ~((2ull << bit) - 1ull);
+            }
+            if (lane == 0) s_kept_bits = kept_bits;
+        }
+        __syncthreads();
+        if (tid > c && tid < nw) {
+            // what the word's kept candidates suppress in this thread's word: eight independent loads per trip
+            const u64* col = mask + (long)64 * c * nws + tid;
+            u64 kb = s_kept_bits;
+            while (kb) {
+                int bit[8];
+                u64 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    bit[u] = kb ? __ffsll(kb) - 1 : -1;
+                    kb &= kb - 1ull;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = bit[u] >= 0 ? col[bit[u] * nws] : 0ull;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) rem |= v[u];
+            }
+        }
+    }
+    if (tid == 0) s_kept = kept;
+    __syncthreads();
+    kept = s_kept;
+    if (tid == 0) out_count[b] = kept;
+    const float* sbox = reinterpret_cast<const float*>(o + L.sbox);
+    const int* ssrc = reinterpret_cast<const int*>(o + L.ssrc);
+    const long TP = (long)T * P;
+    for (long r = tid; r < TP; r += MERGE_WALK_THREADS) {
+        float* q = out + ((long)b * TP + r) * 6;
+        if (r < kept) {
+            const int i = keep_list[r];
+            const float* row = rows + ((long)b * TP + ssrc[i]) * 6;
+            q[0] = sbox[i * 4 + 0]; q[1] = sbox[i * 4 + 1]; q[2] = sbox[i * 4 + 2]; q[3] = sbox[i * 4 + 3];
+            q[4] = row[4];
+            q[5] = row[5];
+        } else {
+            for (int z = 0; z < 6; ++z) q[z] = 0.f;
+        }
+    }
+}
+static bool merge_dims_ok(int B, int T, int P) { return B > 0 && B <= 65535 && T > 0 && P > 0 && (long)T * P <= SGX_TILE_MERGE_MAX_ROWS; }
+extern "C" int64_t sgx_tile_merge_workspace(int32_t B, int32_t T, int32_t P) {
+    if (!merge_dims_ok(B, T, P)) return 256;
+    return (int64_t)B * merge_make_layout((long)T * P).per_image;
+}
+extern "C" int32_t sgx_tile_merge(const float* rows, const int32_t* counts, const int32_t* origins, int32_t B, int32_t T, int32_t P, float iou_threshold,
+                                  float* out, int32_t* out_count, void* ws, int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(rows && counts && origins && out && out_count, "tile_merge: null pointer");
+    SGX_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && P > 0, "tile_merge: bad dims (B=%d T=%d P=%d)", B, T, P);
+    SGX_CHECK_ARG((long)T * P <= SGX_TILE_MERGE_MAX_ROWS, "tile_merge: %d tiles x %d rows = %ld merged rows per image, the limit is %d", T, P, (long)T * P,
+                  SGX_TILE_MERGE_MAX_ROWS);
+    if (!ws || ws_bytes < sgx_tile_merge_workspace(B, T, P) || ((uintptr_t)ws % 16) != 0)
+        SGX_FAIL(SGX_ERR_WORKSPACE, "tile_merge: a 16-byte aligned workspace of %ld bytes is needed (got %ld)", (long)sgx_tile_merge_workspace(B, T, P), (long)ws_bytes);
+    const merge_layout L = merge_make_layout((long)T * P);
+    const int ngroups = (L.nws + MERGE_MASK_WG - 1) / MERGE_MASK_WG;
+    SGX_LAUNCH(merge_collect_kernel, dim3((unsigned)B), dim3(MERGE_THREADS), 0, stream, rows, counts, origins, T, P, L, (char*)ws);
+    SGX_LAUNCH(merge_rank_kernel, dim3((unsigned)(L.rows / MERGE_RANK_THREADS + (L.rows % MERGE_RANK_THREADS ? 1 : 0)), (unsigned)B), dim3(MERGE_RANK_THREADS), 0,
+               stream, L, (char*)ws);
+    SGX_LAUNCH(merge_mask_kernel, dim3((unsigned)(L.nws * ngroups), (unsigned)B), dim3(MERGE_MASK_THREADS), 0, stream, L, (char*)ws, iou_threshold, ngroups);
+    SGX_LAUNCH(merge_walk_kernel, dim3((unsigned)B), dim3(MERGE_WALK_THREADS), 0, stream, rows, T, P, L, (const char*)ws, out, out_count);
+    SGX_CHECK_LAUNCH("tile_merge");
+    return SGX_OK;
+}

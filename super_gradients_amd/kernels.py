@@ -1138,6 +1138,42 @@ def detection_unmap(rows, counts, steps):
     return out
 
 
+TILE_MERGE_MAX_ROWS = 16384  # == SGX_TILE_MERGE_MAX_ROWS (include/sgx_hip.h)
+
+
+def tile_gather(x, origins, tile: int):
+    """x: a contiguous NHWC batch [B,H,W,C], fp32 (C a multiple of 4) or bf16 (C a multiple of 8); origins: int32 [T,2] = (x_t, y_t) on x's
+    device -> [B*T, tile, tile, C], tile t of image b at index b*T + t, pixels outside H x W zero (sgx_tile_gather: one launch, a bit copy)."""
+    if x.dim() != 4 or not x.is_contiguous() or x.dtype not in (torch.float32, HALF):
+        raise _lib.SgxError(f"tile_gather needs a contiguous fp32 / bf16 NHWC batch, got {x.dtype} {tuple(x.shape)} strides {x.stride()}")
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or origins.device != x.device:
+        raise _lib.SgxError("tile_gather: origins must be an int32 [T, 2] tensor on the batch's device")
+    B, H, W, C = x.shape
+    T = int(origins.shape[0])
+    origins = origins.contiguous()
+    y = torch.empty(B * T, tile, tile, C, device=x.device, dtype=x.dtype)
+    check(lib().sgx_tile_gather(ptr(x), B, H, W, C * x.element_size(), ptr(origins), T, int(tile), ptr(y), stream()), "sgx_tile_gather")
+    return y
+
+
+def tile_merge(rows, counts, origins, T: int, iou_threshold: float):
+    """rows [B*T,P,6] + counts [B*T] (the NMS output layout of the tile batch, tile t of image b at b*T + t), origins int32 [T,2] ->
+    (out [B, T*P, 6], out_count [B] int32): per image the tiles' rows shifted to image coordinates and merged by per-class NMS in
+    torchvision's CPU batched_nms arithmetic (sgx_tile_merge); no cut of the merged rows.  T*P <= TILE_MERGE_MAX_ROWS, else SgxError."""
+    BT, P, _ = rows.shape
+    if T <= 0 or BT % T or origins.dtype != torch.int32 or tuple(origins.shape) != (T, 2):
+        raise _lib.SgxError(f"tile_merge: {BT} tile rows do not split into images of {T} tiles with an int32 [T, 2] origin table")
+    B = BT // T
+    dev = rows.device
+    rows, counts, origins = rows.contiguous().float(), counts.contiguous().int(), origins.contiguous()  # bound to names: alive until the launch is enqueued
+    out = torch.empty(B, T * P, 6, device=dev, dtype=torch.float32)
+    cnt = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = WORKSPACE.get(lib().sgx_tile_merge_workspace(B, T, P), dev)
+    check(lib().sgx_tile_merge(ptr(rows), ptr(counts), ptr(origins), B, T, P, float(iou_threshold), ptr(out), ptr(cnt), ptr(ws), ws.numel(), stream()),
+          "sgx_tile_merge")
+    return out, cnt
+
+
 def detection_match(rows, counts, targets, crowd_targets, thresholds, height, width, top_k, denormalize):
     """rows [B,P,6] + counts [B] (the NMS output layout), targets / crowd_targets flat [T,6] -> (matched, ignore) uint8 [B,P,nthr]."""
     B, P, _ = rows.shape

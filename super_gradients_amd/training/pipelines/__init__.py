@@ -1,1 +1,1 @@
-from .pipelines import DetectionPipeline, Pipeline  # noqa: F401
+from .pipelines import DetectionPipeline, Pipeline, SlidingWindowDetectionPipeline  # noqa: F401

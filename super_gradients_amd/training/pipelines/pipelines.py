@@ -171,11 +171,14 @@ class Pipeline(ABC):
             self.model.eval()
         try:
             with torch.no_grad():
-                out = self.model(batch)
+                out = self._model_forward(batch)
                 return decode(out, model_input=batch)
         finally:
             if was_training:
                 self.model.train(True)
+
+    def _model_forward(self, batch: torch.Tensor):
+        return self.model(batch)
 
     @abstractmethod
     def _decode_model_output(self, model_output, model_input):
@@ -226,7 +229,7 @@ class DetectionPipeline(Pipeline):
 
         batch, metadatas = self.image_processor.preprocess_batch(images, device=self.device)
         steps = [self.image_processor.inverse_box_steps(m) for m in metadatas]
-        if any(s is None for s in steps) or not hasattr(self.post_prediction_callback, "forward_batched") or os.environ.get("SGX_PREDICT_HOST_POST") == "1":
+        if not self._device_postprocess(steps):
             yield from self._host_postprocess(images, self.pass_images_through_model(batch), metadatas)
             return
         B, nst = len(steps), max(len(s) for s in steps)
@@ -239,7 +242,7 @@ class DetectionPipeline(Pipeline):
             st = torch.from_numpy(arr).to(self.device)
 
         def decode(model_output, model_input):
-            rows, cnt, _ = self.post_prediction_callback.forward_batched(model_output)
+            rows, cnt = self._batched_rows(model_output)
             return K.detection_unmap(rows, cnt, st).cpu().numpy(), int(rows.shape[1])
 
         flat, P = self._forward_raw(batch, decode)
@@ -250,6 +253,14 @@ class DetectionPipeline(Pipeline):
             r = rows[b, :int(counts[b])]
             pred = DetectionPrediction(bboxes=r[:, :4], confidence=r[:, 4], labels=r[:, 5].astype(int), bbox_format="xyxy", image_shape=shape)
             yield self._instantiate_image_prediction(image=image, prediction=pred)
+
+    def _device_postprocess(self, steps) -> bool:
+        return not (any(s is None for s in steps) or not hasattr(self.post_prediction_callback, "forward_batched") or os.environ.get("SGX_PREDICT_HOST_POST") == "1")
+
+    def _batched_rows(self, model_output):
+        """model output -> device-resident (rows [B, P, 6], counts [B]) without a host synchronisation"""
+        rows, cnt, _ = self.post_prediction_callback.forward_batched(model_output)
+        return rows, cnt
 
     def _host_postprocess(self, images, predictions, metadatas):
         for image, prediction, metadata in zip(images, predictions, metadatas):
@@ -263,3 +274,47 @@ class DetectionPipeline(Pipeline):
         if n_images == 1:
             return next(iter(images_predictions))
         return ImagesDetectionPrediction(_images_prediction_lst=list(images_predictions))
+
+
+class SlidingWindowDetectionPipeline(DetectionPipeline):
+    """predict() of a SlidingWindowInferenceDetectionWrapper (reference: pipelines.py:373-395): `model` is the wrapper, the post-prediction
+    callback (the tile stage's thresholds; its IoU threshold is also the cross-tile merge's) is passed into the wrapper's forward, and the
+    fused copy is a copy of the WRAPPED model.  Everything of DetectionPipeline's device path is kept - one pre-processing launch, the boxes
+    mapped back by kernels.detection_unmap with P = tiles x the tile stage's max_predictions, one device-to-host copy per batch; what is
+    forwarded is the wrapper's batched form (tiles cut on the device, tile batches through the model, batched tile NMS, one merge launch).
+    There is no host path: a processing stage without a step description or a callback without `forward_batched` raises."""
+
+    def __init__(self, model, class_names: List[str], post_prediction_callback, device: Optional[str] = None,
+                 image_processor: Union[Processing, List[Processing]] = None, fuse_model: bool = True, fp16: bool = True):
+        if not hasattr(model, "forward_batched") or not hasattr(model, "model"):
+            raise ValueError("SlidingWindowDetectionPipeline takes a SlidingWindowInferenceDetectionWrapper as its model")
+        # device, materialisation and the fp16 decision (the bf16 kernels for architectures that have them, else the once-per-class notice and
+        # fp32) are the wrapped detector's, exactly as in predict() on the detector itself
+        super().__init__(model=model.model, class_names=class_names, post_prediction_callback=post_prediction_callback, device=device,
+                         image_processor=image_processor, fuse_model=fuse_model, fp16=fp16)
+        self.model = model
+
+    def _fuse_model(self, input_size):
+        wrapper = self.model
+        self.model = wrapper.model
+        try:
+            super()._fuse_model((wrapper.tile_size, wrapper.tile_size))  # (the model sees tiles, whatever the image size)
+            fused = self.model
+        finally:
+            self.model = wrapper
+        self.model = wrapper._around(fused)
+        self.model.eval()
+
+    def _model_forward(self, batch: torch.Tensor):
+        return self.model.forward_batched(batch, sliding_window_post_prediction_callback=self.post_prediction_callback)
+
+    def _device_postprocess(self, steps) -> bool:
+        if any(s is None for s in steps):
+            raise NotImplementedError("sliding-window predict(): a processing stage without `inverse_box_steps` has no device path (there is no host path)")
+        return True
+
+    def _batched_rows(self, model_output):
+        return model_output
+
+    def pass_images_through_model(self, batch: torch.Tensor):
+        raise NotImplementedError("sliding-window predict() has no host post-processing path")
