@@ -1613,6 +1613,102 @@ __global__ __launch_bounds__(WM * WN * 64, BN == 32 ? 3 : 2) void pconv_kernel(I
     }
 }
 
+// ---- the kernels that exist: one row of SGX_CONV_KERNELS each.  The launch, the tuning table's loader and the tile override ask this table.
+// One instantiation: igemm_kernel<bm, bn, WM, WN, flat, math, kd, nbuf, ph2, wpl>, or (patch) pconv_kernel<bn, WM, WN, ph2, fpipe, wpl>
+struct ConvForm {
+    int patch, bm, bn, flat, math, kd, nbuf, ph2, wpl, fpipe;
+};
+struct TileWaves {
+    int wm, wn;
+};
+// (WM, WN): 2 x 2 where the filter tile splits into 64-wide halves, else one 32-row block column per wave (the patch tile: 128 rows)
+constexpr TileWaves tile_waves(int bm, int bn) { return bn % 64 == 0 ? TileWaves{2, 2} : TileWaves{bm / 32, 1}; }
+constexpr uint32_t conv_form_key(int patch, int bm, int bn, int flat, int math, int kd, int nbuf, int ph2, int wpl, int fpipe) {
+    return (uint32_t)patch << 31 | (uint32_t)fpipe << 30 | (uint32_t)bm << 22 | (uint32_t)bn << 14 | (uint32_t)flat << 13 | (uint32_t)math << 12 |
+           (uint32_t)kd << 6 | (uint32_t)nbuf << 4 | (uint32_t)ph2 << 2 | (uint32_t)wpl;
+}
+// (launch has filled the tile counts of the plan: mt, nt, nblk, chunk, fd_nt)
+template <int BM, int BN, bool FLAT, int MATH, int KD, int NBUF, int PH2, int WPL>
+static void launch_igemm(IgemmParams& p, void* stream) {
+    constexpr TileWaves W = tile_waves(BM, BN);
+    p.fd_hw = sgx_make_fastdiv(p.Ha * p.Wa);
+    p.fd_wa = sgx_make_fastdiv(p.Wa);
+    SGX_LAUNCH((igemm_kernel<BM, BN, W.wm, W.wn, FLAT, MATH, KD, NBUF, PH2, WPL>), dim3(p.chunk * 8), dim3(W.wm * W.wn * 64), 0, stream, p);
+}
+template <int BN, int PH2, bool FPIPE, bool WPL>
+static void launch_pconv(IgemmParams& p, void* stream) {
+    constexpr TileWaves W = tile_waves(128, BN);
+    p.fd_txy = sgx_make_fastdiv(sgx_cdiv(p.Wa, PC_TW) * sgx_cdiv(p.Ha, PC_TH));
+    p.fd_tx = sgx_make_fastdiv(sgx_cdiv(p.Wa, PC_TW));
+    SGX_LAUNCH((pconv_kernel<BN, W.wm, W.wn, PH2, FPIPE, WPL>), dim3(p.chunk * 8), dim3(W.wm * W.wn * 64), 0, stream, p);
+}
+// tile sets (bm, bn) a loop form is built for
+#define IG_TILES_ALL(X, ...) \
+    X(128, 128, __VA_ARGS__) X(128, 96, __VA_ARGS__) X(128, 64, __VA_ARGS__) X(128, 32, __VA_ARGS__) X(64, 128, __VA_ARGS__) X(64, 96, __VA_ARGS__) X(64, 64, __VA_ARGS__) X(64, 32, __VA_ARGS__)
+#define IG_TILES_NARROW(X, ...) X(128, 64, __VA_ARGS__) X(128, 32, __VA_ARGS__) X(64, 64, __VA_ARGS__) X(64, 32, __VA_ARGS__)
+#define IG_TILES_ONE_BLOCK(X, ...) X(128, 32, __VA_ARGS__) X(64, 64, __VA_ARGS__) X(64, 32, __VA_ARGS__)  // one 32 x 32 block per wave
+// the two-source / two-output kernels exist for the tiles the heuristic picks (pick_tile_heuristic)
+#define IG_TILES_PH2(X, ...) X(128, 96, __VA_ARGS__) X(128, 32, __VA_ARGS__) X(64, 64, __VA_ARGS__) X(64, 32, __VA_ARGS__)
+// G(bm, bn, flat, math, kd, nbuf, ph2, wpl) / P(bn, ph2, fpipe, wpl).  No row may spill (tools/kernel_regs.py --check): one that does leaves the list.
+#define SGX_CONV_KERNELS(G, P)                                                                                                            \
+    /* fp32 pipe: 16-deep two-buffer loop, 32-deep slabs in one LDS buffer, (variant 11) all slabs up front for <= 4 slabs */             \
+    IG_TILES_ALL(G, 0, 0, 16, 2, 0, 0)                                                                                                    \
+    IG_TILES_ALL(G, 0, 0, 32, 1, 0, 0)                                                                                                    \
+    IG_TILES_NARROW(G, 0, 0, 32, 3, 0, 0)                                                                                                 \
+    /* bf16x3: the same two loops, (variant 6) the pipelined loop, filter planes copied to LDS (wpl 1) or read into registers (wpl 2) */  \
+    IG_TILES_ALL(G, 0, 1, 16, 2, 0, 0)                                                                                                    \
+    IG_TILES_ALL(G, 0, 1, 32, 1, 0, 0)                                                                                                    \
+    IG_TILES_ONE_BLOCK(G, 0, 1, 32, 2, 0, 0)                                                                                              \
+    IG_TILES_ALL(G, 0, 1, 32, 1, 0, 1)                                                                                                    \
+    IG_TILES_NARROW(G, 0, 1, 32, 1, 0, 2)                                                                                                 \
+    /* flattened (tap, channel) K axis (C < 16): narrow tiles only; the two-output form is the RGB stem's QARepVGG block (C = 4) */       \
+    IG_TILES_NARROW(G, 1, 0, 16, 2, 0, 0)                                                                                                 \
+    IG_TILES_NARROW(G, 1, 1, 16, 2, 0, 0)                                                                                                 \
+    G(128, 64, 1, 0, 16, 2, 2, 0) G(64, 64, 1, 0, 16, 2, 2, 0)                                                                            \
+    /* second source into the same accumulator (ph2 1) / into a second output (ph2 2); the plan sends no 128x96 launch to wpl 2 */       \
+    IG_TILES_PH2(G, 0, 0, 16, 2, 1, 0) IG_TILES_PH2(G, 0, 0, 16, 2, 2, 0)                                                                 \
+    IG_TILES_PH2(G, 0, 0, 32, 1, 1, 0) IG_TILES_PH2(G, 0, 0, 32, 1, 2, 0)                                                                 \
+    IG_TILES_PH2(G, 0, 1, 16, 2, 1, 0) IG_TILES_PH2(G, 0, 1, 16, 2, 2, 0)                                                                 \
+    IG_TILES_PH2(G, 0, 1, 32, 1, 1, 0) IG_TILES_PH2(G, 0, 1, 32, 1, 2, 0)                                                                 \
+    IG_TILES_PH2(G, 0, 1, 32, 1, 1, 1) IG_TILES_PH2(G, 0, 1, 32, 1, 2, 1)                                                                 \
+    IG_TILES_PH2(G, 0, 1, 32, 1, 1, 2) IG_TILES_PH2(G, 0, 1, 32, 1, 2, 2)                                                                 \
+    /* patch kernel, one fragment set (fpipe 0): every filter tile and source form (the plan sends two outputs to 32 filters only) */     \
+    P(64, 0, 0, 0) P(64, 0, 0, 1) P(64, 1, 0, 0) P(64, 1, 0, 1) P(64, 2, 0, 0) P(64, 2, 0, 1)                                             \
+    P(32, 0, 0, 0) P(32, 0, 0, 1) P(32, 1, 0, 0) P(32, 1, 0, 1) P(32, 2, 0, 0) P(32, 2, 0, 1)                                             \
+    /* two fragment sets.  Absent because the second set spills (round 6): the 32-filter two-output form (50 / 29 spilled dwords under   \
+       its three-wave bound - only the measurement switch "always" reached it) and the 64-filter two-source form that splits its        \
+       filters in the kernel (10 spilled dwords at 256 registers - reached with the planes switched off) */                              \
+    P(64, 0, 1, 0) P(64, 0, 1, 1) P(64, 1, 1, 1) P(64, 2, 1, 0) P(64, 2, 1, 1)                                                            \
+    P(32, 0, 1, 0) P(32, 0, 1, 1) P(32, 1, 1, 0) P(32, 1, 1, 1)
+typedef void (*ConvLauncher)(IgemmParams&, void*);
+// the row of a form, or nullptr: a compiled switch over the packed key (no allocation, a handful of compares)
+static ConvLauncher conv_kernel(const ConvForm& f) {
+    if ((unsigned)f.bm > 255u || (unsigned)f.bn > 255u) return nullptr;  // (tiles may come from the measurement override)
+    switch (conv_form_key(f.patch, f.bm, f.bn, f.flat, f.math, f.kd, f.nbuf, f.ph2, f.wpl, f.fpipe)) {
+#define SGX_G(BM, BN, FLAT, MATH, KD, NBUF, PH2, WPL) \
+    case conv_form_key(0, BM, BN, FLAT, MATH, KD, NBUF, PH2, WPL, 0): return launch_igemm<BM, BN, FLAT != 0, MATH, KD, NBUF, PH2, WPL>;
+#define SGX_P(BN, PH2, FPIPE, WPL) \
+    case conv_form_key(1, 0, BN, 0, 0, 0, 0, PH2, WPL, FPIPE): return launch_pconv<BN, PH2, FPIPE != 0, WPL != 0>;
+        SGX_CONV_KERNELS(SGX_G, SGX_P)
+#undef SGX_G
+#undef SGX_P
+    }
+    return nullptr;
+}
+// Is the one-source GEMM loop `f` built for the tile (0 = any; tiles are whole 32 x 32 MFMA blocks)?  The tuning table's loader asks.
+static bool conv_loop_exists(ConvForm f, int bm, int bn) {
+    for (f.bm = bm ? bm : 32; f.bm <= (bm ? bm : 224); f.bm += 32)
+        for (f.bn = bn ? bn : 32; f.bn <= (bn ? bn : 224); f.bn += 32)
+            if (conv_kernel(f)) return true;
+    return false;
+}
+static bool conv_tile_exists(int bm, int bn) { return conv_loop_exists(ConvForm{0, 0, 0, 0, 0, IG_BK, 2, 0, 0, 0}, bm, bn); }
+// the loop a variant asks plan_igemm for: 6 = pipelined bf16x3, 7 = 16-deep, 11 = all slabs up front, 12 = filter fragments in registers
+static bool conv_variant_exists(int v) {
+    return v == 0 || (v == 6 && conv_loop_exists(ConvForm{0, 0, 0, 0, 1, 32, 2, 0, 0, 0}, 0, 0)) || (v == 7 && conv_tile_exists(0, 0)) ||
+           (v == 11 && conv_loop_exists(ConvForm{0, 0, 0, 0, 0, 32, 3, 0, 0, 0}, 0, 0)) || (v == 12 && conv_loop_exists(ConvForm{0, 0, 0, 0, 1, 32, 1, 0, 2, 0}, 0, 0));
+}
+
 // ------------------------------------------------------------------------------------------------
 // tile-shape selection
 // ------------------------------------------------------------------------------------------------
@@ -1652,13 +1748,6 @@ static int conv_math_for(int taps, int C) {
     // mode 4 (measurement; r4a: +0.5 %): the patch kernel on its problems AND the per-problem rule of mode 2 for the rest
     // mode 5 (round 4): mode 4, and the two-source / two-output (QARepVGG) launches follow the same rule
     return (m == 2 || m == 4 || m == 5) ? ((long)taps * C >= g_bf3_min_depth.load(std::memory_order_relaxed) ? 1 : 0) : m;
-}
-// Mode 3: 3x3, stride 1, pad 1, channel counts in 16s -> pconv_kernel (bf16x3 from an LDS-resident patch).  Decidable from the descriptor,
-// so that the forward statistics rows (one per 8 x 16 pixel tile and image) are known before the launch.
-static int conv_variant();
-static bool pconv_shape_ok(int R, int S, int stride, int pad, int C, int K, long HoWo) {
-    return g_conv_math.load(std::memory_order_relaxed) >= 3 && R == 3 && S == 3 && stride == 1 && pad == 1 && C % 16 == 0 && C >= 16 && K % 4 == 0 &&
-           (HoWo >= 1600 || conv_variant() == 9);
 }
 static int pconv_tiles(int N, int H, int W) { return N * sgx_cdiv(H, PC_TH) * sgx_cdiv(W, PC_TW); }
 extern "C" int32_t sgx_debug_set_variant(int32_t v) {
@@ -1717,9 +1806,9 @@ extern "C" int32_t sgx_conv_tuning_load(const int32_t* entries, int32_t n) {
             SGX_CHECK_ARG((e[9] == 0 || e[9] == 32 || e[9] == 64 || e[9] == 96 || e[9] == 128) && wide && e[11] >= 0 &&
                               (e[9] == 0) == (e[10] == 0),  // all 16 tiles of {32, 64, 96, 128}^2 are instantiated
                           "conv_tuning_load: entry %d: no weight-gradient kernel (tile %dx%d, split target %d)", i, e[9], e[10], e[11]);
-        else
-            SGX_CHECK_ARG((e[9] == 0 || e[9] == 64 || e[9] == 128) && wide && (e[11] == 0 || e[11] == 6 || e[11] == 7 || e[11] == 11 || e[11] == 12),
-                          "conv_tuning_load: entry %d: no kernel (tile %dx%d, variant %d)", i, e[9], e[10], e[11]);
+        else  // forward / data gradient: a tile (0 = the heuristic's) and a variant the kernel table has
+            SGX_CHECK_ARG(conv_tile_exists(e[9], e[10]) && conv_variant_exists(e[11]), "conv_tuning_load: entry %d: no kernel (tile %dx%d, variant %d)", i,
+                          e[9], e[10], e[11]);
         m[std::array<int, 9>{e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8]}] = TuneVal{e[9], e[10], e[11]};
     }
     {
@@ -1736,23 +1825,6 @@ static int conv_variant() {
     return v ? v : (t_tune ? t_tune->var : 0);
 }
 
-static TileCfg pick_tile_heuristic(long M, int N);
-static TileCfg pick_tile(long M, int N, int math) {
-    TileCfg t = pick_tile_heuristic(M, N);
-    if (t_tune && t_tune->bm) t.bm = t_tune->bm;
-    if (t_tune && t_tune->bn) t.bn = t_tune->bn;
-    if (const int o = g_ovr_bm.load(std::memory_order_relaxed)) t.bm = o;
-    if (const int o = g_ovr_bn.load(std::memory_order_relaxed)) t.bn = o;
-    return t;
-}
-// tile of the two-source / two-output launches: the heuristic's, unless the measurement override (sgx_debug_set_tiles) names one of the tiles
-// those kernels are instantiated for
-static TileCfg ph2_tile(long M, int N) {
-    TileCfg t = pick_tile_heuristic(M, N);
-    const int bm = g_ovr_bm.load(std::memory_order_relaxed), bn = g_ovr_bn.load(std::memory_order_relaxed);
-    if ((bm == 128 && bn == 96) || (bm == 128 && bn == 32) || (bm == 64 && bn == 64) || (bm == 64 && bn == 32)) t = TileCfg{bm, bn};
-    return t;
-}
 static TileCfg pick_tile_heuristic(long M, int N) {
     // Measured (tools/conv_tune.py, profiles/r1m_conv_tune.txt: exhaustive search over the 201 conv problems of a YOLO-NAS-S
     // step): the 64x64 tile (4 waves x one 32x32 accumulator, 36 VGPRs, 22 KB LDS -> 7 workgroups per CU) wins on 83 of 140
@@ -1764,126 +1836,17 @@ static TileCfg pick_tile_heuristic(long M, int N) {
     if (N % 96 == 0 && M >= 200000) return TileCfg{128, 96};
     return TileCfg{M >= 16384 ? 128 : 64, 32};
 }
-
-// 32-deep slabs (one LDS buffer) are the default wherever they apply - channel-chunked K axis, C a multiple of 32 (a ragged last chunk
-// would multiply zeros for up to half a slab): measured on MI355X (profiles/r2d_conv_tune_variants.txt) they win on 3x3 and deep 1x1
-// layers alike (+5-10 %, whole-line loads, half the load instructions per FLOP).  Variant 7 (tuning table / sgx_debug_set_variant) = the
-// 16-deep loop; two LDS buffers with 32-deep slabs measured slower (lower occupancy) and were removed.
-static bool igemm_deep_slabs(const IgemmParams& p) { return conv_variant() != 7 && p.C % 32 == 0; }
-// dispatch over the eight non-flat tile shapes for one (MATH, KD, NBUF, PH2)
-#define SGX_IGEMM_TILES(MATH_, KD_, NBUF_, PH2_) SGX_IGEMM_TILES_W(MATH_, KD_, NBUF_, PH2_, 0)
-#define SGX_IGEMM_TILES_W(MATH_, KD_, NBUF_, PH2_, WPL_)                                                                \
-    do {                                                                                                                \
-        if (bm == 128 && bn == 128) launch_igemm<128, 128, 2, 2, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);      \
-        else if (bm == 128 && bn == 96) launch_igemm<128, 96, 4, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);   \
-        else if (bm == 128 && bn == 64) launch_igemm<128, 64, 2, 2, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);   \
-        else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);   \
-        else if (bm == 64 && bn == 128) launch_igemm<64, 128, 2, 2, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);   \
-        else if (bm == 64 && bn == 96) launch_igemm<64, 96, 2, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);     \
-        else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);     \
-        else if (bm == 64 && bn == 32) launch_igemm<64, 32, 2, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);     \
-        else SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: no tile %dx%d (math %d, %d-deep slabs)", bm, bn, MATH_, KD_);         \
-    } while (0)
-// the two-source kernels exist for the tiles the heuristic picks (pick_tile_heuristic): overrides / table entries do not apply to them
-#define SGX_IGEMM_TILES_PH2(MATH_, KD_, NBUF_, PH2_) SGX_IGEMM_TILES_PH2_W(MATH_, KD_, NBUF_, PH2_, 0)
-#define SGX_IGEMM_TILES_PH2_W(MATH_, KD_, NBUF_, PH2_, WPL_)                                                            \
-    do {                                                                                                                \
-        if (bm == 128 && bn == 96) launch_igemm<128, 96, 4, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);        \
-        else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);   \
-        else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);     \
-        else if (bm == 64 && bn == 32) launch_igemm<64, 32, 2, 1, false, MATH_, KD_, NBUF_, PH2_, WPL_>(p, stream);     \
-        else SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv (two sources): no tile %dx%d", bm, bn);                                \
-    } while (0)
-template <int BM, int BN, int WM, int WN, bool FLAT, int MATH = 0, int KD = IG_BK, int NBUF = 2, int PH2 = 0, int WPL = 0>
-static void launch_igemm(IgemmParams& p, void* stream) {
-    p.mt = sgx_cdiv(p.M, BM);
-    p.nt = sgx_cdiv(p.Nout, BN);
-    p.nblk = p.mt * p.nt;
-    p.chunk = sgx_cdiv(p.nblk, 8);
-    p.fd_nt = sgx_make_fastdiv(p.nt);
-    p.fd_hw = sgx_make_fastdiv(p.Ha * p.Wa);
-    p.fd_wa = sgx_make_fastdiv(p.Wa);
-    int grid = p.chunk * 8;
-    SGX_LAUNCH((igemm_kernel<BM, BN, WM, WN, FLAT, MATH, KD, NBUF, PH2, WPL>), dim3(grid), dim3(WM * WN * 64), 0, stream, p);
-}
-
-// ---- pconv dispatch ------------------------------------------------------------------------------------------------------------------
-static bool pconv_ok(const IgemmParams& p, int ph2) {
-    if (g_conv_math.load(std::memory_order_relaxed) < 3) return false;
-    // dense taps whose input offsets all lie in [-1, +1]: the 3x3 stride-1 forward / data gradient, and the output-parity classes of a 3x3
-    // stride-2 data gradient (2x2 / 2x1 / 1x2 taps at offsets {0, +1}; the output grid is then written with stride `so`)
-    if (p.si != 1 || p.Th > 3 || p.Tw > 3 || p.Th * p.Tw < 2 || (p.dstep != 1 && p.dstep != -1)) return false;
-    for (int i = 0; i < p.Th; ++i)
-        if (p.dh0 + p.dstep * i < -1 || p.dh0 + p.dstep * i > 1) return false;
-    for (int j = 0; j < p.Tw; ++j)
-        if (p.dw0 + p.dstep * j < -1 || p.dw0 + p.dstep * j > 1) return false;
-    if (p.C % 16 || p.C < 16 || !p.vec) return false;
-    // A forward launch that emits BatchNorm statistic rows must be a problem sgx_conv2d_fwd_stat_blocks sized those rows for (one row per
-    // patch tile): the 3x3 pad-1 shape of pconv_shape_ok and nothing wider - a 2x2 / 1x3 stride-1 filter would otherwise get patch-tile row
-    // counts written into a buffer allocated for cdiv(M, bm) rows
-    if (p.stat_partials && !(p.Th == 3 && p.Tw == 3 && p.dh0 == -1 && p.dw0 == -1 && p.dstep == 1 && p.so == 1 && p.Nout % 4 == 0)) return false;
-    // Where it pays (r3g, replay of every conv problem of a YOLO-NAS-S step): the stride-1 problems on maps of 40 x 40 and larger (1.25-1.6x
-    // over the fp32 pipe).  20 x 20 maps fill their 8 x 16 tiles to 52 %, and the parity classes of a stride-2 data gradient carry
-    // 2x2 / 2x1 taps only - a quarter of the reuse the patch is staged for, and 0.65x on the 768-channel layer.  Variant 9 lifts both.
-    if (conv_variant() != 9 && (p.so != 1 || (long)p.Ha * p.Wa < 1600)) return false;
-    if (ph2 && p.A2 && !(p.Th2 == 1 && p.Tw2 == 1 && p.dh02 == 0 && p.dw02 == 0)) return false;
-    if (ph2 == 2 && (p.A2 != p.A || p.a2_ld_pix != p.a_ld_pix || p.a2_ld_img != p.a_ld_img)) return false;  // the second filter reads the same patch
-    if ((long)p.Hin * p.Win * p.a_ld_pix * 4 > SGX_BUF_MAX) return false;
-    return true;
-}
-static std::atomic<long> g_fp_hits{0};  // launches that read pre-split filter planes (see fplanes_attach)
-template <int BN, int WM, int WN, int PH2>
-static void launch_pconv(IgemmParams& p, void* stream) {
-    // two fragment sets where they do not cost a wave of occupancy (r3f lab: the 64-filter tile gains 4-6 %, the 32-filter tiles - three
-    // workgroups per CU with one set, two with two - lose 5-15 %); measurement: variant 9 = always
-    // (round 5: the 32-filter tiles of the one- / two-source forms take the second fragment set as well - under their launch bound of three
-    // waves per SIMD they fit it without spilling, 137 / 165 registers; the two-output form does not.  r5f: 716.0 -> 718.8 images/s)
-    const bool fpipe = conv_variant() == 9 || BN == 64 || PH2 != 2;
-    p.mt = pconv_tiles(p.M / (p.Ha * p.Wa), p.Ha, p.Wa);
-    p.nt = sgx_cdiv(p.Nout, BN);
-    p.nblk = p.mt * p.nt;
-    p.chunk = sgx_cdiv(p.nblk, 8);
-    p.fd_nt = sgx_make_fastdiv(p.nt);
-    p.fd_txy = sgx_make_fastdiv(sgx_cdiv(p.Wa, PC_TW) * sgx_cdiv(p.Ha, PC_TH));
-    p.fd_tx = sgx_make_fastdiv(sgx_cdiv(p.Wa, PC_TW));
-    p.stat_nblk = p.mt;
-    // pre-split filter planes (fplanes_attach): every filter of the launch has them, or none is used
-    const bool wpl = p.Wp && (!(PH2 && p.A2) || p.Wp2);
-    if (wpl) g_fp_hits.fetch_add(1, std::memory_order_relaxed);
-    // Forms whose second fragment set spills are not instantiated at all (round 6; tools/kernel_regs.py --check): the 32-filter two-output
-    // form (50 / 29 spilled dwords under its three-wave bound - only the measurement switch "always" reached it) and the 64-filter
-    // two-source form that splits its filters in the kernel (10 spilled dwords at 256 registers - reached with the planes switched off).
-    constexpr bool PIPE_PL = !(BN == 32 && PH2 == 2), PIPE_SPLIT = PIPE_PL && !(BN == 64 && PH2 == 1);
-    if (wpl) {
-        if constexpr (PIPE_PL) {
-            if (fpipe) {
-                SGX_LAUNCH((pconv_kernel<BN, WM, WN, PH2, true, true>), dim3(p.chunk * 8), dim3(WM * WN * 64), 0, stream, p);
-                return;
-            }
-        }
-        SGX_LAUNCH((pconv_kernel<BN, WM, WN, PH2, false, true>), dim3(p.chunk * 8), dim3(WM * WN * 64), 0, stream, p);
-        return;
-    }
-    if constexpr (PIPE_SPLIT) {
-        if (fpipe) {
-            SGX_LAUNCH((pconv_kernel<BN, WM, WN, PH2, true>), dim3(p.chunk * 8), dim3(WM * WN * 64), 0, stream, p);
-            return;
-        }
-    }
-    SGX_LAUNCH((pconv_kernel<BN, WM, WN, PH2, false>), dim3(p.chunk * 8), dim3(WM * WN * 64), 0, stream, p);
-}
-template <int PH2>
-static void launch_pconv_n(IgemmParams& p, void* stream) {
-    // N tile: 64 filters (two 32-wide accumulator columns x two 64-row halves) where that wastes nothing, else 32 (four 32-row waves)
-    // (two outputs: ten filter slabs of 64 rows would leave room for one workgroup per CU only - 32-filter tiles, three per CU)
-    if (PH2 != 2 && (p.Nout % 64 == 0 || (p.Nout > 32 && p.Nout % 32 != 0))) launch_pconv<64, 2, 2, PH2>(p, stream);
-    else launch_pconv<32, 4, 1, PH2>(p, stream);
-}
-static int32_t run_pconv(IgemmParams& p, void* stream, int ph2) {
-    if (ph2 == 0 || !p.A2) launch_pconv_n<0>(p, stream);
-    else if (ph2 == 1) launch_pconv_n<1>(p, stream);
-    else launch_pconv_n<2>(p, stream);
-    return SGX_OK;
+// The heuristic's tile, then the problem's tuning-table entry, then the measurement override (sgx_debug_set_tiles).  Two-source / two-output
+// launches (ph2): the heuristic's tile (no table entries), unless the override names a tile those kernels are built for.
+static TileCfg pick_tile(long M, int N, int ph2) {
+    TileCfg t = pick_tile_heuristic(M, N);
+    const int om = g_ovr_bm.load(std::memory_order_relaxed), on = g_ovr_bn.load(std::memory_order_relaxed);
+    if (ph2) return om && on && conv_kernel(ConvForm{0, om, on, 0, 0, IG_BK, 2, 1, 0, 0}) ? TileCfg{om, on} : t;
+    if (t_tune && t_tune->bm) t.bm = t_tune->bm;
+    if (t_tune && t_tune->bn) t.bn = t_tune->bn;
+    if (om) t.bm = om;
+    if (on) t.bn = on;
+    return t;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1910,6 +1873,7 @@ struct FplanesEntry {
 static std::mutex g_fp_mu;
 static std::unordered_map<const void*, FplanesEntry> g_fp_map;
 static std::atomic<int> g_fp_on{1};
+static std::atomic<long> g_fp_hits{0};  // launches that read pre-split filter planes (counted by launch)
 // Scope depth of the CALLING thread (a process-global boolean let an inner close - nested autograd, a second network on another
 // thread - switch the outer step's planes off, or a launch outside the owning step see them on): a launch looks planes up only while the
 // thread that issues it is inside a training step's forward / backward.
@@ -1994,122 +1958,154 @@ static void fplanes_attach(IgemmParams& p, int ph2) {
     p.wp_bytes = p.wp2_bytes = 0;
     if (t_fp_scope <= 0 || !g_fp_on.load(std::memory_order_relaxed) || p.C % 16) return;
     p.Wp = fplanes_lookup(p.Wt, p.Nout, p.Th * p.Tw, p.C, p.w_ld_n, &p.wp_bytes);
-    if (ph2 && p.A2) p.Wp2 = fplanes_lookup(p.Wt2, p.Nout, p.Th2 * p.Tw2, p.C, p.w2_ld_n, &p.wp2_bytes);
+    if (ph2) p.Wp2 = fplanes_lookup(p.Wt2, p.Nout, p.Th2 * p.Tw2, p.C, p.w2_ld_n, &p.wp2_bytes);
 }
 // launches that read planes since the process started (tests: a planes-path parity check must not pass by never taking the path)
 extern "C" int64_t sgx_debug_filter_planes_hits(void) { return g_fp_hits.load(); }
 
-// ph2: 0 = one source; 1 = second source into the same accumulator; 2 = second source into a second output (see IgemmParams)
-static int32_t run_igemm(IgemmParams& p, int bm, int bn, void* stream, int ph2 = 0) {
-    const int T = p.Th * p.Tw;
-    if (T > SGX_MAX_TAPS) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: more than %d taps", SGX_MAX_TAPS);
-    if (p.w_bytes > SGX_BUF_MAX) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: weight tensor larger than 2 GiB");
-    {
-        const long hw = (long)p.Ha * p.Wa;
-        const long imgs = (bm + hw - 1) / hw + 1;  // images a pixel tile can touch
-        if (imgs * p.a_ld_img * 4 > SGX_BUF_MAX) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: one pixel tile spans more than 2 GiB of input");
-        if (ph2 && p.A2 && imgs * p.a2_ld_img * 4 > SGX_BUF_MAX) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: one pixel tile spans more than 2 GiB of input");
-    }
-    p.vec = (p.Nout % 4 == 0 && p.y_ld_pix % 4 == 0 && p.y_ld_img % 4 == 0 && ((uintptr_t)p.Y % 16) == 0 && ((uintptr_t)p.addend % 16) == 0 &&
-             ((uintptr_t)p.bias % 16) == 0)
-                ? 1
-                : 0;
-    if (p.nreq && !p.vec) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: BatchNorm-reduce requests need 16-byte aligned outputs");
-    fplanes_attach(p, ph2);
-    // algorithmic work: every input element, weight and output element once (fp32); the second source adds its taps
-    const double T2 = (ph2 && p.A2) ? (double)p.Th2 * p.Tw2 : 0.0;
-    // (profiling class 0 = fp32-MFMA implicit GEMM, 2 = the bf16x3 patch kernel, 3 = the implicit GEMM in bf16x3 arithmetic: same algorithmic
-    // FLOPs, priced separately by bench.py)
-    const bool gemm_bf3 = conv_math_for(T, p.C) == 1 && (!ph2 || g_conv_math.load(std::memory_order_relaxed) == 5);
-    SGX_PROF(pconv_ok(p, ph2) ? 2 : gemm_bf3 ? 3 : 0, 2.0 * (double)p.M * (double)p.Nout * (double)p.C * ((double)T + T2),
-             4.0 * ((double)p.M / ((double)p.Ha * p.Wa) * p.Hin * p.Win * p.C * (ph2 == 1 && p.A2 ? 2.0 : 1.0) + (double)p.Nout * p.C * (T + T2) +
-                    (double)p.M * p.Nout * (ph2 == 2 ? 2.0 : 1.0)), stream);
-    const bool flat = p.C < IG_BK && T > 1;
-    if (!pconv_ok(p, ph2) && p.stat_partials && p.dstep == 1 && p.so == 1 && pconv_shape_ok(p.Th, p.Tw, p.si, -p.dh0, p.C, p.Nout, (long)p.Ha * p.Wa))
-        SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv (math mode 3): the statistics rows of this forward follow the patch kernel's tiles, which needs 16-byte aligned operands");
-    if (pconv_ok(p, ph2)) {
-        int32_t rc = run_pconv(p, stream, ph2);
-        if (rc) return rc;
-        SGX_CHECK_LAUNCH("pconv");
-        return SGX_OK;
-    }
-    if (ph2 == 2 && flat && p.vec && !gemm_bf3) {
-        // the two-output forward of a block with few input channels (the RGB stem, C = 4): flattened (tap, channel) K axis, fp32 pipe
-        if (bm == 128) launch_igemm<128, 64, 2, 2, true, 0, IG_BK, 2, 2>(p, stream);
-        else launch_igemm<64, 64, 2, 2, true, 0, IG_BK, 2, 2>(p, stream);
-    } else if (ph2) {
-        if (flat || !p.vec) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv (two sources): needs C >= 16 and 16-byte aligned outputs");
-        const bool bf3 = gemm_bf3;  // (mode 5: the primary source's depth decides for the launch)
-        if (p.C % 32 == 0) {
-            if (bf3 && p.Wp && (!p.A2 || p.Wp2)) {
-                g_fp_hits.fetch_add(1, std::memory_order_relaxed);
-                // register fragments (mode 2, or variant 12; the tiles of one 32-filter block per wave) - by default the two-output forward
-                // pair takes them (r5ac lab: -6 %) and the two-source data gradient does not (+8 %)
-                const int fpm = g_fp_on.load(std::memory_order_relaxed);
-                const bool wpr = (fpm == 2 || conv_variant() == 12 || (fpm == 1 && ph2 == 2)) && bn <= 64;
-                if (wpr && ph2 == 1) SGX_IGEMM_TILES_PH2_W(1, 32, 1, 1, 2);
-                else if (wpr) SGX_IGEMM_TILES_PH2_W(1, 32, 1, 2, 2);
-                else if (ph2 == 1) SGX_IGEMM_TILES_PH2_W(1, 32, 1, 1, 1);
-                else SGX_IGEMM_TILES_PH2_W(1, 32, 1, 2, 1);
-            } else if (bf3) {
-                if (ph2 == 1) SGX_IGEMM_TILES_PH2(1, 32, 1, 1);
-                else SGX_IGEMM_TILES_PH2(1, 32, 1, 2);
-            } else if (ph2 == 1) SGX_IGEMM_TILES_PH2(0, 32, 1, 1);
-            else SGX_IGEMM_TILES_PH2(0, 32, 1, 2);
-        } else {
-            if (bf3) {
-                if (ph2 == 1) SGX_IGEMM_TILES_PH2(1, 16, 2, 1);
-                else SGX_IGEMM_TILES_PH2(1, 16, 2, 2);
-            } else if (ph2 == 1) SGX_IGEMM_TILES_PH2(0, 16, 2, 1);
-            else SGX_IGEMM_TILES_PH2(0, 16, 2, 2);
-        }
-    } else if (gemm_bf3) {
-        if (flat && bn > 64) bn = 64;
-        if (flat && bm == 128 && bn == 64) launch_igemm<128, 64, 2, 2, true, 1>(p, stream);
-        else if (flat && bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, true, 1>(p, stream);
-        else if (flat && bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, true, 1>(p, stream);
-        else if (flat && bm == 64 && bn == 32) launch_igemm<64, 32, 2, 1, true, 1>(p, stream);
-        else if (flat) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv (bf16x3): no flat tile %dx%d", bm, bn);
-        else if (igemm_deep_slabs(p) && conv_variant() == 6 && bm * bn <= 128 * 32) {
-            // the pipelined loop (two LDS buffers: tiles whose two slabs fit 64 KB)
-            if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, 1, 32, 2, 0>(p, stream);
-            else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, 1, 32, 2, 0>(p, stream);
-            else launch_igemm<64, 32, 2, 1, false, 1, 32, 2, 0>(p, stream);
-        } else if (igemm_deep_slabs(p) && p.Wp) {
-            g_fp_hits.fetch_add(1, std::memory_order_relaxed);
-            // register fragments: mode 2, or the problem's tuning-table variant 12 (tools/conv_tune.py measures both forms per problem)
-            if ((g_fp_on.load(std::memory_order_relaxed) == 2 || conv_variant() == 12) && bn <= 64) {
-                if (bm == 128 && bn == 64) launch_igemm<128, 64, 2, 2, false, 1, 32, 1, 0, 2>(p, stream);
-                else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, 1, 32, 1, 0, 2>(p, stream);
-                else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, 1, 32, 1, 0, 2>(p, stream);
-                else if (bm == 64 && bn == 32) launch_igemm<64, 32, 2, 1, false, 1, 32, 1, 0, 2>(p, stream);
-                else SGX_IGEMM_TILES_W(1, 32, 1, 0, 1);
-            } else SGX_IGEMM_TILES_W(1, 32, 1, 0, 1);
-        }
-        else if (igemm_deep_slabs(p)) SGX_IGEMM_TILES(1, 32, 1, 0);
-        else SGX_IGEMM_TILES(1, 16, 2, 0);
-    } else if (flat) {
-        if (bn > 64) bn = 64;  // the flat variants exist for the narrow tiles only (stem layers have few output channels)
-        if (bm == 128 && bn == 64) launch_igemm<128, 64, 2, 2, true>(p, stream);
-        else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, true>(p, stream);
-        else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, true>(p, stream);
-        else if (bm == 64 && bn == 32) launch_igemm<64, 32, 2, 1, true>(p, stream);
-        else SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv: no flat tile %dx%d", bm, bn);
-    } else if (igemm_deep_slabs(p) && conv_variant() == 11 && T * ((p.C + 31) / 32) <= 4 && bm * bn <= 128 * 64 && bn != 96 && bn != 128) {
-        // all slabs up front (reductions of <= 4 slabs: shallow 1x1 layers)
-        if (bm == 128 && bn == 64) launch_igemm<128, 64, 2, 2, false, 0, 32, 3, 0>(p, stream);
-        else if (bm == 64 && bn == 64) launch_igemm<64, 64, 2, 2, false, 0, 32, 3, 0>(p, stream);
-        else if (bm == 128 && bn == 32) launch_igemm<128, 32, 4, 1, false, 0, 32, 3, 0>(p, stream);
-        else launch_igemm<64, 32, 2, 1, false, 0, 32, 3, 0>(p, stream);
-    } else if (igemm_deep_slabs(p)) SGX_IGEMM_TILES(0, 32, 1, 0);  // 32-deep slabs (see igemm_kernel): whole-line loads
-    else SGX_IGEMM_TILES(0, 16, 2, 0);
-    SGX_CHECK_LAUNCH("igemm");
-    return SGX_OK;
+// ------------------------------------------------------------------------------------------------
+// The plan of one launch: which kernel runs, on which tiles, and therefore how many statistics rows it writes.  The row-count entry points,
+// the pre-launch checks of a data gradient with requests and the launch read the SAME plan (rows sized for another tiling).
+// ------------------------------------------------------------------------------------------------
+struct ConvPlan {
+    ConvForm form;
+    ConvLauncher kernel;  // the table's row of `form`
+    int mt;               // pixel tiles = statistics rows
+    int vec;              // IgemmParams::vec
+    int prof_cls;         // profiling class: 0 = fp32-MFMA implicit GEMM, 2 = the bf16x3 patch kernel, 3 = the implicit GEMM in bf16x3 arithmetic
+    bool req_ok;          // the launch can carry BatchNorm-reduce requests
+    int32_t err;          // SGX_OK, or why the problem cannot run (msg)
+    char msg[160];
+};
+// The patch kernel's shape (mode 3 and up): dense taps whose input offsets all lie in [-1, +1] - the 3x3 stride-1 forward / data gradient, and
+// the output-parity classes of a 3x3 stride-2 data gradient (2x2 / 2x1 / 1x2 taps at offsets {0, +1}; the output grid is then written with
+// stride `so`) - and channel counts in 16s.  Decidable from the descriptor, so that forward statistics rows are known before the launch.
+static bool pconv_shape_ok(const IgemmParams& p, int ph2, bool stats, int variant) {
+    if (g_conv_math.load(std::memory_order_relaxed) < 3) return false;
+    if (p.si != 1 || p.Th > 3 || p.Tw > 3 || p.Th * p.Tw < 2 || (p.dstep != 1 && p.dstep != -1)) return false;
+    for (int i = 0; i < p.Th; ++i)
+        if (p.dh0 + p.dstep * i < -1 || p.dh0 + p.dstep * i > 1) return false;
+    for (int j = 0; j < p.Tw; ++j)
+        if (p.dw0 + p.dstep * j < -1 || p.dw0 + p.dstep * j > 1) return false;
+    if (p.C % 16 || p.C < 16) return false;
+    // A forward launch that emits BatchNorm statistic rows (one per 8 x 16 pixel tile and image): the 3x3 pad-1 shape and nothing wider - a
+    // 2x2 / 1x3 stride-1 filter is not a shape whose rows callers size per patch tile
+    if (stats && !(p.Th == 3 && p.Tw == 3 && p.dh0 == -1 && p.dw0 == -1 && p.dstep == 1 && p.so == 1 && p.Nout % 4 == 0)) return false;
+    // Where it pays (r3g, replay of every conv problem of a YOLO-NAS-S step): the stride-1 problems on maps of 40 x 40 and larger (1.25-1.6x
+    // over the fp32 pipe).  20 x 20 maps fill their 8 x 16 tiles to 52 %, and the parity classes of a stride-2 data gradient carry
+    // 2x2 / 2x1 taps only - a quarter of the reuse the patch is staged for, and 0.65x on the 768-channel layer.  Variant 9 lifts both.
+    if (variant != 9 && (p.so != 1 || (long)p.Ha * p.Wa < 1600)) return false;
+    if (ph2 && !(p.Th2 == 1 && p.Tw2 == 1 && p.dh02 == 0 && p.dw02 == 0)) return false;
+    return !(ph2 == 2 && (p.A2 != p.A || p.a2_ld_pix != p.a_ld_pix || p.a2_ld_img != p.a_ld_img));  // the second filter reads the same patch
 }
-static TileCfg igemm_tile(const IgemmParams& p) {
-    TileCfg t = pick_tile(p.M, p.Nout, conv_math_for(p.Th * p.Tw, p.C));
-    if (p.C < IG_BK && p.Th * p.Tw > 1 && t.bn > 64) t.bn = 64;
-    return t;
+#define SGX_PLAN_FAIL(...) return pl.err = SGX_ERR_UNSUPPORTED, snprintf(pl.msg, sizeof(pl.msg), __VA_ARGS__), pl
+// ph2: 0 = one source; 1 = second source into the same accumulator; 2 = second source into a second output (see IgemmParams).  aligned: Y,
+// addend and bias are 16-byte aligned (callers without addresses say what they will pass); stats: forward statistics rows.  Launches nothing.
+static ConvPlan plan_igemm(const IgemmParams& p, int ph2, bool aligned, bool stats) {
+    ConvPlan pl = {};
+    pl.form.ph2 = ph2;
+    const int T = p.Th * p.Tw, mode = g_conv_math.load(std::memory_order_relaxed), variant = conv_variant(), fpm = g_fp_on.load(std::memory_order_relaxed);
+    const long hw = (long)p.Ha * p.Wa;
+    const TileCfg t = pick_tile(p.M, p.Nout, ph2);
+    if (T > SGX_MAX_TAPS) SGX_PLAN_FAIL("conv: more than %d taps", SGX_MAX_TAPS);
+    if (p.w_bytes > SGX_BUF_MAX) SGX_PLAN_FAIL("conv: weight tensor larger than 2 GiB");
+    const long imgs = (t.bm + hw - 1) / hw + 1;  // images a pixel tile can touch
+    if (imgs * p.a_ld_img * 4 > SGX_BUF_MAX || (ph2 && imgs * p.a2_ld_img * 4 > SGX_BUF_MAX)) SGX_PLAN_FAIL("conv: one pixel tile spans more than 2 GiB of input");
+    pl.vec = (aligned && p.Nout % 4 == 0 && p.y_ld_pix % 4 == 0 && p.y_ld_img % 4 == 0) ? 1 : 0;
+    const bool flat = p.C < IG_BK && T > 1;
+    // (mode 5: the primary source's depth decides for a two-source / two-output launch)
+    const bool bf3 = conv_math_for(T, p.C) == 1 && (!ph2 || mode == 5);
+    // 32-deep slabs (one LDS buffer) are the default wherever they apply - channel-chunked K axis, C a multiple of 32 (a ragged last chunk
+    // would multiply zeros for up to half a slab): measured on MI355X (profiles/r2d_conv_tune_variants.txt) they win on 3x3 and deep 1x1
+    // layers alike (+5-10 %, whole-line loads, half the load instructions per FLOP).  Variant 7 (tuning table / sgx_debug_set_variant) = the
+    // 16-deep loop; two LDS buffers with 32-deep slabs measured slower (lower occupancy) and were removed.
+    const bool deep = p.C % 32 == 0 && (ph2 || variant != 7);
+    const bool planes = p.Wp && (!ph2 || p.Wp2);  // pre-split filter planes (fplanes_attach): every filter of the launch has them, or none is used
+    pl.req_ok = pl.vec && !flat && !(ph2 && p.C < IG_BK);
+    ConvForm& f = pl.form;
+    const bool patch_shape = pconv_shape_ok(p, ph2, stats, variant);
+    if (patch_shape && pl.vec && (long)p.Hin * p.Win * p.a_ld_pix * 4 <= SGX_BUF_MAX) {
+        pl.prof_cls = 2;
+        pl.mt = pconv_tiles((int)(p.M / hw), p.Ha, p.Wa);
+        f.patch = 1;
+        // N tile: 64 filters (two 32-wide accumulator columns x two 64-row halves) where that wastes nothing, else 32 (four 32-row waves)
+        // (two outputs: ten filter slabs of 64 rows would leave room for one workgroup per CU only - 32-filter tiles, three per CU)
+        f.bn = (ph2 != 2 && (p.Nout % 64 == 0 || (p.Nout > 32 && p.Nout % 32 != 0))) ? 64 : 32;
+        f.wpl = planes;
+        // two fragment sets where they do not cost a wave of occupancy (r3f lab: the 64-filter tile gains 4-6 %, the 32-filter tiles - three
+        // workgroups per CU with one set, two with two - lose 5-15 %); measurement: variant 9 = always
+        // (round 5: the 32-filter tiles of the one- / two-source forms take the second fragment set as well - under their launch bound of three
+        // waves per SIMD they fit it without spilling, 137 / 165 registers; the two-output form does not.  r5f: 716.0 -> 718.8 images/s)
+        f.fpipe = variant == 9 || f.bn == 64 || ph2 != 2;
+        pl.kernel = conv_kernel(f);
+        if (!pl.kernel && f.fpipe) {  // (a form whose second fragment set spills is not in the table: one set)
+            f.fpipe = 0;
+            pl.kernel = conv_kernel(f);
+        }
+        if (!pl.kernel) SGX_PLAN_FAIL("conv (patch kernel): no %d-filter tile", f.bn);
+        return pl;
+    }
+    // callers sized the statistics rows for the patch kernel's tiles before they had addresses: refuse, do not write another tiling
+    if (stats && patch_shape) {
+        pl.mt = pconv_tiles((int)(p.M / hw), p.Ha, p.Wa);
+        SGX_PLAN_FAIL("conv (math mode 3): the statistics rows of this forward follow the patch kernel's tiles, which needs 16-byte aligned operands");
+    }
+    pl.prof_cls = bf3 ? 3 : 0;
+    f.bm = t.bm;
+    f.bn = flat && t.bn > 64 ? 64 : t.bn;  // the flat variants exist for the narrow tiles only (stem layers have few output channels)
+    f.flat = flat;
+    f.math = bf3;
+    f.kd = deep ? 32 : IG_BK;
+    f.nbuf = deep ? 1 : 2;
+    if (ph2 == 2 && flat && pl.vec && !bf3) {
+        // the two-output forward of a block with few input channels (the RGB stem, C = 4): 64-filter tiles
+        f.bm = t.bm == 128 ? 128 : 64;
+        f.bn = 64;
+    } else if (ph2) {
+        if (flat || !pl.vec) SGX_PLAN_FAIL("conv (two sources): needs C >= 16 and 16-byte aligned outputs");
+        // register fragments (mode 2, or variant 12; the tiles of one 32-filter block per wave) - by default the two-output forward
+        // pair takes them (r5ac lab: -6 %) and the two-source data gradient does not (+8 %)
+        if (bf3 && deep && planes) f.wpl = ((fpm == 2 || variant == 12 || (fpm == 1 && ph2 == 2)) && f.bn <= 64) ? 2 : 1;
+    } else if (bf3 && deep) {
+        // variant 6: the pipelined loop (two LDS buffers: tiles whose two slabs fit 64 KB)
+        if (variant == 6 && f.bm * f.bn <= 128 * 32) f.nbuf = 2;
+        // register fragments: mode 2, or the problem's tuning-table variant 12 (tools/conv_tune.py measures both forms per problem)
+        else if (planes) f.wpl = ((fpm == 2 || variant == 12) && f.bn <= 64) ? 2 : 1;
+    } else if (deep && variant == 11 && T * ((p.C + 31) / 32) <= 4 && f.bm * f.bn <= 128 * 64 && f.bn != 96 && f.bn != 128) {
+        f.nbuf = 3;  // all slabs up front (reductions of <= 4 slabs: shallow 1x1 layers)
+    }
+    pl.mt = sgx_cdiv(p.M, f.bm);
+    pl.kernel = conv_kernel(f);
+    if (!pl.kernel) {
+        if (ph2) SGX_PLAN_FAIL("conv (two sources): no tile %dx%d", f.bm, f.bn);
+        if (flat) SGX_PLAN_FAIL("conv%s: no flat tile %dx%d", bf3 ? " (bf16x3)" : "", f.bm, f.bn);
+        SGX_PLAN_FAIL("conv: no tile %dx%d (math %d, %d-deep slabs)", f.bm, f.bn, f.math, f.kd);
+    }
+    return pl;
+}
+#undef SGX_PLAN_FAIL
+static ConvPlan plan_launch(IgemmParams& p, int ph2) {
+    fplanes_attach(p, ph2);
+    return plan_igemm(p, ph2, ((uintptr_t)p.Y % 16) == 0 && ((uintptr_t)p.addend % 16) == 0 && ((uintptr_t)p.bias % 16) == 0, p.stat_partials != nullptr);
+}
+static int32_t launch(const ConvPlan& pl, IgemmParams& p, void* stream) {
+    if (pl.err) SGX_FAIL(pl.err, "%s", pl.msg);
+    const int ph2 = pl.form.ph2;
+    p.vec = pl.vec;
+    p.mt = p.stat_nblk = pl.mt;
+    p.nt = sgx_cdiv(p.Nout, pl.form.bn);
+    p.nblk = p.mt * p.nt;
+    p.chunk = sgx_cdiv(p.nblk, 8);
+    p.fd_nt = sgx_make_fastdiv(p.nt);
+    // algorithmic work: every input element, weight and output element once (fp32); the second source adds its taps
+    const double T = (double)p.Th * p.Tw, T2 = ph2 ? (double)p.Th2 * p.Tw2 : 0.0;
+    SGX_PROF(pl.prof_cls, 2.0 * (double)p.M * (double)p.Nout * (double)p.C * (T + T2),
+             4.0 * ((double)p.M / ((double)p.Ha * p.Wa) * p.Hin * p.Win * p.C * (ph2 == 1 ? 2.0 : 1.0) + (double)p.Nout * p.C * (T + T2) +
+                    (double)p.M * p.Nout * (ph2 == 2 ? 2.0 : 1.0)), stream);
+    if (pl.form.wpl) g_fp_hits.fetch_add(1, std::memory_order_relaxed);
+    pl.kernel(p, stream);
+    SGX_CHECK_LAUNCH(pl.form.patch ? "pconv" : "igemm");
+    return SGX_OK;
 }
 
 static int32_t check_desc(const sgx_conv_desc* d) {
@@ -2128,57 +2124,11 @@ static long view_bytes(int N, int H, int W, int C, long ld_pix, long ld_img) {
     return ((long)(N - 1) * ld_img + ((long)H * W - 1) * ld_pix + C) * 4;
 }
 
-extern "C" int32_t sgx_conv2d_fwd_stat_blocks(const sgx_conv_desc* d) {
-    if (pconv_shape_ok(d->R, d->S, d->stride, d->pad, d->C, d->K, (long)d->Ho * d->Wo)) return pconv_tiles(d->N, d->Ho, d->Wo);
-    TuneScope tune(0, d);
-    long M = (long)d->N * d->Ho * d->Wo;
-    TileCfg t = pick_tile(M, d->K, conv_math_for(d->R * d->S, d->C));
-    return sgx_cdiv(M, t.bm);
-}
-
-extern "C" int32_t sgx_conv2d_fwd(const sgx_conv_desc* d, const float* x, const float* w, const float* bias,
-                                  const float* addend, float* y, int32_t act, float* stat_partials, void* stream) {
-    int32_t rc = check_desc(d);
-    if (rc) return rc;
-    SGX_CHECK_ARG(x && w && y, "conv fwd: null pointer");
-    TuneScope tune(0, d);
+// what a descriptor decides about a forward launch (operands: the caller's; all NULL where only the plan is wanted)
+static IgemmParams fwd_params(const sgx_conv_desc* d, const float* x, const float* w, float* y, float* stat_partials) {
     IgemmParams p;
     memset(&p, 0, sizeof(p));
-    p.A = x; p.Wt = w; p.bias = bias; p.addend = addend; p.Y = y; p.stat_partials = stat_partials;
-    p.M = d->N * d->Ho * d->Wo; p.Ha = d->Ho; p.Wa = d->Wo; p.Hin = d->H; p.Win = d->W;
-    p.C = d->C; p.Nout = d->K; p.Th = d->R; p.Tw = d->S;
-    p.dh0 = -d->pad; p.dw0 = -d->pad; p.dstep = 1;
-    p.si = d->stride; p.so = 1; p.ph = 0; p.pw = 0; p.Hout = d->Ho; p.Wout = d->Wo;
-    p.a_ld_pix = d->x_ld_pix; p.a_ld_img = d->x_ld_img; p.y_ld_pix = d->y_ld_pix; p.y_ld_img = d->y_ld_img;
-    p.w_ld_n = (long)d->R * d->S * d->C;
-    p.a_bytes = view_bytes(d->N, d->H, d->W, d->C, d->x_ld_pix, d->x_ld_img);
-    p.w_bytes = (long)d->K * p.w_ld_n * 4;
-    p.act = act; p.accumulate = 0;
-    TileCfg t = pick_tile(p.M, p.Nout, conv_math_for(p.Th * p.Tw, p.C));  // the statistics rows follow the M tile: keep it in step with sgx_conv2d_fwd_stat_blocks
-    p.stat_nblk = sgx_cdiv(p.M, t.bm);
-    TileCfg u = igemm_tile(p);
-    return run_igemm(p, t.bm, u.bn, stream);
-}
-
-// y = conv RxS(x, w) (no bias), u = conv1x1(x, w1) + bias1 with the same stride, as ONE launch: the 1x1 filter reads exactly the centre
-// tap of the RxS one (pad = R / 2), so the workgroup that owns an output tile walks the taps of w into one accumulator and then the
-// centre tap again with w1 into a second one.  stat5: [5][sgx_conv2d_fwd_dual_stat_blocks(d)][K] = sum y, y^2, u0, u0^2, y*u0 per row block (u0 = u - bias1).
-extern "C" int32_t sgx_conv2d_fwd_dual_stat_blocks(const sgx_conv_desc* d) {
-    if (pconv_shape_ok(d->R, d->S, d->stride, d->pad, d->C, d->K, (long)d->Ho * d->Wo)) return pconv_tiles(d->N, d->Ho, d->Wo);
-    long M = (long)d->N * d->Ho * d->Wo;
-    return sgx_cdiv(M, ph2_tile(M, d->K).bm);
-}
-extern "C" int32_t sgx_conv2d_fwd_dual(const sgx_conv_desc* d, const float* x, const float* w, const float* w1, const float* bias1, float* y,
-                                       float* u, float* stat5, void* stream) {
-    int32_t rc = check_desc(d);
-    if (rc) return rc;
-    SGX_CHECK_ARG(x && w && w1 && y && u && stat5, "conv fwd_dual: null pointer");
-    SGX_CHECK_ARG(d->R == d->S && (d->R & 1) && d->pad == d->R / 2, "conv fwd_dual: odd square filter with pad = R / 2 (the 1x1 branch reads its centre tap)");
-    SGX_CHECK_ARG(((uintptr_t)u % 16) == 0, "conv fwd_dual: needs a 16-byte aligned second output");
-    SGX_CHECK_ARG(d->C >= IG_BK || d->K <= 64, "conv fwd_dual: C < 16 (the flattened K axis) has the 64-filter tiles only (K = %d)", d->K);
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = x; p.Wt = w; p.Y = y; p.stat_partials = stat5;
+    p.A = x; p.Wt = w; p.Y = y; p.stat_partials = stat_partials;
     p.M = d->N * d->Ho * d->Wo; p.Ha = d->Ho; p.Wa = d->Wo; p.Hin = d->H; p.Win = d->W;
     p.C = d->C; p.Nout = d->K; p.Th = d->R; p.Tw = d->S;
     p.dh0 = -d->pad; p.dw0 = -d->pad; p.dstep = 1;
@@ -2188,12 +2138,50 @@ extern "C" int32_t sgx_conv2d_fwd_dual(const sgx_conv_desc* d, const float* x, c
     p.a_bytes = view_bytes(d->N, d->H, d->W, d->C, d->x_ld_pix, d->x_ld_img);
     p.w_bytes = (long)d->K * p.w_ld_n * 4;
     p.act = SGX_ACT_NONE; p.accumulate = 0;
+    return p;
+}
+// ... and about the 1x1 branch of a two-output forward (it reads the centre tap of the same input)
+static IgemmParams fwd_dual_params(const sgx_conv_desc* d, const float* x, const float* w, const float* w1, const float* bias1, float* y, float* u,
+                                   float* stat5) {
+    IgemmParams p = fwd_params(d, x, w, y, stat5);
     p.A2 = x; p.Wt2 = w1; p.bias2 = bias1; p.Y2 = u;
     p.Hin2 = d->H; p.Win2 = d->W; p.Th2 = 1; p.Tw2 = 1; p.dh02 = 0; p.dw02 = 0; p.dstep2 = 1;
     p.a2_ld_pix = d->x_ld_pix; p.a2_ld_img = d->x_ld_img; p.w2_ld_n = d->C; p.a2_bytes = p.a_bytes; p.w2_bytes = (long)d->K * d->C * 4;
-    TileCfg t = ph2_tile(p.M, p.Nout);
-    p.stat_nblk = sgx_cdiv(p.M, t.bm);
-    return run_igemm(p, t.bm, t.bn, stream, 2);
+    return p;
+}
+
+extern "C" int32_t sgx_conv2d_fwd_stat_blocks(const sgx_conv_desc* d) {
+    TuneScope tune(0, d);
+    return plan_igemm(fwd_params(d, nullptr, nullptr, nullptr, nullptr), 0, true, true).mt;
+}
+
+extern "C" int32_t sgx_conv2d_fwd(const sgx_conv_desc* d, const float* x, const float* w, const float* bias,
+                                  const float* addend, float* y, int32_t act, float* stat_partials, void* stream) {
+    int32_t rc = check_desc(d);
+    if (rc) return rc;
+    SGX_CHECK_ARG(x && w && y, "conv fwd: null pointer");
+    TuneScope tune(0, d);
+    IgemmParams p = fwd_params(d, x, w, y, stat_partials);
+    p.bias = bias; p.addend = addend; p.act = act;
+    return launch(plan_launch(p, 0), p, stream);
+}
+
+// y = conv RxS(x, w) (no bias), u = conv1x1(x, w1) + bias1 with the same stride, as ONE launch: the 1x1 filter reads exactly the centre
+// tap of the RxS one (pad = R / 2), so the workgroup that owns an output tile walks the taps of w into one accumulator and then the
+// centre tap again with w1 into a second one.  stat5: [5][sgx_conv2d_fwd_dual_stat_blocks(d)][K] = sum y, y^2, u0, u0^2, y*u0 per row block (u0 = u - bias1).
+extern "C" int32_t sgx_conv2d_fwd_dual_stat_blocks(const sgx_conv_desc* d) {
+    return plan_igemm(fwd_dual_params(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), 2, true, true).mt;
+}
+extern "C" int32_t sgx_conv2d_fwd_dual(const sgx_conv_desc* d, const float* x, const float* w, const float* w1, const float* bias1, float* y,
+                                       float* u, float* stat5, void* stream) {
+    int32_t rc = check_desc(d);
+    if (rc) return rc;
+    SGX_CHECK_ARG(x && w && w1 && y && u && stat5, "conv fwd_dual: null pointer");
+    SGX_CHECK_ARG(d->R == d->S && (d->R & 1) && d->pad == d->R / 2, "conv fwd_dual: odd square filter with pad = R / 2 (the 1x1 branch reads its centre tap)");
+    SGX_CHECK_ARG(((uintptr_t)u % 16) == 0, "conv fwd_dual: needs a 16-byte aligned second output");
+    SGX_CHECK_ARG(d->C >= IG_BK || d->K <= 64, "conv fwd_dual: C < 16 (the flattened K axis) has the 64-filter tiles only (K = %d)", d->K);
+    IgemmParams p = fwd_dual_params(d, x, w, w1, bias1, y, u, stat5);
+    return launch(plan_launch(p, 2), p, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2240,9 +2228,62 @@ extern "C" int64_t sgx_conv2d_bwd_data_workspace(const sgx_conv_desc* d) {
     return (int64_t)d->R * d->S * d->C * d->K * sizeof(float) + 256;
 }
 
-// mode 0: transpose the weights into ws, then run; mode 1: only transpose (dy/dx unused); mode 2: ws already holds the transposed
-// weights of sgx_conv2d_transpose_weights (the host mirror prepares them on a side stream during the forward pass)
-struct DgradSecond {  // the 1x1 branch of a QARepVGG block: dx += dgrad1x1(ds) inside the same launch
+// One GEMM per OUTPUT-PARITY CLASS (ph, pw) of dx - the pixels (a * stride + ph, b * stride + pw), which see the same filter taps.
+// dgrad_classes lists them once; the weight transposes, the transpose-job recorder, the row count and the launches walk that list.
+struct DgradClass {
+    int T;          // filter taps that reach the class (0: none, e.g. 1x1 stride 2 - dx there is the addends alone)
+    TapList taps;   // their indices in the R x S filter, tap-row major (Th x Tw)
+    long wt_off;    // where the class's transposed weights [C][T][K] start in the workspace (floats)
+    IgemmParams p;  // Th, Tw, Ha, Wa, dh0, dw0 and whatever else the descriptor decides; operands and requests are the launch's to fill
+};
+#define SGX_MAX_DGRAD_CLASSES 64  // stride <= 8
+static int32_t dgrad_classes(const sgx_conv_desc* d, DgradClass* cls, int* ncls) {
+    int32_t rc = check_desc(d);
+    if (rc) return rc;
+    SGX_CHECK_ARG(d->K % 4 == 0 && d->y_ld_pix % 4 == 0, "conv bwd_data: K and dy pixel stride must be multiples of 4");
+    const int s = d->stride;
+    if (s > 8) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv bwd_data: stride %d (at most 8: %d output-parity classes)", s, SGX_MAX_DGRAD_CLASSES);
+    int n = 0;
+    long wt_off = 0;
+    for (int ph = 0; ph < s; ++ph)
+        for (int pw = 0; pw < s; ++pw) {
+            const int Ha = (d->H - ph + s - 1) / s, Wa = (d->W - pw + s - 1) / s;
+            if (Ha <= 0 || Wa <= 0) continue;
+            DgradClass& c = cls[n++];
+            // taps of this output-parity class: filter rows r with (ph + pad - r) % s == 0, in increasing r; the input (dY)
+            // row they read is (ph + pad - r)/s, i.e. it DEcreases by one per tap: dstep = -1
+            memset(&c.taps, 0, sizeof(c.taps));
+            int rows[SGX_MAX_TAPS], cols[SGX_MAX_TAPS], Th = 0, Tw = 0;
+            for (int r = 0; r < d->R; ++r)
+                if ((((ph + d->pad - r) % s) + s) % s == 0) rows[Th++] = r;
+            for (int q = 0; q < d->S; ++q)
+                if ((((pw + d->pad - q) % s) + s) % s == 0) cols[Tw++] = q;
+            const int T = Th * Tw;
+            for (int i = 0; i < Th; ++i)
+                for (int j = 0; j < Tw; ++j) c.taps.idx[i * Tw + j] = (unsigned char)(rows[i] * d->S + cols[j]);
+            c.T = T;
+            c.wt_off = wt_off;
+            wt_off += (long)d->C * T * d->K;
+            IgemmParams& p = c.p;
+            memset(&p, 0, sizeof(p));
+            p.M = d->N * Ha * Wa; p.Ha = Ha; p.Wa = Wa; p.Hin = d->Ho; p.Win = d->Wo;
+            p.C = d->K; p.Nout = d->C; p.Th = Th; p.Tw = Tw;
+            // floor division: (ph + pad - r) is a multiple of s for the selected taps
+            p.dh0 = T ? (ph + d->pad - rows[0]) / s : 0;
+            p.dw0 = T ? (pw + d->pad - cols[0]) / s : 0;
+            p.dstep = -1;
+            p.si = 1; p.so = s; p.ph = ph; p.pw = pw; p.Hout = d->H; p.Wout = d->W;
+            p.a_ld_pix = d->y_ld_pix; p.a_ld_img = d->y_ld_img; p.y_ld_pix = d->x_ld_pix; p.y_ld_img = d->x_ld_img;
+            p.w_ld_n = (long)T * d->K;
+            p.a_bytes = view_bytes(d->N, d->Ho, d->Wo, d->K, d->y_ld_pix, d->y_ld_img);
+            p.w_bytes = (long)d->C * p.w_ld_n * 4;
+            p.act = SGX_ACT_NONE;
+        }
+    *ncls = n;
+    return SGX_OK;
+}
+// the 1x1 branch of a QARepVGG block: dx += dgrad1x1(ds) inside the same launch.  It reaches parity class (0, 0) only.
+struct DgradSecond {
     const float* ds;
     long ld_pix, ld_img;
     const float* w1t;  // [C][K]
@@ -2251,19 +2292,35 @@ struct DgradSecond {  // the 1x1 branch of a QARepVGG block: dx += dgrad1x1(ds) 
     float a2_scale;
     const float* a2_scale_dev;
 };
-static int32_t conv_bwd_data_impl(const sgx_conv_desc* d, const float* dy, const float* w, const float* bias, const float* addend,
-                                  float* dx, int32_t accumulate, void* ws, int64_t ws_bytes, void* stream, int mode, const DgradSecond* sec = nullptr,
-                                  const sgx_bn_reduce_req* reqs = nullptr, int nreq = 0, int* rows_out = nullptr);
-extern "C" int32_t sgx_conv2d_bwd_data(const sgx_conv_desc* d, const float* dy, const float* w, const float* addend,
-                                       float* dx, int32_t accumulate, void* ws, int64_t ws_bytes, void* stream) {
-    return conv_bwd_data_impl(d, dy, w, nullptr, addend, dx, accumulate, ws, ws_bytes, stream, 0);
+// sec == NULL: what the descriptor alone decides (enough for the plan)
+static void dgrad_second(IgemmParams& p, const sgx_conv_desc* d, const DgradSecond* sec) {
+    p.Hin2 = d->Ho; p.Win2 = d->Wo; p.Th2 = 1; p.Tw2 = 1; p.dh02 = 0; p.dw02 = 0; p.dstep2 = 1;
+    p.w2_ld_n = d->K;
+    p.w2_bytes = (long)d->C * d->K * 4;
+    if (!sec) return;
+    p.A2 = sec->ds; p.Wt2 = sec->w1t;
+    p.a2_ld_pix = sec->ld_pix; p.a2_ld_img = sec->ld_img;
+    p.a2_bytes = view_bytes(d->N, d->Ho, d->Wo, d->K, sec->ld_pix, sec->ld_img);
+    p.addend2 = sec->addend2; p.a2d_ld_pix = sec->a2_ld_pix; p.a2d_ld_img = sec->a2_ld_img;
+    p.addend2_scale = sec->a2_scale; p.addend2_scale_dev = sec->a2_scale_dev;
 }
+
+// wt: the weights of every class, transposed, back to back (sgx_conv2d_bwd_data_workspace(d) bytes)
 extern "C" int32_t sgx_conv2d_transpose_weights(const sgx_conv_desc* d, const float* w, float* wt, int64_t wt_bytes, void* stream) {
-    return conv_bwd_data_impl(d, nullptr, w, nullptr, nullptr, nullptr, 0, wt, wt_bytes, stream, 1);
-}
-extern "C" int32_t sgx_conv2d_bwd_data_wt(const sgx_conv_desc* d, const float* dy, const float* wt, const float* addend, float* dx,
-                                          int32_t accumulate, void* stream) {
-    return conv_bwd_data_impl(d, dy, nullptr, nullptr, addend, dx, accumulate, const_cast<float*>(wt), sgx_conv2d_bwd_data_workspace(d), stream, 2);
+    DgradClass cls[SGX_MAX_DGRAD_CLASSES];
+    int n = 0;
+    int32_t rc = dgrad_classes(d, cls, &n);
+    if (rc) return rc;
+    SGX_CHECK_ARG(w, "conv bwd_data: null pointer");
+    if (wt_bytes < sgx_conv2d_bwd_data_workspace(d) || !wt) SGX_FAIL(SGX_ERR_WORKSPACE, "conv bwd_data: workspace too small");
+    for (int i = 0; i < n; ++i) {
+        if (!cls[i].T) continue;
+        const long e = (long)d->C * cls[i].T * d->K;
+        const int grid = (int)((e + 255) / 256 > 2048 ? 2048 : (e + 255) / 256);
+        SGX_LAUNCH(wtrans_kernel, dim3(grid), dim3(256), 0, stream, w, wt + cls[i].wt_off, d->K, d->C, d->R * d->S, cls[i].T, cls[i].taps);
+        SGX_CHECK_LAUNCH("wtrans");
+    }
+    return SGX_OK;
 }
 // batched form of wtrans_kernel: blockIdx.y = job, blockIdx.x strides over the job's elements
 __global__ void wtrans_batch_kernel(const sgx_wtrans_job* jobs) {
@@ -2306,37 +2363,123 @@ extern "C" int32_t sgx_qarep_prep_batch(const sgx_qarep_prep_job* jobs_dev, int3
     SGX_CHECK_LAUNCH("qarep_prep_batch");
     return SGX_OK;
 }
-// mode 3 of conv_bwd_data_impl records the transposes instead of launching them
-struct WtransRecorder {
-    sgx_wtrans_job* jobs;
-    int max, n;
-};
-static thread_local WtransRecorder* g_wt_rec = nullptr;
+// the transposes of sgx_conv2d_transpose_weights as jobs of one sgx_wtrans_batch launch
 extern "C" int32_t sgx_conv2d_transpose_jobs(const sgx_conv_desc* d, const float* w, float* wt, int64_t wt_bytes, sgx_wtrans_job* jobs,
                                              int32_t max_jobs, int32_t* njobs) {
     SGX_CHECK_ARG(jobs && njobs && max_jobs > 0, "transpose_jobs: null pointer");
-    WtransRecorder rec{jobs, max_jobs, 0};
-    g_wt_rec = &rec;
-    int32_t rc = conv_bwd_data_impl(d, nullptr, w, nullptr, nullptr, nullptr, 0, wt, wt_bytes, nullptr, 1);
-    g_wt_rec = nullptr;
+    DgradClass cls[SGX_MAX_DGRAD_CLASSES];
+    int n = 0;
+    int32_t rc = dgrad_classes(d, cls, &n);
     if (rc) return rc;
-    if (rec.n > max_jobs) SGX_FAIL(SGX_ERR_BAD_ARG, "transpose_jobs: %d jobs, room for %d", rec.n, max_jobs);
-    *njobs = rec.n;
+    SGX_CHECK_ARG(w, "conv bwd_data: null pointer");
+    if (wt_bytes < sgx_conv2d_bwd_data_workspace(d) || !wt) SGX_FAIL(SGX_ERR_WORKSPACE, "conv bwd_data: workspace too small");
+    int nj = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!cls[i].T) continue;
+        if (nj < max_jobs) {
+            sgx_wtrans_job& j = jobs[nj];
+            memset(&j, 0, sizeof(j));
+            j.w = w; j.wt = wt + cls[i].wt_off; j.K = d->K; j.C = d->C; j.RS = d->R * d->S; j.T = cls[i].T;
+            memcpy(j.taps, cls[i].taps.idx, sizeof(cls[i].taps.idx) < sizeof(j.taps) ? sizeof(cls[i].taps.idx) : sizeof(j.taps));
+        }
+        ++nj;
+    }
+    if (nj > max_jobs) SGX_FAIL(SGX_ERR_BAD_ARG, "transpose_jobs: %d jobs, room for %d", nj, max_jobs);
+    *njobs = nj;
     return SGX_OK;
+}
+
+// Rows a data gradient with BatchNorm-reduce requests writes: one per pixel tile of every class's launch.  0 = cannot carry requests: a class
+// no filter tap reaches still defines dx there (zeros / the addends) and no launch forms its g; unaligned / flat launches have no request epilogue.
+extern "C" int32_t sgx_conv2d_bwd_data_stat_blocks(const sgx_conv_desc* d, int32_t two_source) {
+    DgradClass cls[SGX_MAX_DGRAD_CLASSES];
+    int n = 0, rows = 0;
+    if (dgrad_classes(d, cls, &n)) return 0;
+    TuneScope tune(1, d);
+    for (int i = 0; i < n; ++i) {
+        if (!cls[i].T) return 0;
+        const int ph2 = two_source && cls[i].p.ph == 0 && cls[i].p.pw == 0;
+        if (ph2) dgrad_second(cls[i].p, d, nullptr);
+        const ConvPlan pl = plan_igemm(cls[i].p, ph2, true, false);
+        if (pl.err || !pl.req_ok) return 0;
+        rows += pl.mt;
+    }
+    return rows;
+}
+
+// wt as sgx_conv2d_transpose_weights left it.  Every class is planned with its real operands BEFORE anything is launched: a problem that
+// cannot run, or cannot carry its requests in exactly the rows they were allocated for, is refused without having written anything.
+static int32_t dgrad_launch(const sgx_conv_desc* d, const float* dy, const float* wt, const float* bias, const float* addend, float* dx,
+                            int32_t accumulate, const DgradSecond* sec, const sgx_bn_reduce_req* reqs, int nreq, void* stream) {
+    DgradClass cls[SGX_MAX_DGRAD_CLASSES];
+    ConvPlan plans[SGX_MAX_DGRAD_CLASSES];
+    int n = 0, rows = 0;
+    int32_t rc = dgrad_classes(d, cls, &n);
+    if (rc) return rc;
+    SGX_CHECK_ARG(dy && dx, "conv bwd_data: null pointer");
+    if (!wt) SGX_FAIL(SGX_ERR_WORKSPACE, "conv bwd_data: workspace too small");
+    SGX_CHECK_ARG(nreq >= 0 && nreq <= SGX_MAX_BN_REQ && (nreq == 0 || reqs), "conv bwd_data: bad BatchNorm-reduce requests");
+    for (int r = 0; r < nreq; ++r)
+        SGX_CHECK_ARG(reqs[r].t && reqs[r].scale && reqs[r].shift && reqs[r].mean && reqs[r].partials && reqs[r].c_lo >= 0 && reqs[r].c_hi <= d->C &&
+                          reqs[r].c_lo < reqs[r].c_hi && reqs[r].c_lo % 4 == 0 && reqs[r].c_hi % 4 == 0 && reqs[r].t_ld_pix % 4 == 0 &&
+                          reqs[r].t_ld_img % 4 == 0 && ((uintptr_t)reqs[r].t % 16) == 0 && ((uintptr_t)reqs[r].scale % 16) == 0 &&
+                          ((uintptr_t)reqs[r].shift % 16) == 0 && ((uintptr_t)reqs[r].mean % 16) == 0,
+                      "conv bwd_data: BatchNorm-reduce request %d: null pointer, unaligned operand or a channel range outside [0, C)", r);
+    TuneScope tune(1, d);
+    for (int i = 0; i < n; ++i) {
+        IgemmParams& p = cls[i].p;
+        p.A = dy; p.Wt = wt + cls[i].wt_off; p.bias = bias; p.addend = addend; p.Y = dx; p.accumulate = accumulate;
+        const int ph2 = sec && p.ph == 0 && p.pw == 0;
+        if (ph2) dgrad_second(p, d, sec);
+        if (cls[i].T) {
+            plans[i] = plan_launch(p, ph2);
+            if (plans[i].err) SGX_FAIL(plans[i].err, "%s", plans[i].msg);
+        }
+        if (!nreq) continue;
+        if (!cls[i].T || !plans[i].req_ok)
+            SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv bwd_data: this problem cannot carry BatchNorm-reduce requests (sgx_conv2d_bwd_data_stat_blocks = 0)");
+        p.nreq = nreq;
+        p.req_row0 = rows;
+        rows += plans[i].mt;
+        for (int r = 0; r < nreq; ++r) {
+            p.req[r].t = reqs[r].t; p.req[r].scale = reqs[r].scale; p.req[r].shift = reqs[r].shift; p.req[r].mean = reqs[r].mean;
+            p.req[r].parts = reqs[r].partials; p.req[r].t_ld_pix = reqs[r].t_ld_pix; p.req[r].t_ld_img = reqs[r].t_ld_img;
+            p.req[r].c_lo = reqs[r].c_lo; p.req[r].c_hi = reqs[r].c_hi; p.req[r].act = reqs[r].act; p.req[r].rows = reqs[r].rows;
+        }
+    }
+    for (int r = 0; r < nreq; ++r)
+        SGX_CHECK_ARG(reqs[r].rows == rows, "conv bwd_data: request %d was allocated for %d rows, the launch writes %d (sgx_conv2d_bwd_data_stat_blocks)", r, reqs[r].rows, rows);
+    for (int i = 0; i < n; ++i) {
+        IgemmParams& p = cls[i].p;
+        if (cls[i].T) {
+            rc = launch(plans[i], p, stream);
+            if (rc) return rc;
+        } else if (!(accumulate && !addend && !bias)) {  // no filter tap reaches this parity class: nothing to add when accumulating
+            const long e = (long)p.M * (p.Nout / 4);
+            const int grid = (int)((e + 255) / 256 > 4096 ? 4096 : (e + 255) / 256);
+            SGX_LAUNCH(dgrad_fill_kernel, dim3(grid), dim3(256), 0, stream, p);
+            SGX_CHECK_LAUNCH("dgrad_fill");
+        }
+    }
+    return SGX_OK;
+}
+extern "C" int32_t sgx_conv2d_bwd_data(const sgx_conv_desc* d, const float* dy, const float* w, const float* addend,
+                                       float* dx, int32_t accumulate, void* ws, int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(dy && dx, "conv bwd_data: null pointer");
+    int32_t rc = sgx_conv2d_transpose_weights(d, w, (float*)ws, ws_bytes, stream);
+    return rc ? rc : dgrad_launch(d, dy, (const float*)ws, nullptr, addend, dx, accumulate, nullptr, nullptr, 0, stream);
+}
+extern "C" int32_t sgx_conv2d_bwd_data_wt(const sgx_conv_desc* d, const float* dy, const float* wt, const float* addend, float* dx,
+                                          int32_t accumulate, void* stream) {
+    return dgrad_launch(d, dy, wt, nullptr, addend, dx, accumulate, nullptr, nullptr, 0, stream);
+}
+extern "C" int32_t sgx_conv2d_bwd_data_wt_req(const sgx_conv_desc* d, const float* dy, const float* wt, const float* addend, float* dx,
+                                              int32_t accumulate, const sgx_bn_reduce_req* reqs, int32_t nreq, void* stream) {
+    return dgrad_launch(d, dy, wt, nullptr, addend, dx, accumulate, nullptr, reqs, nreq, stream);
 }
 // dx = conv_transpose RxS(dy, w) + conv_transpose 1x1(ds, w1) [+ addend] [+ dx] as ONE launch per output-parity class: the data gradient of
 // a QARepVGG block's two convolution branches (same stride; the 1x1 branch reaches parity class (0, 0) only).  wt: the RxS weights as
 // sgx_conv2d_transpose_weights lays them out; w1t: the 1x1 weights transposed, [C][K].
-extern "C" int32_t sgx_conv2d_bwd_data_dual(const sgx_conv_desc* d, const float* dy, const float* wt, const float* ds, int64_t ds_ld_pix,
-                                            int64_t ds_ld_img, const float* w1t, const float* addend, const float* addend2, int64_t a2_ld_pix,
-                                            int64_t a2_ld_img, float a2_scale, const float* a2_scale_dev, float* dx, int32_t accumulate,
-                                            void* stream) {
-    SGX_CHECK_ARG(ds && w1t && d && d->K >= IG_BK && ds_ld_pix % 4 == 0, "conv bwd_data_dual: bad args (needs K >= 16)");
-    SGX_CHECK_ARG(!addend2 || (d->stride == 1 && a2_ld_pix % 4 == 0 && a2_ld_img % 4 == 0 && ((uintptr_t)addend2 % 16) == 0),
-                  "conv bwd_data_dual: the scaled second addend needs stride 1 and 16-byte aligned rows");
-    DgradSecond sec{ds, (long)ds_ld_pix, (long)ds_ld_img, w1t, addend2, (long)a2_ld_pix, (long)a2_ld_img, a2_scale, a2_scale_dev};
-    return conv_bwd_data_impl(d, dy, nullptr, nullptr, addend, dx, accumulate, const_cast<float*>(wt), sgx_conv2d_bwd_data_workspace(d), stream, 2, &sec);
-}
 extern "C" int32_t sgx_conv2d_bwd_data_dual_req(const sgx_conv_desc* d, const float* dy, const float* wt, const float* ds, int64_t ds_ld_pix,
                                                 int64_t ds_ld_img, const float* w1t, const float* addend, const float* addend2, int64_t a2_ld_pix,
                                                 int64_t a2_ld_img, float a2_scale, const float* a2_scale_dev, float* dx, int32_t accumulate,
@@ -2345,161 +2488,14 @@ extern "C" int32_t sgx_conv2d_bwd_data_dual_req(const sgx_conv_desc* d, const fl
     SGX_CHECK_ARG(!addend2 || (d->stride == 1 && a2_ld_pix % 4 == 0 && a2_ld_img % 4 == 0 && ((uintptr_t)addend2 % 16) == 0),
                   "conv bwd_data_dual: the scaled second addend needs stride 1 and 16-byte aligned rows");
     DgradSecond sec{ds, (long)ds_ld_pix, (long)ds_ld_img, w1t, addend2, (long)a2_ld_pix, (long)a2_ld_img, a2_scale, a2_scale_dev};
-    return conv_bwd_data_impl(d, dy, nullptr, nullptr, addend, dx, accumulate, const_cast<float*>(wt), sgx_conv2d_bwd_data_workspace(d), stream, 2, &sec, reqs, nreq);
+    return dgrad_launch(d, dy, wt, nullptr, addend, dx, accumulate, &sec, reqs, nreq, stream);
 }
-// mode 3: no launch - counts the statistic rows a launch with requests would write (*rows_out; 0 = cannot carry requests)
-static int32_t conv_bwd_data_impl(const sgx_conv_desc* d, const float* dy, const float* w, const float* bias, const float* addend,
-                                  float* dx, int32_t accumulate, void* ws, int64_t ws_bytes, void* stream, int mode, const DgradSecond* sec,
-                                  const sgx_bn_reduce_req* reqs, int nreq, int* rows_out) {
-    int32_t rc = check_desc(d);
-    if (rc) return rc;
-    const bool dry = mode == 3;
-    SGX_CHECK_ARG(dry || ((mode == 1 || (dy && dx)) && (mode == 2 || w)), "conv bwd_data: null pointer");
-    TuneScope tune(1, d);
-    SGX_CHECK_ARG(d->K % 4 == 0 && d->y_ld_pix % 4 == 0, "conv bwd_data: K and dy pixel stride must be multiples of 4");
-    if (!dry && (ws_bytes < sgx_conv2d_bwd_data_workspace(d) || !ws)) SGX_FAIL(SGX_ERR_WORKSPACE, "conv bwd_data: workspace too small");
-    SGX_CHECK_ARG(nreq >= 0 && nreq <= SGX_MAX_BN_REQ && (nreq == 0 || (reqs && mode == 2)), "conv bwd_data: bad BatchNorm-reduce requests");
-    for (int r = 0; r < nreq; ++r)
-        SGX_CHECK_ARG(reqs[r].t && reqs[r].scale && reqs[r].shift && reqs[r].mean && reqs[r].partials && reqs[r].c_lo >= 0 && reqs[r].c_hi <= d->C &&
-                          reqs[r].c_lo < reqs[r].c_hi && reqs[r].c_lo % 4 == 0 && reqs[r].c_hi % 4 == 0 && reqs[r].t_ld_pix % 4 == 0 &&
-                          reqs[r].t_ld_img % 4 == 0 && ((uintptr_t)reqs[r].t % 16) == 0 && ((uintptr_t)reqs[r].scale % 16) == 0 &&
-                          ((uintptr_t)reqs[r].shift % 16) == 0 && ((uintptr_t)reqs[r].mean % 16) == 0,
-                      "conv bwd_data: BatchNorm-reduce request %d: null pointer, unaligned operand or a channel range outside [0, C)", r);
-    if (nreq) {  // the rows the launches below will write, before anything is launched
-        int rows = 0;
-        rc = conv_bwd_data_impl(d, nullptr, nullptr, nullptr, nullptr, sec ? reinterpret_cast<float*>(16) : nullptr, 0, nullptr, 0, nullptr, 3, nullptr, nullptr, 0, &rows);
-        if (rc) return rc;
-        if (rows <= 0) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv bwd_data: this problem cannot carry BatchNorm-reduce requests (sgx_conv2d_bwd_data_stat_blocks = 0)");
-        for (int r = 0; r < nreq; ++r)
-            SGX_CHECK_ARG(reqs[r].rows == rows, "conv bwd_data: request %d was allocated for %d rows, the launch writes %d (sgx_conv2d_bwd_data_stat_blocks)", r, reqs[r].rows, rows);
-    }
-    int rows_total = 0;
-    bool rows_ok = true;  // every parity class can carry requests
-    const int s = d->stride;
-    float* wt = (float*)ws;
-    for (int ph = 0; ph < s; ++ph)
-        for (int pw = 0; pw < s; ++pw) {
-            IgemmParams p;
-            memset(&p, 0, sizeof(p));
-            // taps of this output-parity class: filter rows r with (ph + pad - r) % s == 0, in increasing r; the input (dY)
-            // row they read is (ph + pad - r)/s, i.e. it DEcreases by one per tap: dstep = -1
-            TapList taps;
-            memset(&taps, 0, sizeof(taps));
-            int rows[SGX_MAX_TAPS], cols[SGX_MAX_TAPS], Th = 0, Tw = 0;
-            for (int r = 0; r < d->R; ++r)
-                if ((((ph + d->pad - r) % s) + s) % s == 0) rows[Th++] = r;
-            for (int q = 0; q < d->S; ++q)
-                if ((((pw + d->pad - q) % s) + s) % s == 0) cols[Tw++] = q;
-            const int T = Th * Tw;
-            for (int i = 0; i < Th; ++i)
-                for (int j = 0; j < Tw; ++j) taps.idx[i * Tw + j] = (unsigned char)(rows[i] * d->S + cols[j]);
-            const int Ha = (d->H - ph + s - 1) / s, Wa = (d->W - pw + s - 1) / s;
-            if (Ha <= 0 || Wa <= 0) continue;
-            p.A = dy; p.Wt = wt; p.bias = bias; p.addend = addend; p.Y = dx; p.stat_partials = nullptr;
-            p.M = d->N * Ha * Wa; p.Ha = Ha; p.Wa = Wa; p.Hin = d->Ho; p.Win = d->Wo;
-            p.C = d->K; p.Nout = d->C; p.Th = Th; p.Tw = Tw;
-            // floor division: (ph + pad - r) is a multiple of s for the selected taps
-            p.dh0 = T ? (ph + d->pad - rows[0]) / s : 0;
-            p.dw0 = T ? (pw + d->pad - cols[0]) / s : 0;
-            p.dstep = -1;
-            p.si = 1; p.so = s; p.ph = ph; p.pw = pw; p.Hout = d->H; p.Wout = d->W;
-            p.a_ld_pix = d->y_ld_pix; p.a_ld_img = d->y_ld_img; p.y_ld_pix = d->x_ld_pix; p.y_ld_img = d->x_ld_img;
-            p.w_ld_n = (long)T * d->K;
-            p.a_bytes = view_bytes(d->N, d->Ho, d->Wo, d->K, d->y_ld_pix, d->y_ld_img);
-            p.w_bytes = (long)d->C * p.w_ld_n * 4;
-            p.act = SGX_ACT_NONE; p.accumulate = accumulate;
-            if (T == 0) {
-                if (mode == 1) continue;
-                if (dry || nreq) {  // a class no filter tap reaches still defines dx there (zeros / the addends): its g is not formed by any launch
-                    rows_ok = false;
-                    if (nreq) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv bwd_data: BatchNorm-reduce requests need a filter that reaches every output-parity class");
-                    continue;
-                }
-                // no filter tap reaches this parity class (e.g. 1x1 stride 2): nothing to add when accumulating
-                if (accumulate && !addend && !bias) continue;
-                long n = (long)p.M * (p.Nout / 4);
-                int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-                SGX_LAUNCH(dgrad_fill_kernel, dim3(grid), dim3(256), 0, stream, p);
-                SGX_CHECK_LAUNCH("dgrad_fill");
-                continue;
-            }
-            if (dry || nreq) {
-                // the rows of this class: one per pixel tile of the launch, decided exactly as run_igemm decides below
-                IgemmParams q = p;
-                q.vec = (q.Nout % 4 == 0 && q.y_ld_pix % 4 == 0 && q.y_ld_img % 4 == 0) ? 1 : 0;
-                // the launch itself (run_igemm) also looks at the operands' addresses: a real call decides with them BEFORE anything is
-                // launched, so a launch that cannot carry the requests is refused here and never writes partial rows
-                if (!dry && (((uintptr_t)p.Y % 16) || ((uintptr_t)p.addend % 16) || ((uintptr_t)p.bias % 16))) q.vec = 0;
-                const int ph2 = (sec || (dry && dx != nullptr)) && ph == 0 && pw == 0 ? 1 : 0;  // (dry: dx != nullptr marks the two-source form)
-                if (ph2) {
-                    q.A2 = q.A ? q.A : reinterpret_cast<const float*>(16);
-                    q.Th2 = q.Tw2 = 1; q.dh02 = q.dw02 = 0; q.dstep2 = 1;
-                }
-                const bool flat = q.C < IG_BK && T > 1;
-                int mt;
-                if (!q.vec || flat || (ph2 && q.C < IG_BK)) rows_ok = false, mt = 0;
-                else if (pconv_ok(q, ph2)) mt = pconv_tiles(q.M / (q.Ha * q.Wa), q.Ha, q.Wa);
-                else if (ph2) mt = sgx_cdiv(q.M, ph2_tile(q.M, q.Nout).bm);
-                else mt = sgx_cdiv(q.M, pick_tile(q.M, q.Nout, conv_math_for(q.Th * q.Tw, q.C)).bm);
-                if (nreq) {
-                    if (!rows_ok) SGX_FAIL(SGX_ERR_UNSUPPORTED, "conv bwd_data: this problem cannot carry BatchNorm-reduce requests (sgx_conv2d_bwd_data_stat_blocks = 0)");
-                    p.nreq = nreq;
-                    p.req_row0 = rows_total;
-                    for (int r = 0; r < nreq; ++r) {
-                        p.req[r].t = reqs[r].t; p.req[r].scale = reqs[r].scale; p.req[r].shift = reqs[r].shift; p.req[r].mean = reqs[r].mean;
-                        p.req[r].parts = reqs[r].partials; p.req[r].t_ld_pix = reqs[r].t_ld_pix; p.req[r].t_ld_img = reqs[r].t_ld_img;
-                        p.req[r].c_lo = reqs[r].c_lo; p.req[r].c_hi = reqs[r].c_hi; p.req[r].act = reqs[r].act; p.req[r].rows = reqs[r].rows;
-                    }
-                }
-                rows_total += mt;
-                if (dry) continue;
-            }
-            if (mode == 1 && g_wt_rec) {
-                if (g_wt_rec->n < g_wt_rec->max) {
-                    sgx_wtrans_job& j = g_wt_rec->jobs[g_wt_rec->n];
-                    memset(&j, 0, sizeof(j));
-                    j.w = w; j.wt = wt; j.K = d->K; j.C = d->C; j.RS = d->R * d->S; j.T = T;
-                    memcpy(j.taps, taps.idx, sizeof(taps.idx) < sizeof(j.taps) ? sizeof(taps.idx) : sizeof(j.taps));
-                }
-                ++g_wt_rec->n;
-            } else if (mode != 2) {
-                long n = (long)d->C * T * d->K;
-                int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-                SGX_LAUNCH(wtrans_kernel, dim3(grid), dim3(256), 0, stream, w, wt, d->K, d->C, d->R * d->S, T, taps);
-                SGX_CHECK_LAUNCH("wtrans");
-            }
-            if (mode != 1 && sec && ph == 0 && pw == 0) {
-                p.A2 = sec->ds; p.Wt2 = sec->w1t;
-                p.Hin2 = d->Ho; p.Win2 = d->Wo; p.Th2 = 1; p.Tw2 = 1; p.dh02 = 0; p.dw02 = 0; p.dstep2 = 1;
-                p.a2_ld_pix = sec->ld_pix; p.a2_ld_img = sec->ld_img; p.w2_ld_n = d->K;
-                p.a2_bytes = view_bytes(d->N, d->Ho, d->Wo, d->K, sec->ld_pix, sec->ld_img);
-                p.w2_bytes = (long)d->C * d->K * 4;
-                p.addend2 = sec->addend2; p.a2d_ld_pix = sec->a2_ld_pix; p.a2d_ld_img = sec->a2_ld_img;
-                p.addend2_scale = sec->a2_scale; p.addend2_scale_dev = sec->a2_scale_dev;
-                TileCfg t = ph2_tile(p.M, p.Nout);
-                rc = run_igemm(p, t.bm, t.bn, stream, 1);
-                if (rc) return rc;
-            } else if (mode != 1) {
-                TileCfg t = igemm_tile(p);
-                TileCfg m = pick_tile(p.M, p.Nout, conv_math_for(p.Th * p.Tw, p.C));
-                rc = run_igemm(p, m.bm, t.bn, stream);
-                if (rc) return rc;
-            }
-            if (nreq && p.req_row0 + p.mt != rows_total) SGX_FAIL(SGX_ERR_HIP, "conv bwd_data: internal - statistic rows %d + %d != %d", p.req_row0, p.mt, rows_total);
-            wt += (long)d->C * T * d->K;
-        }
-    if (rows_out) *rows_out = rows_ok ? rows_total : 0;
-    return SGX_OK;
-}
-extern "C" int32_t sgx_conv2d_bwd_data_stat_blocks(const sgx_conv_desc* d, int32_t two_source) {
-    int rows = 0;
-    // (dry run: the non-null dx pointer only marks the two-source form, nothing is dereferenced)
-    if (conv_bwd_data_impl(d, nullptr, nullptr, nullptr, nullptr, two_source ? reinterpret_cast<float*>(16) : nullptr, 0, nullptr, 0, nullptr, 3, nullptr, nullptr, 0, &rows)) return 0;
-    return rows;
-}
-extern "C" int32_t sgx_conv2d_bwd_data_wt_req(const sgx_conv_desc* d, const float* dy, const float* wt, const float* addend, float* dx,
-                                              int32_t accumulate, const sgx_bn_reduce_req* reqs, int32_t nreq, void* stream) {
-    return conv_bwd_data_impl(d, dy, nullptr, nullptr, addend, dx, accumulate, const_cast<float*>(wt), sgx_conv2d_bwd_data_workspace(d), stream, 2, nullptr, reqs, nreq);
+extern "C" int32_t sgx_conv2d_bwd_data_dual(const sgx_conv_desc* d, const float* dy, const float* wt, const float* ds, int64_t ds_ld_pix,
+                                            int64_t ds_ld_img, const float* w1t, const float* addend, const float* addend2, int64_t a2_ld_pix,
+                                            int64_t a2_ld_img, float a2_scale, const float* a2_scale_dev, float* dx, int32_t accumulate,
+                                            void* stream) {
+    return sgx_conv2d_bwd_data_dual_req(d, dy, wt, ds, ds_ld_pix, ds_ld_img, w1t, addend, addend2, a2_ld_pix, a2_ld_img, a2_scale, a2_scale_dev, dx,
+                                        accumulate, nullptr, 0, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3287,7 +3283,9 @@ extern "C" int32_t sgx_convT2x2_fwd(int32_t N, int32_t H, int32_t W, int32_t C, 
                                     const float* wt, const float* bias, float* y, int64_t y_ld_pix, int64_t y_ld_img, void* ws,
                                     int64_t ws_bytes, void* stream) {
     sgx_conv_desc d = convT_adjoint_desc(N, H, W, C, K, x_ld_pix, x_ld_img, y_ld_pix, y_ld_img);
-    return conv_bwd_data_impl(&d, x, wt, bias, nullptr, y, 0, ws, ws_bytes, stream, 0);
+    SGX_CHECK_ARG(x && y, "conv bwd_data: null pointer");
+    int32_t rc = sgx_conv2d_transpose_weights(&d, wt, (float*)ws, ws_bytes, stream);
+    return rc ? rc : dgrad_launch(&d, x, (const float*)ws, bias, nullptr, y, 0, nullptr, nullptr, 0, stream);
 }
 // wtt: the filter as sgx_conv2d_transpose_weights leaves it for the adjoint convolution (K = C filters of K channels, 2x2, stride 2, no padding) -
 // the host mirror keeps it in the network's per-step transpose batch, so the four parity launches go out without a transpose launch each
@@ -3295,7 +3293,7 @@ extern "C" int32_t sgx_convT2x2_fwd_wt(int32_t N, int32_t H, int32_t W, int32_t 
                                        const float* wtt, const float* bias, float* y, int64_t y_ld_pix, int64_t y_ld_img, void* stream) {
     SGX_CHECK_ARG(wtt, "convT2x2_fwd_wt: null pointer");
     sgx_conv_desc d = convT_adjoint_desc(N, H, W, C, K, x_ld_pix, x_ld_img, y_ld_pix, y_ld_img);
-    return conv_bwd_data_impl(&d, x, nullptr, bias, nullptr, y, 0, const_cast<float*>(wtt), sgx_conv2d_bwd_data_workspace(&d), stream, 2);
+    return dgrad_launch(&d, x, wtt, bias, nullptr, y, 0, nullptr, nullptr, 0, stream);
 }
 extern "C" int32_t sgx_convT2x2_bwd_data(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, const float* dy, int64_t dy_ld_pix,
                                          int64_t dy_ld_img, const float* wt, float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, void* stream) {

@@ -2,7 +2,7 @@
 
     python tools/conv_tune.py [--model s] [--batch 32] [--size 640] [--out gpurun_out/conv_tune.txt]
 For every distinct problem recorded by tools/conv_bench.py's recorder: time the heuristic choice and every legal override,
-print the best and the gain.  Output feeds the tile heuristics in csrc/conv.hip (pick_tile_heuristic / wgrad_plan)."""
+print the best and the gain.  Output feeds the tile heuristics in csrc/conv.hip (pick_tile_heuristic behind plan_igemm / wgrad_tile)."""
 import argparse
 import os
 import sys
