@@ -662,6 +662,44 @@ int32_t sgx_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, 
 int32_t sgx_sgd_step(float* p, const float* g, float* mom, int64_t n, float lr, float momentum, float dampening,
                      int32_t nesterov, int32_t first_step, const int64_t* seg_end, const float* seg_wd, int32_t nseg,
                      void* stream);
+/* The reference's other registered optimizers (optimizer_utils.py:88-143 resolves SGD, Adam, AdamW, RMSprop, RMSpropTF, Lamb, Lion), same
+ * arena convention.  Hyper-parameters are doubles (Python's floats): derived constants (1 - beta, lr / bias correction) are formed in double
+ * and rounded once, as ATen rounds scalar arguments.  grad_scale (device scalar, may be NULL) multiplies every gradient (the data-parallel mean).
+ * Adam     : torch.optim.Adam, amsgrad=False (L2 weight decay added to the gradient, bias correction).
+ * RMSprop  : torch.optim.RMSprop, and with SGX_RMSPROP_TF the reference's RMSpropTF (training/utils/optimizers/rmsprop_tf.py:89-151: eps
+ *            inside the square root, avg += (1 - alpha)(g^2 - avg); the caller initialises square_avg to ones).  grad_avg is non-NULL exactly
+ *            with SGX_RMSPROP_CENTERED, momentum_buffer exactly with momentum > 0: a disabled buffer does not exist.
+ * Lion     : training/utils/optimizers/lion.py:45-79 (decay, sign step, momentum - in that order; the sign is taken of an uncontracted sum). */
+#define SGX_RMSPROP_CENTERED 1
+#define SGX_RMSPROP_TF 2
+#define SGX_RMSPROP_DECOUPLED_DECAY 4
+#define SGX_RMSPROP_LR_IN_MOMENTUM 8
+int32_t sgx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                      int32_t step, const int64_t* seg_end, const float* seg_wd, int32_t nseg, const float* grad_scale, void* stream);
+int32_t sgx_rmsprop_step(float* p, const float* g, float* square_avg, float* grad_avg, float* momentum_buffer, int64_t n, double lr,
+                         double alpha, double eps, double momentum, int32_t flags, const int64_t* seg_end, const float* seg_wd,
+                         int32_t nseg, const float* grad_scale, void* stream);
+int32_t sgx_lion_step(float* p, const float* g, float* m, int64_t n, double lr, double beta1, double beta2, const int64_t* seg_end,
+                      const float* seg_wd, int32_t nseg, const float* grad_scale, void* stream);
+/* Lamb (training/utils/optimizers/lamb.py:123-216) as three calls on one stream, no host synchronisation:
+ *   moments : the global gradient norm (a reduce pre-pass that leaves the clip factor as a device scalar in ws), then m, v from g / clip and
+ *             the per-slot sums of p^2 and u^2, u = (m/bc1) / (sqrt(v)/sqrt(bc2) + eps) + wd*p, as fp64 partials in ws.  g is NOT written
+ *             (the reference divides p.grad in place).  step = 0: no bias correction.
+ *   finalize: trust[slot] = (|p| > 0 && |u| > 0) ? |p| / |u| : 1 (min 1 with trust_clip) for slots with weight decay != 0 or always_adapt,
+ *             1 otherwise - partials folded in a fixed order in fp64, no atomics: bit-identical from run to run.
+ *   apply   : p -= lr * trust[slot] * u with u recomputed from (m, v, p).
+ * slot_end[nslot] (int64, ascending, device; the last slot extends to n) are the end offsets of the parameter tensors in the arena; ws is
+ * sgx_lamb_workspace bytes, 16-byte aligned, and must survive from moments to finalize.                                              */
+int64_t sgx_lamb_workspace(int64_t n, int32_t nslot);
+int32_t sgx_lamb_moments(const float* p, const float* g, float* m, float* v, int64_t n, double beta1, double beta2, double eps,
+                         int32_t step, int32_t grad_averaging, double max_grad_norm, const int64_t* seg_end, const float* seg_wd,
+                         int32_t nseg, const int64_t* slot_end, int32_t nslot, const float* grad_scale, void* ws, int64_t ws_bytes,
+                         void* stream);
+int32_t sgx_lamb_finalize(int64_t n, const int64_t* seg_end, const float* seg_wd, int32_t nseg, const int64_t* slot_end, int32_t nslot,
+                          int32_t trust_clip, int32_t always_adapt, const void* ws, int64_t ws_bytes, float* trust, void* stream);
+int32_t sgx_lamb_apply(float* p, const float* m, const float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                       int32_t step, const int64_t* seg_end, const float* seg_wd, int32_t nseg, const int64_t* slot_end, int32_t nslot,
+                       const float* trust, void* stream);
 int32_t sgx_ema_update(float* ema, const float* p, int64_t n, float decay, void* stream);
 int32_t sgx_fill(float* p, int64_t n, float v, void* stream);
 

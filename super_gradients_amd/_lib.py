@@ -77,7 +77,7 @@ class MatchDesc(ctypes.Structure):
 
 
 _P = c_void_p
-_i32, _i64, _f = c_int32, c_int64, c_float
+_i32, _i64, _f, _d = c_int32, c_int64, c_float, ctypes.c_double
 _CD, _LD, _ND = POINTER(ConvDesc), POINTER(LossDesc), POINTER(NmsDesc)
 
 # name -> (restype, argtypes); mirrors include/sgx_hip.h one to one
@@ -201,6 +201,13 @@ PROTOTYPES = {
     "sgx_softmax_ce_fwd_bwd": (_i32, [_i32, _i32, _P, _P, _f, _P, _i32, _i32, _P, _P, _P]),
     "sgx_adamw_step": (_i32, [_P, _P, _P, _P, _i64, _f, _f, _f, _f, _i32, _P, _P, _i32, _P, _P]),
     "sgx_sgd_step": (_i32, [_P, _P, _P, _i64, _f, _f, _f, _i32, _i32, _P, _P, _i32, _P]),
+    "sgx_adam_step": (_i32, [_P, _P, _P, _P, _i64, _d, _d, _d, _d, _i32, _P, _P, _i32, _P, _P]),
+    "sgx_rmsprop_step": (_i32, [_P, _P, _P, _P, _P, _i64, _d, _d, _d, _d, _i32, _P, _P, _i32, _P, _P]),
+    "sgx_lion_step": (_i32, [_P, _P, _P, _i64, _d, _d, _d, _P, _P, _i32, _P, _P]),
+    "sgx_lamb_workspace": (_i64, [_i64, _i32]),
+    "sgx_lamb_moments": (_i32, [_P, _P, _P, _P, _i64, _d, _d, _d, _i32, _i32, _d, _P, _P, _i32, _P, _i32, _P, _P, _i64, _P]),
+    "sgx_lamb_finalize": (_i32, [_i64, _P, _P, _i32, _P, _i32, _i32, _i32, _P, _i64, _P, _P]),
+    "sgx_lamb_apply": (_i32, [_P, _P, _P, _i64, _d, _d, _d, _d, _i32, _P, _P, _i32, _P, _i32, _P, _P]),
     "sgx_ema_update": (_i32, [_P, _P, _i64, _f, _P]),
     "sgx_fill": (_i32, [_P, _i64, _f, _P]),
 }

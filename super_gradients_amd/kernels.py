@@ -1215,6 +1215,51 @@ def sgd_step(p, g, mom, lr, momentum, dampening, nesterov, first_step, seg_end, 
     weights_written()
 
 
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, seg_end, seg_wd, grad_scale=None):
+    check(lib().sgx_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, ptr(seg_end), ptr(seg_wd), seg_end.numel(),
+                              ptr(grad_scale), stream()), "sgx_adam_step")
+    weights_written()
+
+
+RMSPROP_CENTERED, RMSPROP_TF, RMSPROP_DECOUPLED_DECAY, RMSPROP_LR_IN_MOMENTUM = 1, 2, 4, 8  # include/sgx_hip.h SGX_RMSPROP_*
+
+
+def rmsprop_step(p, g, square_avg, grad_avg, momentum_buffer, lr, alpha, eps, momentum, seg_end, seg_wd, tf=False, decoupled_decay=False,
+                 lr_in_momentum=False, grad_scale=None):
+    """torch.optim.RMSprop, or with tf=True the reference's RMSpropTF.  grad_avg is None unless centered, momentum_buffer None unless momentum > 0."""
+    flags = (RMSPROP_CENTERED if grad_avg is not None else 0) | (RMSPROP_TF if tf else 0) | (RMSPROP_DECOUPLED_DECAY if decoupled_decay else 0) | (
+        RMSPROP_LR_IN_MOMENTUM if lr_in_momentum else 0)
+    check(lib().sgx_rmsprop_step(ptr(p), ptr(g), ptr(square_avg), ptr(grad_avg), ptr(momentum_buffer), p.numel(), lr, alpha, eps, momentum, flags,
+                                 ptr(seg_end), ptr(seg_wd), seg_end.numel(), ptr(grad_scale), stream()), "sgx_rmsprop_step")
+    weights_written()
+
+
+def lion_step(p, g, m, lr, beta1, beta2, seg_end, seg_wd, grad_scale=None):
+    check(lib().sgx_lion_step(ptr(p), ptr(g), ptr(m), p.numel(), lr, beta1, beta2, ptr(seg_end), ptr(seg_wd), seg_end.numel(), ptr(grad_scale), stream()),
+          "sgx_lion_step")
+    weights_written()
+
+
+def lamb_workspace(n: int, nslot: int, device) -> torch.Tensor:
+    """The caller-owned partial-sum workspace of lamb_step for an arena of n elements in nslot tensors."""
+    return torch.empty(int(lib().sgx_lamb_workspace(n, nslot)), dtype=torch.uint8, device=device)
+
+
+def lamb_step(p, g, m, v, lr, beta1, beta2, eps, step, seg_end, seg_wd, slot_end, ws, trust, grad_averaging=True, max_grad_norm=1.0, trust_clip=False,
+              always_adapt=False, grad_scale=None):
+    """One Lamb step: moments + per-slot norms, trust ratios (left in `trust`, one float per slot), apply - three calls on the current stream, no
+    host synchronisation.  The gradient arena is NOT written: the reference divides p.grad by the clip factor in place, and the Trainer zeroes
+    the arena right after the step, so nothing observes the difference.  step = 0: bias_correction=False."""
+    n, ns, nseg = p.numel(), slot_end.numel(), seg_end.numel()
+    check(lib().sgx_lamb_moments(ptr(p), ptr(g), ptr(m), ptr(v), n, beta1, beta2, eps, step, int(grad_averaging), max_grad_norm, ptr(seg_end), ptr(seg_wd), nseg,
+                                 ptr(slot_end), ns, ptr(grad_scale), ptr(ws), ws.numel(), stream()), "sgx_lamb_moments")
+    check(lib().sgx_lamb_finalize(n, ptr(seg_end), ptr(seg_wd), nseg, ptr(slot_end), ns, int(trust_clip), int(always_adapt), ptr(ws), ws.numel(), ptr(trust),
+                                  stream()), "sgx_lamb_finalize")
+    check(lib().sgx_lamb_apply(ptr(p), ptr(m), ptr(v), n, lr, beta1, beta2, eps, step, ptr(seg_end), ptr(seg_wd), nseg, ptr(slot_end), ns, ptr(trust), stream()),
+          "sgx_lamb_apply")
+    weights_written()
+
+
 def ema_update(ema, p, decay):
     check(lib().sgx_ema_update(ptr(ema), ptr(p), ema.numel(), float(decay), stream()), "sgx_ema_update")
     weights_written()

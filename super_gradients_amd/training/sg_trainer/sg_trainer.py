@@ -82,6 +82,12 @@ class AverageMeter:
         return tuple((self.sum / max(self.n, 1)).tolist())
 
 
+def _optimizer_state_names(o):
+    """The arena-sized state buffers a checkpoint carries: what the optimizer class declares (`state_names`; an entry may be None when its
+    option is off).  An optimizer object that declares nothing is asked for the three names checkpoints have always carried."""
+    return getattr(o, "state_names", None) or ("exp_avg", "exp_avg_sq", "momentum_buffer")
+
+
 def _update_metric(m, outputs, targets, inputs, extras):
     """Classification metrics take (preds, target); detection metrics also need the image batch (for H, W) and optional crowd targets
     (metrics/detection_metrics.py:166-200)."""
@@ -340,7 +346,7 @@ class Trainer:
                 handler.on_train_batch_gradient_step_start(context)
                 if tp.clip_grad_norm:
                     self._clip_grad_norm(float(tp.clip_grad_norm), world)
-                if self.reducer is not None and world > 1 and hasattr(self.optimizer, "exp_avg"):
+                if self.reducer is not None and world > 1 and getattr(self.optimizer, "takes_grad_scale", False):
                     self.optimizer.step(grad_scale=self.reducer.grad_scale)
                 elif self.reducer is not None and world > 1:
                     self.net.g_arena.buf.mul_(1.0 / world)
@@ -474,8 +480,8 @@ class Trainer:
     def _optimizer_state(self):
         o = self.optimizer
         st = {"param_groups": [{k: v for k, v in g.items() if k != "params"} for g in o.param_groups], "steps": getattr(o, "_steps", 0)}
-        for name in ("exp_avg", "exp_avg_sq", "momentum_buffer"):
-            if hasattr(o, name):
+        for name in _optimizer_state_names(o):
+            if getattr(o, name, None) is not None:
                 st[name] = getattr(o, name).detach().cpu().clone()
         return st
 
@@ -494,8 +500,8 @@ class Trainer:
             self.ema_model.b_ema.copy_(self.net.b_arena.buf)
         if load_opt and "optimizer_state_dict" in ckpt:
             st = ckpt["optimizer_state_dict"]
-            for name in ("exp_avg", "exp_avg_sq", "momentum_buffer"):
-                if name in st and hasattr(self.optimizer, name):
+            for name in _optimizer_state_names(self.optimizer):
+                if name in st and getattr(self.optimizer, name, None) is not None:
                     getattr(self.optimizer, name).copy_(st[name])
             self.optimizer._steps = plain_number(st, "steps", int, 0)
             for g, s in zip(self.optimizer.param_groups, st["param_groups"]):
