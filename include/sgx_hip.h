@@ -437,6 +437,24 @@ int32_t sgx_dual_affine_act_bwd(const float* dy, int64_t dy_ld, const float* x1,
 int32_t sgx_dual_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
                                        const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2, const float* mean2,
                                        float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials4, void* stream);
+/* RepVGGBlock with the identity-BatchNorm branch (the RepVGG classifiers' blocks with in == out, stride 1; modules/repvgg_block.py:94-103:
+ * act(bn3(conv3x3 x) + alpha * bn1(conv1x1 x) + bn_id(x))) as ONE sweep:
+ *   y = act(s1[c]*x1 + t1[c] [+ s2[c]*x2 + t2[c]] [+ s3[c]*x3 + t3[c]]) [+ r_scale * r_scale_dev[0] * r]     x2 / x3 / r may be NULL.
+ * partials (may be NULL): [2][nblk][C] per-channel sum / sum of squares of the value STORED in y - the rows sgx_bn_finalize /
+ * sgx_bn_reduce_sums consume; the next block's identity BatchNorm normalises exactly that tensor, so no statistics pass over it runs.
+ * nblk: row blocks of the sweep, 0 = sgx_stats_blocks(M); y does not depend on it.  x3 NULL: sgx_dual_affine_act_fwd's y bit for bit. */
+int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const float* s1, const float* t1, const float* x2, int64_t x2_ld,
+                               const float* s2, const float* t2, const float* x3, int64_t x3_ld, const float* s3, const float* t3,
+                               const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev, float* y, int64_t y_ld, int64_t M,
+                               int32_t C, int32_t act, float* partials, int32_t nblk, void* stream);
+/* its backward through the activation and the reduce rows of ALL THREE BatchNorm backward passes in one sweep:
+ *   g = dy * act'(pre-activation, recomputed),   partials = [6][nblk][C] = sum g, sum g (x1 - mean1), sum g, sum g (x2 - mean2), sum g,
+ *   sum g (x3 - mean3): rows 2i, 2i+1 are what sgx_bn_bwd_reduce(g, x_i) would produce (act = none).  x3 NULL: [4][nblk][C],
+ * sgx_dual_affine_act_bwd_reduce's g and rows bit for bit.  nblk as above.                                                        */
+int32_t sgx_tri_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
+                                      const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2, const float* mean2,
+                                      const float* x3, int64_t x3_ld, const float* s3, const float* t3, const float* mean3, float* g,
+                                      int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials, int32_t nblk, void* stream);
 /* per-channel column sum: out[c] (+)= sum_rows x[row][c]  (conv bias gradients).                     */
 /* rows_per_img/ld_img: rows are grouped in images of rows_per_img rows, image i starts at x + i*ld_img
  * (pass rows_per_img = M, ld_img = 0 for a plain [M,C] matrix).  ws: sgx_colsum_workspace(M, C) bytes.  */

@@ -1049,6 +1049,126 @@ extern "C" int32_t sgx_dual_affine_act_bwd_reduce(const float* dy, int64_t dy_ld
     return SGX_OK;
 }
 
+// RepVGG three-branch block (the classifiers' blocks with in == out, stride 1: modules/repvgg_block.py:94-103 of the reference):
+//   y = act(s1*x1 + t1 [+ s2*x2 + t2] [+ s3*x3 + t3]) [+ r_scale * r]      x3 = the block's own input (identity BatchNorm branch)
+// in ONE sweep, which on request also leaves the per-channel sum y, sum y^2 partial rows of the value it STORES ([2][nblk][C], the layout
+// of sgx_affine_act_fwd's): the next block's identity BatchNorm normalises exactly this tensor, so no statistics pass over it runs.
+// The first two branches are DualAffineF's arithmetic, statement for statement: a null third branch gives its result bit for bit.
+// nblk: the number of row blocks (0: sgx_stats_blocks(M)) - the stored values do not depend on it, the partial rows' count does.
+static SweepGeom sweep_geom_rows(long M, int C, int nblk) {
+    SweepGeom g = sweep_geom(M, C);
+    if (nblk > 0) {
+        g.nblk = nblk;
+        g.rows_per_blk = (int)((M + g.nblk - 1) / g.nblk);
+    }
+    return g;
+}
+struct TriAffineF {
+    DualAffineF p; const float* x3; long x3_ld; const float* s3; const float* t3;
+    struct In { float4 a, b, e, u; };
+    struct Cst { DualAffineF::Cst k; float4 s, t; };
+    __device__ In load(long row, int c) const {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        In in;
+        in.a = sgx_ld4(p.x1 + row * p.x1_ld + c);
+        in.b = p.x2 ? sgx_ld4(p.x2 + row * p.x2_ld + c) : z;
+        in.e = x3 ? sgx_ld4(x3 + row * x3_ld + c) : z;
+        in.u = p.r ? sgx_ld4(p.r + row * p.r_ld + c) : z;
+        return in;
+    }
+    __device__ Cst consts(int c) const {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        return Cst{p.consts(c), x3 ? sgx_ld4(s3 + c) : z, x3 ? sgx_ld4(t3 + c) : z};
+    }
+    __device__ float4 pre(const Cst& k, const float4& a, const float4& b, const float4& e) const {
+        float4 v = p.pre(k.k, a, b);
+        if (x3) {
+            const float4 s = k.s, t = k.t;
+            v.x += s.x * e.x + t.x; v.y += s.y * e.y + t.y; v.z += s.z * e.z + t.z; v.w += s.w * e.w + t.w;
+        }
+        return v;
+    }
+    __device__ void apply(long row, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
+        float4 v = pre(k, in.a, in.b, in.e);
+        float4 o = make_float4(sgx_act(v.x, p.act), sgx_act(v.y, p.act), sgx_act(v.z, p.act), sgx_act(v.w, p.act));
+        if (p.r) {
+            const float sc = k.k.sc;
+            o.x += sc * in.u.x; o.y += sc * in.u.y; o.z += sc * in.u.z; o.w += sc * in.u.w;
+        }
+        sgx_st4(p.y + row * p.y_ld + c, o);
+        q0.x += o.x; q0.y += o.y; q0.z += o.z; q0.w += o.w;
+        q1.x += o.x * o.x; q1.y += o.y * o.y; q1.z += o.z * o.z; q1.w += o.w * o.w;
+    }
+};
+extern "C" int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const float* s1, const float* t1, const float* x2, int64_t x2_ld,
+                                          const float* s2, const float* t2, const float* x3, int64_t x3_ld, const float* s3, const float* t3,
+                                          const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev, float* y, int64_t y_ld, int64_t M,
+                                          int32_t C, int32_t act, float* partials, int32_t nblk, void* stream) {
+    SGX_CHECK_ARG(x1 && s1 && t1 && y, "tri_affine_act_fwd: null pointer");
+    SGX_CHECK_ARG(!x2 || (s2 && t2), "tri_affine_act_fwd: second branch needs scale and shift");
+    SGX_CHECK_ARG(!x3 || (s3 && t3), "tri_affine_act_fwd: third branch needs scale and shift");
+    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "tri_affine_act_fwd: need M>0 and C%%4==0 (C=%d)", C);
+    SGX_CHECK_ARG(nblk >= 0 && nblk <= M, "tri_affine_act_fwd: row blocks %d outside 0..M", nblk);
+    TriAffineF f{DualAffineF{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, r, r_ld, y, y_ld, act, r_scale, r_scale_dev}, x3, x3_ld, s3, t3};
+    SweepGeom g = sweep_geom_rows(M, C, nblk);
+    SGX_LAUNCH((sweep_kernel<TriAffineF, 2>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, f, g, partials);
+    SGX_CHECK_LAUNCH("tri_affine_act_fwd");
+    return SGX_OK;
+}
+
+// Its backward through the activation AND the reduce rows of all three BatchNorm backward passes in one sweep:
+//   g = dy * act'(pre)   (written),   partials [6][nblk][C] = sum g, sum g (x1 - mean1), sum g, sum g (x2 - mean2), sum g, sum g (x3 - mean3)
+// - three [2][nblk][C] row sets as sgx_bn_bwd_reduce(g, x_i) (act = none) leaves them, bit for bit: the sums take the g values that are STORED,
+// so the product dy * act' is rounded before it is added (no contraction there: an fma would add the unrounded product, which is not the
+// stored g as soon as act' is not 0 or 1).  x3 NULL: DualAffineBwdReduceF itself runs - partials [4][nblk][C],
+// sgx_dual_affine_act_bwd_reduce's result bit for bit.
+struct TriAffineBwdReduceF {
+    TriAffineF p; const float* dy; long dy_ld; float* g; long g_ld; const float* mean1; const float* mean2; const float* mean3;
+    struct In { float4 a, b, e, d; };
+    struct Cst { TriAffineF::Cst k; float4 m1, m2, m3; };
+    __device__ In load(long row, int c) const {
+        return In{sgx_ld4(p.p.x1 + row * p.p.x1_ld + c), sgx_ld4(p.p.x2 + row * p.p.x2_ld + c), sgx_ld4(p.x3 + row * p.x3_ld + c),
+                  sgx_ld4(dy + row * dy_ld + c)};
+    }
+    __device__ Cst consts(int c) const { return Cst{p.consts(c), sgx_ld4(mean1 + c), sgx_ld4(mean2 + c), sgx_ld4(mean3 + c)}; }
+    __device__ float4 grad(const float4& d, const float4& v) const {
+#pragma clang fp contract(off)
+        return make_float4(d.x * sgx_act_grad(v.x, p.p.act), d.y * sgx_act_grad(v.y, p.p.act), d.z * sgx_act_grad(v.z, p.p.act),
+                           d.w * sgx_act_grad(v.w, p.p.act));
+    }
+    __device__ void apply(long row, int c, const In& in, const Cst& k, float4 (&q)[6]) const {
+        const float4 o = grad(in.d, p.pre(k.k, in.a, in.b, in.e));
+        sgx_st4(g + row * g_ld + c, o);
+        q[0].x += o.x; q[0].y += o.y; q[0].z += o.z; q[0].w += o.w;
+        q[1].x += o.x * (in.a.x - k.m1.x); q[1].y += o.y * (in.a.y - k.m1.y); q[1].z += o.z * (in.a.z - k.m1.z); q[1].w += o.w * (in.a.w - k.m1.w);
+        q[2].x += o.x; q[2].y += o.y; q[2].z += o.z; q[2].w += o.w;
+        q[3].x += o.x * (in.b.x - k.m2.x); q[3].y += o.y * (in.b.y - k.m2.y); q[3].z += o.z * (in.b.z - k.m2.z); q[3].w += o.w * (in.b.w - k.m2.w);
+        q[4].x += o.x; q[4].y += o.y; q[4].z += o.z; q[4].w += o.w;
+        q[5].x += o.x * (in.e.x - k.m3.x); q[5].y += o.y * (in.e.y - k.m3.y); q[5].z += o.z * (in.e.z - k.m3.z); q[5].w += o.w * (in.e.w - k.m3.w);
+    }
+};
+extern "C" int32_t sgx_tri_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
+                                                 const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2,
+                                                 const float* mean2, const float* x3, int64_t x3_ld, const float* s3, const float* t3,
+                                                 const float* mean3, float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials,
+                                                 int32_t nblk, void* stream) {
+    SGX_CHECK_ARG(dy && x1 && s1 && t1 && mean1 && x2 && s2 && t2 && mean2 && g && partials, "tri_affine_act_bwd_reduce: null pointer");
+    SGX_CHECK_ARG(!x3 || (s3 && t3 && mean3), "tri_affine_act_bwd_reduce: third branch needs scale, shift and mean");
+    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "tri_affine_act_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
+    SGX_CHECK_ARG(nblk >= 0 && nblk <= M, "tri_affine_act_bwd_reduce: row blocks %d outside 0..M", nblk);
+    const DualAffineF two{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, nullptr, 0, nullptr, 0, act, 1.f, nullptr};
+    SweepGeom gm = sweep_geom_rows(M, C, nblk);
+    if (x3) {
+        TriAffineBwdReduceF f{TriAffineF{two, x3, x3_ld, s3, t3}, dy, dy_ld, g, g_ld, mean1, mean2, mean3};
+        SGX_LAUNCH((sweepq_kernel<TriAffineBwdReduceF, 6>), dim3(gm.nblk, gm.ctiles), dim3(SW_THREADS), 0, stream, f, gm, partials);
+    } else {
+        DualAffineBwdReduceF f{two, dy, dy_ld, g, g_ld, mean1, mean2};
+        SGX_LAUNCH((sweepq_kernel<DualAffineBwdReduceF, 4>), dim3(gm.nblk, gm.ctiles), dim3(SW_THREADS), 0, stream, f, gm, partials);
+    }
+    SGX_CHECK_LAUNCH("tri_affine_act_bwd_reduce");
+    return SGX_OK;
+}
+
 struct ColsumF {
     const float* x; long ld; long rows_per_img; long ld_img;
     struct In { float4 v; };
