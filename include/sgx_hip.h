@@ -37,6 +37,8 @@ extern "C" {
 #define SGX_ACT_NONE 0
 #define SGX_ACT_RELU 1
 #define SGX_ACT_SILU 2
+#define SGX_ACT_RELU6 3 /* min(max(v, 0), 6), derivative 1 on 0 < v < 6 (nn.ReLU6): sgx_affine_act_fwd, sgx_bn_bwd_reduce / _apply and the depthwise
+                         * convolution implement it; every other entry point that takes an activation rejects it (SGX_ERR_BAD_ARG) */
 
 int32_t sgx_version(void);
 const char* sgx_last_error(void);
@@ -479,6 +481,28 @@ int32_t sgx_avgpool_fwd(int32_t N, int32_t HW, int32_t C, const float* x, int64_
                         float* y, void* stream);
 int32_t sgx_avgpool_bwd(int32_t N, int32_t HW, int32_t C, const float* dy, float* dx, int64_t dx_ld_pix,
                         int64_t dx_ld_img, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution, pad 1, stride 1 or 2: nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False) of
+ *   training/models/classification_models/mobilenetv2.py:73,87 (InvertedResidual's "dw" layer) and its backward.
+ * d: an sgx_conv_desc with K == C, R == S == 3, pad == 1, stride in {1, 2} (anything else: SGX_ERR_BAD_ARG); strides as everywhere.
+ * Filter storage [3][3][C] (tap-major, channels contiguous): the logical [C,1,3,3] tensor of the reference's state_dict as a strided view.
+ * Per-channel stencils - memory-bound, no matrix pipe.  Deterministic: no atomics, every reduction folds partial rows in a fixed order.
+ * ------------------------------------------------------------------------------------------- */
+/* y = act(dwconv(x, w) + bias[c]); bias may be NULL; act: any SGX_ACT_* including RELU6.  stat_partials (may be NULL; then bias must be
+ * NULL and act NONE): [2][sgx_dwconv3x3_stat_blocks(d)][C] per-workgroup sum / sum of squares of y - the rows sgx_bn_finalize and
+ * sgx_bn_reduce_sums consume, in sgx_conv2d_fwd's format.                                                                        */
+int32_t sgx_dwconv3x3_stat_blocks(const sgx_conv_desc* d);
+int32_t sgx_dwconv3x3_fwd(const sgx_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int32_t act,
+                          float* stat_partials, void* stream);
+/* dx (+)= the data gradient; d describes the FORWARD problem, dy has the y strides, dx the x strides.  Gather form: every dx element sums
+ * the taps whose output position exists (stride 2: the taps of matching parity only).                                          */
+int32_t sgx_dwconv3x3_bwd_data(const sgx_conv_desc* d, const float* dy, const float* w, float* dx, int32_t accumulate, void* stream);
+/* dw[3][3][C] += sum over pixels of dy * x (accumulates, like sgx_conv2d_bwd_weight).  Two launches: per-workgroup partial rows in ws
+ * (sgx_dwconv3x3_bwd_weight_workspace(d) bytes, 16-byte aligned), then an fp64 fold in a fixed order: the same bits on every call. */
+int64_t sgx_dwconv3x3_bwd_weight_workspace(const sgx_conv_desc* d);
+int32_t sgx_dwconv3x3_bwd_weight(const sgx_conv_desc* d, const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Squeeze-excitation gates and nearest up-sampling of PP-YOLOE:

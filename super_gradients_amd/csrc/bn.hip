@@ -435,7 +435,7 @@ struct AffineActF {
         }
         q0.x += v.x; q0.y += v.y; q0.z += v.z; q0.w += v.w;
         q1.x += v.x * v.x; q1.y += v.y * v.y; q1.z += v.z * v.z; q1.w += v.w * v.w;
-        float4 o = make_float4(sgx_act(v.x, act), sgx_act(v.y, act), sgx_act(v.z, act), sgx_act(v.w, act));
+        float4 o = make_float4(sgx_act6(v.x, act), sgx_act6(v.y, act), sgx_act6(v.z, act), sgx_act6(v.w, act));
         sgx_st4(y + r * y_ld + c, o);
     }
 };
@@ -443,6 +443,7 @@ extern "C" int32_t sgx_affine_act_fwd(const float* x, int64_t x_ld, const float*
                                       int64_t r1_ld, float a1, const float* a1_dev, const float* r2, int64_t r2_ld, float a2, float* y,
                                       int64_t y_ld, int64_t M, int32_t C, int32_t act, float* partials, void* stream) {
     SGX_CHECK_ARG(x && y, "affine_act: null pointer");
+    SGX_CHECK_ACT4(act, "affine_act");
     SGX_CHECK_ARG((scale == nullptr) == (shift == nullptr), "affine_act: scale and shift go together");
     AffineActF f{x, x_ld, scale, shift, r1, r1_ld, a1, a1_dev, r2, r2_ld, a2, y, y_ld, act};
     return run_sweep<AffineActF, 2>(f, M, C, partials, stream, "affine_act");
@@ -450,7 +451,7 @@ extern "C" int32_t sgx_affine_act_fwd(const float* x, int64_t x_ld, const float*
 
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float bn_masked(float dy, float x, float s, float t, int act) {
-    return act == SGX_ACT_NONE ? dy : dy * sgx_act_grad(s * x + t, act);
+    return act == SGX_ACT_NONE ? dy : dy * sgx_act6_grad(s * x + t, act);
 }
 struct BnBwdReduceF {
     const float* dy; long dy_ld; const float* x; long x_ld; const float* scale; const float* shift; const float* mean; int act;
@@ -471,6 +472,7 @@ struct BnBwdReduceF {
 extern "C" int32_t sgx_bn_bwd_reduce(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
                                      const float* save_mean, int64_t M, int32_t C, int32_t act, float* partials, void* stream) {
     SGX_CHECK_ARG(dy && x && scale && shift && save_mean && partials, "bn_bwd_reduce: null pointer");
+    SGX_CHECK_ACT4(act, "bn_bwd_reduce");
     BnBwdReduceF f{dy, dy_ld, x, x_ld, scale, shift, save_mean, act};
     return run_sweep<BnBwdReduceF, 2>(f, M, C, partials, stream, "bn_bwd_reduce");
 }
@@ -553,6 +555,7 @@ extern "C" int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float*
                                     const float* coef, float* dx, int64_t dx_ld, float* g_out, int64_t g_ld, int64_t M, int32_t C,
                                     int32_t act, void* stream) {
     SGX_CHECK_ARG(dy && x && scale && shift && coef && dx, "bn_bwd_apply: null pointer");
+    SGX_CHECK_ACT4(act, "bn_bwd_apply");
     BnBwdApplyF f{dy, dy_ld, x, x_ld, scale, shift, coef, C, dx, dx_ld, g_out, g_ld, act};
     return run_sweep<BnBwdApplyF, 0>(f, M, C, nullptr, stream, "bn_bwd_apply");
 }
@@ -747,6 +750,7 @@ extern "C" int32_t sgx_dual_affine_act_fwd(const float* x1, int64_t x1_ld, const
                                            const float* s2, const float* t2, const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev,
                                            float* y, int64_t y_ld, int64_t M, int32_t C, int32_t act, void* stream) {
     SGX_CHECK_ARG(x1 && s1 && t1 && y, "dual_affine_act_fwd: null pointer");
+    SGX_CHECK_ACT3(act, "dual_affine_act_fwd");
     SGX_CHECK_ARG(!x2 || (s2 && t2), "dual_affine_act_fwd: second branch needs scale and shift");
     DualAffineF f{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, r, r_ld, y, y_ld, act, r_scale, r_scale_dev};
     return run_sweep<DualAffineF, 0>(f, M, C, nullptr, stream, "dual_affine_act_fwd");
@@ -774,6 +778,7 @@ extern "C" int32_t sgx_dual_affine_act_bwd(const float* dy, int64_t dy_ld, const
                                            const float* x2, int64_t x2_ld, const float* s2, const float* t2, float* g, int64_t g_ld, int64_t M,
                                            int32_t C, int32_t act, void* stream) {
     SGX_CHECK_ARG(dy && x1 && s1 && t1 && g, "dual_affine_act_bwd: null pointer");
+    SGX_CHECK_ACT3(act, "dual_affine_act_bwd");
     SGX_CHECK_ARG(!x2 || (s2 && t2), "dual_affine_act_bwd: second branch needs scale and shift");
     DualAffineBwdF f{DualAffineF{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, nullptr, 0, nullptr, 0, act, 1.f, nullptr}, dy, dy_ld, g, g_ld};
     return run_sweep<DualAffineBwdF, 0>(f, M, C, nullptr, stream, "dual_affine_act_bwd");
@@ -933,6 +938,7 @@ struct QarepBwdReduceF {
 extern "C" int32_t sgx_qarep_bwd_reduce(const float* dout, int64_t d_ld, const float* y, int64_t y_ld, const float* u, int64_t u_ld, const float* cf,
                                         const float* sv, int64_t M, int32_t C, int32_t act, float* partials4, void* stream) {
     SGX_CHECK_ARG(dout && y && u && cf && sv && partials4, "qarep_bwd_reduce: null pointer");
+    SGX_CHECK_ACT3(act, "qarep_bwd_reduce");
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "qarep_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
     QarepBwdReduceF f{QarepBwdBase{dout, d_ld, y, y_ld, u, u_ld, cf, sv, C, act}};
     SweepGeom g = sweep_geom(M, C);
@@ -1004,6 +1010,7 @@ extern "C" int32_t sgx_qarep_bwd_apply(const float* dout, int64_t d_ld, const fl
                                        const float* sv, const float* cb, float* ds, int64_t ds_ld, float* dy, int64_t dy_ld, int64_t M, int32_t C,
                                        int32_t act, void* stream) {
     SGX_CHECK_ARG(dout && y && u && cf && sv && cb && ds && dy, "qarep_bwd_apply: null pointer");
+    SGX_CHECK_ACT3(act, "qarep_bwd_apply");
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "qarep_bwd_apply: need M>0 and C%%4==0 (C=%d)", C);
     QarepBwdApplyF f{QarepBwdBase{dout, d_ld, y, y_ld, u, u_ld, cf, sv, C, act}, cb, ds, ds_ld, dy, dy_ld};
     SweepGeom g = sweep_geom(M, C);
@@ -1041,6 +1048,7 @@ extern "C" int32_t sgx_dual_affine_act_bwd_reduce(const float* dy, int64_t dy_ld
                                                   const float* mean2, float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials4,
                                                   void* stream) {
     SGX_CHECK_ARG(dy && x1 && s1 && t1 && mean1 && x2 && s2 && t2 && mean2 && g && partials4, "dual_affine_act_bwd_reduce: null pointer");
+    SGX_CHECK_ACT3(act, "dual_affine_act_bwd_reduce");
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "dual_affine_act_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
     DualAffineBwdReduceF f{DualAffineF{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, nullptr, 0, nullptr, 0, act, 1.f, nullptr}, dy, dy_ld, g, g_ld, mean1, mean2};
     SweepGeom gm = sweep_geom(M, C);
@@ -1105,6 +1113,7 @@ extern "C" int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const 
                                           const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev, float* y, int64_t y_ld, int64_t M,
                                           int32_t C, int32_t act, float* partials, int32_t nblk, void* stream) {
     SGX_CHECK_ARG(x1 && s1 && t1 && y, "tri_affine_act_fwd: null pointer");
+    SGX_CHECK_ACT3(act, "tri_affine_act_fwd");
     SGX_CHECK_ARG(!x2 || (s2 && t2), "tri_affine_act_fwd: second branch needs scale and shift");
     SGX_CHECK_ARG(!x3 || (s3 && t3), "tri_affine_act_fwd: third branch needs scale and shift");
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "tri_affine_act_fwd: need M>0 and C%%4==0 (C=%d)", C);
@@ -1153,6 +1162,7 @@ extern "C" int32_t sgx_tri_affine_act_bwd_reduce(const float* dy, int64_t dy_ld,
                                                  const float* mean3, float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials,
                                                  int32_t nblk, void* stream) {
     SGX_CHECK_ARG(dy && x1 && s1 && t1 && mean1 && x2 && s2 && t2 && mean2 && g && partials, "tri_affine_act_bwd_reduce: null pointer");
+    SGX_CHECK_ACT3(act, "tri_affine_act_bwd_reduce");
     SGX_CHECK_ARG(!x3 || (s3 && t3 && mean3), "tri_affine_act_bwd_reduce: third branch needs scale, shift and mean");
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "tri_affine_act_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
     SGX_CHECK_ARG(nblk >= 0 && nblk <= M, "tri_affine_act_bwd_reduce: row blocks %d outside 0..M", nblk);

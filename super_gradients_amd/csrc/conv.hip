@@ -2160,6 +2160,7 @@ extern "C" int32_t sgx_conv2d_fwd(const sgx_conv_desc* d, const float* x, const 
     int32_t rc = check_desc(d);
     if (rc) return rc;
     SGX_CHECK_ARG(x && w && y, "conv fwd: null pointer");
+    SGX_CHECK_ACT3(act, "conv fwd");
     TuneScope tune(0, d);
     IgemmParams p = fwd_params(d, x, w, y, stat_partials);
     p.bias = bias; p.addend = addend; p.act = act;
@@ -2425,6 +2426,7 @@ static int32_t dgrad_launch(const sgx_conv_desc* d, const float* dy, const float
                           reqs[r].t_ld_img % 4 == 0 && ((uintptr_t)reqs[r].t % 16) == 0 && ((uintptr_t)reqs[r].scale % 16) == 0 &&
                           ((uintptr_t)reqs[r].shift % 16) == 0 && ((uintptr_t)reqs[r].mean % 16) == 0,
                       "conv bwd_data: BatchNorm-reduce request %d: null pointer, unaligned operand or a channel range outside [0, C)", r);
+    for (int r = 0; r < nreq; ++r) SGX_CHECK_ACT3(reqs[r].act, "conv bwd_data: BatchNorm-reduce request");
     TuneScope tune(1, d);
     for (int i = 0; i < n; ++i) {
         IgemmParams& p = cls[i].p;

@@ -366,6 +366,7 @@ extern "C" int32_t sgx_hconv2d_fwd(const sgx_conv_desc* d, const void* x, const 
                                    const void* post_add, int64_t post_ld_pix, int64_t post_ld_img, float post_scale, const float* post_scale_dev,
                                    void* stream) {
     SGX_CHECK_ARG(d && x && w && y, "hconv2d_fwd: null pointer");
+    SGX_CHECK_ACT3(act, "hconv2d_fwd");
     SGX_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->K > 0 && d->R > 0 && d->S > 0 && d->stride >= 1 && d->pad >= 0, "hconv2d_fwd: bad dims");
     SGX_CHECK_ARG(d->Ho == (d->H + 2 * d->pad - d->R) / d->stride + 1 && d->Wo == (d->W + 2 * d->pad - d->S) / d->stride + 1, "hconv2d_fwd: Ho/Wo do not match (H+2p-R)/s+1");
     SGX_CHECK_ARG(d->x_ld_pix >= d->C && d->y_ld_pix >= d->K, "hconv2d_fwd: bad pixel strides");

@@ -1,5 +1,6 @@
 // Pooling kernels (HBM/L2-bound, no MFMA): SPP max-pool k=5/9/13 stride 1, ResNet 3x3 s2 max-pool,
 // global average pool.  One thread owns a float4 channel group of one output pixel.
+// Below them: the depthwise 3x3 convolution (forward, data gradient, weight gradient) - the other per-channel window kernels.
 // Reference call sites: include/sgx_hip.h (Pooling section).
 #include "sgx_common.h"
 #include <atomic>
@@ -337,5 +338,362 @@ extern "C" int32_t sgx_avgpool_bwd(int32_t N, int32_t HW, int32_t C, const float
     SGX_LAUNCH(avgpool_bwd_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, stream, N, HW, C, dy, dx, (long)dx_ld_pix,
                (long)dx_ld_img);
     SGX_CHECK_LAUNCH("avgpool_bwd");
+    return SGX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Depthwise 3x3 convolution, pad 1, stride 1 or 2 (MobileNetV2's nn.Conv2d(groups = channels)): per-channel stencils, no matrix work -
+// memory-bound like the pooling kernels above.  Filter [3][3][C]: a lane reads the nine taps of its four channels as nine 16-byte loads.
+//
+// One geometry serves the three kernels.  A workgroup is CG channel groups (16 bytes each) x PL "columns"; a column is one output pixel
+// column of a strip of TH output rows of one image.  Lane = (column, channel group), channel groups fastest: a wave reads whole contiguous
+// pixel rows.  A thread walks its strip downwards and keeps the three input rows of the window in registers, so an input element is loaded
+// by the threads of its (at most) three horizontal neighbours and once more per strip boundary - not nine times.  The rows the NEXT
+// output row needs are requested before the current one is computed and stored.
+// TH: eight rows, halved (down to two) until the launch has DW_MIN_THREADS threads - 7 x 7 x 960 at batch 64 runs 4 strips x 7 columns x
+// 240 groups x 64 images = 430 080 threads (26 waves per CU); 112 x 112 x 32 at batch 64 keeps TH = 8 and has 802 816 (49 waves per CU).
+// Every reduction (statistics rows, weight gradient) is per-workgroup partial rows folded in a fixed order: no atomics.
+#define DW_THREADS 256
+#define DW_MIN_THREADS 262144  // 256 CUs x 16 waves
+struct DwGeom {
+    int N, Hi, Wi, Ho, Wo, C, C4, CG, PL, TH, nstrips, ctiles;
+    long items;                                // columns: N x nstrips x Wo
+    long i_ld_pix, i_ld_img, o_ld_pix, o_ld_img;  // strides of the tensor the window walks / of the tensor indexed by output pixels
+};
+// Hi x Wi: the map the window walks, Ho x Wo: the map a column belongs to
+static DwGeom dw_geom(int N, int Hi, int Wi, int Ho, int Wo, int C, long i_ld_pix, long i_ld_img, long o_ld_pix, long o_ld_img, long min_threads) {
+    DwGeom g;
+    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.C = C; g.C4 = C / 4;
+    g.ctiles = sgx_cdiv(g.C4, 64);
+    g.CG = sgx_cdiv(g.C4, g.ctiles);  // (1296 channels: six strips of 54 groups, not five of 64 and one of 4)
+    g.PL = DW_THREADS / g.CG;
+    g.TH = 8;
+    while (g.TH > 2 && (long)N * sgx_cdiv(Ho, g.TH) * Wo * g.C4 < min_threads) g.TH >>= 1;
+    g.nstrips = sgx_cdiv(Ho, g.TH);
+    g.items = (long)N * g.nstrips * Wo;
+    g.i_ld_pix = i_ld_pix; g.i_ld_img = i_ld_img; g.o_ld_pix = o_ld_pix; g.o_ld_img = o_ld_img;
+    return g;
+}
+struct DwCol {
+    int img, strip, col;
+};
+__device__ __forceinline__ DwCol dw_column(const DwGeom& g, long item) {
+    DwCol k;
+    k.col = (int)(item % g.Wo);
+    const long t = item / g.Wo;
+    k.strip = (int)(t % g.nstrips);
+    k.img = (int)(t / g.nstrips);
+    return k;
+}
+// the three window columns wi0 .. wi0 + 2 of input row hi (zeros outside the map, or when !on)
+__device__ __forceinline__ void dw_ldrow(const float* __restrict__ xb, const DwGeom& g, int hi, int wi0, bool on, float4 (&r)[3]) {
+    const bool ok = on && hi >= 0 && hi < g.Hi;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int wi = wi0 + s;
+        r[s] = (ok && wi >= 0 && wi < g.Wi) ? sgx_ld4(xb + ((long)hi * g.Wi + wi) * g.i_ld_pix) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+__device__ __forceinline__ void dw_fma(float4& a, const float4& x, const float4& w) {
+    a.x = fmaf(x.x, w.x, a.x); a.y = fmaf(x.y, w.y, a.y); a.z = fmaf(x.z, w.z, a.z); a.w = fmaf(x.w, w.w, a.w);
+}
+__device__ __forceinline__ void dw_put(float* p, float4 v, int accumulate) {
+    if (accumulate) {
+        const float4 u = sgx_ld4(p);
+        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+    }
+    sgx_st4(p, v);
+}
+// per-workgroup partial row of `q`: the PL column lanes of a channel group meet in LDS and are added in lane order, in double
+__device__ __forceinline__ void dw_fold_store(float4 (&red)[DW_THREADS], const DwGeom& g, int tid, int cg, int pl, bool lane_ok, float4 q, float* dst) {
+    red[tid] = q;
+    __syncthreads();
+    if (lane_ok && pl == 0) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < g.PL; ++k) {
+            const float4 a = red[k * g.CG + cg];
+            s[0] += a.x; s[1] += a.y; s[2] += a.z; s[3] += a.w;
+        }
+        sgx_st4(dst, make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]));
+    }
+    __syncthreads();
+}
+
+// y = act(dwconv(x, w) + bias); flip: the taps in reverse order (the stride-1 data gradient is this kernel on dy); accumulate: y += ...;
+// partials: [2][gridDim.x][C] sum / sum of squares of the value before bias and activation.
+template <int ST>
+__global__ __launch_bounds__(DW_THREADS) void dwconv_fwd_kernel(DwGeom g, const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, float* __restrict__ y, int act, int flip, int accumulate,
+                                                                float* __restrict__ partials) {
+    __shared__ float4 red[DW_THREADS];
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c4 = blockIdx.y * g.CG + cg, c = c4 * 4;
+    const long item = (long)blockIdx.x * g.PL + pl;
+    const bool lane_ok = pl < g.PL && c4 < g.C4;
+    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+    if (lane_ok && item < g.items) {
+        const DwCol k = dw_column(g, item);
+        float4 wt[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) wt[t] = sgx_ld4(w + (long)(flip ? 8 - t : t) * g.C + c);
+        const float4 b = bias ? sgx_ld4(bias + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* __restrict__ xb = x + (long)k.img * g.i_ld_img + c;
+        float* __restrict__ yb = y + (long)k.img * g.o_ld_img + c;
+        const int wi0 = k.col * ST - 1;
+        const int ho0 = k.strip * g.TH, ho1 = min(g.Ho, ho0 + g.TH);
+        float4 r0[3], r1[3], r2[3], n1[3], n2[3];
+        dw_ldrow(xb, g, ho0 * ST - 1, wi0, true, r0);
+        dw_ldrow(xb, g, ho0 * ST, wi0, true, r1);
+        dw_ldrow(xb, g, ho0 * ST + 1, wi0, true, r2);
+        for (int ho = ho0; ho < ho1; ++ho) {
+            const bool more = ho + 1 < ho1;
+            const int hn = (ho + 1) * ST - 1;  // first window row of the next output row
+            if (ST == 2) dw_ldrow(xb, g, hn + 1, wi0, more, n1);
+            dw_ldrow(xb, g, hn + 2, wi0, more, n2);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) dw_fma(v, r0[s], wt[s]);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) dw_fma(v, r1[s], wt[3 + s]);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) dw_fma(v, r2[s], wt[6 + s]);
+            q0.x += v.x; q0.y += v.y; q0.z += v.z; q0.w += v.w;
+            q1.x += v.x * v.x; q1.y += v.y * v.y; q1.z += v.z * v.z; q1.w += v.w * v.w;
+            float* yp = yb + ((long)ho * g.Wo + k.col) * g.o_ld_pix;
+            if (accumulate) {
+                const float4 u = sgx_ld4(yp);
+                v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+            }
+            v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+            sgx_st4(yp, make_float4(sgx_act6(v.x, act), sgx_act6(v.y, act), sgx_act6(v.z, act), sgx_act6(v.w, act)));
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                if (ST == 1) { r0[s] = r1[s]; r1[s] = r2[s]; }
+                else { r0[s] = r2[s]; r1[s] = n1[s]; }
+                r2[s] = n2[s];
+            }
+        }
+    }
+    if (partials) {
+        dw_fold_store(red, g, tid, cg, pl, lane_ok, q0, partials + (long)blockIdx.x * g.C + c);
+        dw_fold_store(red, g, tid, cg, pl, lane_ok, q1, partials + ((long)gridDim.x + blockIdx.x) * g.C + c);
+    }
+}
+
+// Data gradient at stride 2, gather form.  Column = (image, strip of TH input rows, input column wi).  dx(hi, wi) takes the taps whose
+// output position exists: rows r with (hi + 1 - r) even, columns s with (wi + 1 - s) even.  Even wi: s = 1 at wo = wi / 2; odd wi: s = 2
+// at wo = (wi - 1) / 2 and s = 0 at wo = (wi + 1) / 2 - so a thread reads one or two dy columns (A, B).  Even hi = 2k: r = 1 at ho = k;
+// odd hi = 2k + 1: r = 2 at ho = k and r = 0 at ho = k + 1 - walking down, every dy row is loaded once per strip and used for three dx rows.
+__global__ __launch_bounds__(DW_THREADS) void dwconv_bwd_data_s2_kernel(DwGeom g, const float* __restrict__ dy, const float* __restrict__ w,
+                                                                        float* __restrict__ dx, int accumulate) {
+    // here g.Hi x g.Wi is the dy map (the rows the window walks) and g.Ho x g.Wo the dx map (TH even: strips start at even rows)
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c4 = blockIdx.y * g.CG + cg, c = c4 * 4;
+    const long item = (long)blockIdx.x * g.PL + pl;
+    if (!(pl < g.PL && c4 < g.C4 && item < g.items)) return;
+    const DwCol k = dw_column(g, item);
+    const int wi = k.col, odd = wi & 1;
+    const int colA = wi >> 1, colB = (wi + 1) >> 1, sA = odd ? 2 : 1;
+    const bool vB = odd && colB < g.Wi;
+    float4 wA[3], wB[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        wA[r] = sgx_ld4(w + (long)(r * 3 + sA) * g.C + c);
+        wB[r] = sgx_ld4(w + (long)(r * 3) * g.C + c);
+    }
+    const float* __restrict__ gb = dy + (long)k.img * g.i_ld_img + c;
+    float* __restrict__ xb = dx + (long)k.img * g.o_ld_img + c;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int hi0 = k.strip * g.TH, hi1 = min(g.Ho, hi0 + g.TH);
+    const float* pA = gb + (long)colA * g.i_ld_pix;
+    const float* pB = gb + (long)colB * g.i_ld_pix;
+    const long row_ld = (long)g.Wi * g.i_ld_pix;
+    float* px = xb + (long)wi * g.o_ld_pix;
+    const long xrow_ld = (long)g.Wo * g.o_ld_pix;
+    int ho = hi0 >> 1;
+    float4 aA = sgx_ld4(pA + ho * row_ld), aB = vB ? sgx_ld4(pB + ho * row_ld) : z;  // (row hi0 / 2 always exists)
+    for (int hi = hi0; hi < hi1; hi += 2, ++ho) {
+        const bool two = hi + 1 < hi1, nxt = two && ho + 1 < g.Hi;
+        const float4 bA = nxt ? sgx_ld4(pA + (ho + 1) * row_ld) : z, bB = (nxt && vB) ? sgx_ld4(pB + (ho + 1) * row_ld) : z;
+        float4 v = z;
+        dw_fma(v, aA, wA[1]);
+        dw_fma(v, aB, wB[1]);
+        dw_put(px + hi * xrow_ld, v, accumulate);
+        if (two) {
+            float4 u = z;
+            dw_fma(u, bA, wA[0]);
+            dw_fma(u, bB, wB[0]);
+            dw_fma(u, aA, wA[2]);
+            dw_fma(u, aB, wB[2]);
+            dw_put(px + (hi + 1) * xrow_ld, u, accumulate);
+        }
+        aA = bA; aB = bB;
+    }
+}
+
+// Weight gradient, stage 1: a workgroup owns the columns [blockIdx.x * per_blk, ...) and leaves ONE partial row [9][C] of its channel strip:
+// ws[blockIdx.x][tap][c] = sum over its pixels of dy * x(tap).  A thread walks its columns' strips with the forward kernel's window.
+template <int ST>
+__global__ __launch_bounds__(DW_THREADS) void dwconv_wgrad_kernel(DwGeom g, long per_blk, const float* __restrict__ x, const float* __restrict__ dy,
+                                                                  float* __restrict__ ws) {
+    __shared__ float4 red[DW_THREADS];
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c4 = blockIdx.y * g.CG + cg, c = c4 * 4;
+    const bool lane_ok = pl < g.PL && c4 < g.C4;
+    float4 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane_ok) {
+        const long i0 = (long)blockIdx.x * per_blk, i1 = i0 + per_blk < g.items ? i0 + per_blk : g.items;
+        for (long item = i0 + pl; item < i1; item += g.PL) {
+            const DwCol k = dw_column(g, item);
+            const float* __restrict__ xb = x + (long)k.img * g.i_ld_img + c;
+            const float* __restrict__ gb = dy + (long)k.img * g.o_ld_img + c;
+            const int wi0 = k.col * ST - 1;
+            const int ho0 = k.strip * g.TH, ho1 = min(g.Ho, ho0 + g.TH);
+            float4 r0[3], r1[3], r2[3];
+            dw_ldrow(xb, g, ho0 * ST - 1, wi0, true, r0);
+            if (ST == 1) dw_ldrow(xb, g, ho0, wi0, true, r1);
+            for (int ho = ho0; ho < ho1; ++ho) {
+                if (ST == 2) dw_ldrow(xb, g, ho * 2, wi0, true, r1);
+                dw_ldrow(xb, g, ho * ST + 1, wi0, true, r2);
+                const float4 d = sgx_ld4(gb + ((long)ho * g.Wo + k.col) * g.o_ld_pix);
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    dw_fma(acc[s], r0[s], d);
+                    dw_fma(acc[3 + s], r1[s], d);
+                    dw_fma(acc[6 + s], r2[s], d);
+                }
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    if (ST == 1) { r0[s] = r1[s]; r1[s] = r2[s]; }
+                    else r0[s] = r2[s];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) dw_fold_store(red, g, tid, cg, pl, lane_ok, acc[t], ws + ((long)blockIdx.x * 9 + t) * g.C + c);
+}
+// stage 2: dw[col] += sum over the nblk partial rows, in double, in a fixed order (64 row lanes x 4 column groups per workgroup: a lane adds
+// its rows ascending, the lanes meet in LDS and are added in lane order)
+__global__ __launch_bounds__(DW_THREADS) void dwconv_wgrad_fold_kernel(const float* __restrict__ ws, int nblk, int ncol, float* __restrict__ dw) {
+    __shared__ double red[64][4][4];
+    const int cgp = threadIdx.x & 3, rl = threadIdx.x >> 2;
+    const int col = (blockIdx.x * 4 + cgp) * 4;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    if (col < ncol)
+        for (int b = rl; b < nblk; b += 64) {
+            const float4 v = sgx_ld4(ws + (long)b * ncol + col);
+            a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
+        }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[rl][cgp][j] = a[j];
+    __syncthreads();
+    if (rl == 0 && col < ncol) {
+        double t[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < 64; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] += red[k][cgp][j];
+        const float4 u = sgx_ld4(dw + col);
+        sgx_st4(dw + col, make_float4(u.x + (float)t[0], u.y + (float)t[1], u.z + (float)t[2], u.w + (float)t[3]));
+    }
+}
+
+#define DW_ALIGNED(p) (((uintptr_t)(p) % 16) == 0)
+static int32_t dw_check(const sgx_conv_desc* d, const char* what) {
+    SGX_CHECK_ARG(d, "%s: null descriptor", what);
+    SGX_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "%s: bad dims N=%d H=%d W=%d C=%d", what, d->N, d->H, d->W, d->C);
+    SGX_CHECK_ARG(d->C % 4 == 0, "%s: C=%d must be a multiple of 4 (16-byte channel groups)", what, d->C);
+    SGX_CHECK_ARG(d->K == d->C, "%s: depthwise means K == C (one filter per channel), got K=%d C=%d", what, d->K, d->C);
+    SGX_CHECK_ARG(d->R == 3 && d->S == 3 && d->pad == 1, "%s: only the 3x3 pad-1 filter is built, got R=%d S=%d pad=%d", what, d->R, d->S, d->pad);
+    SGX_CHECK_ARG(d->stride == 1 || d->stride == 2, "%s: stride %d is not built (1 or 2)", what, d->stride);
+    SGX_CHECK_ARG(d->Ho == (d->H - 1) / d->stride + 1 && d->Wo == (d->W - 1) / d->stride + 1, "%s: Ho/Wo do not match (H+2p-R)/s+1", what);
+    SGX_CHECK_ARG(d->x_ld_pix >= d->C && d->y_ld_pix >= d->C && d->x_ld_pix % 4 == 0 && d->y_ld_pix % 4 == 0 && d->x_ld_img % 4 == 0 && d->y_ld_img % 4 == 0,
+                  "%s: pixel / image strides must be multiples of 4 floats and at least C", what);
+    SGX_CHECK_ARG((long)d->N * d->H * d->W < 0x7fffffffL, "%s: more than 2^31 pixels", what);
+    return SGX_OK;
+}
+static DwGeom dw_fwd_geom(const sgx_conv_desc* d) {
+    return dw_geom(d->N, d->H, d->W, d->Ho, d->Wo, d->C, d->x_ld_pix, d->x_ld_img, d->y_ld_pix, d->y_ld_img, DW_MIN_THREADS);
+}
+static dim3 dw_grid(const DwGeom& g) { return dim3((unsigned)sgx_cdiv(g.items, g.PL), (unsigned)g.ctiles); }
+
+extern "C" int32_t sgx_dwconv3x3_stat_blocks(const sgx_conv_desc* d) {
+    if (dw_check(d, "dwconv3x3_stat_blocks")) return 0;
+    const DwGeom g = dw_fwd_geom(d);
+    return (int32_t)sgx_cdiv(g.items, g.PL);
+}
+extern "C" int32_t sgx_dwconv3x3_fwd(const sgx_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int32_t act,
+                                     float* stat_partials, void* stream) {
+    int32_t rc = dw_check(d, "dwconv3x3_fwd");
+    if (rc) return rc;
+    SGX_CHECK_ARG(x && w && y, "dwconv3x3_fwd: null pointer");
+    SGX_CHECK_ARG(DW_ALIGNED(x) && DW_ALIGNED(w) && DW_ALIGNED(y) && DW_ALIGNED(bias) && DW_ALIGNED(stat_partials), "dwconv3x3_fwd: operands must be 16-byte aligned");
+    SGX_CHECK_ACT4(act, "dwconv3x3_fwd");
+    SGX_CHECK_ARG(!stat_partials || (!bias && act == SGX_ACT_NONE), "dwconv3x3_fwd: statistics rows go with the plain convolution (no bias, no activation)");
+    const DwGeom g = dw_fwd_geom(d);
+    if (d->stride == 1) SGX_LAUNCH(dwconv_fwd_kernel<1>, dw_grid(g), dim3(DW_THREADS), 0, stream, g, x, w, bias, y, act, 0, 0, stat_partials);
+    else SGX_LAUNCH(dwconv_fwd_kernel<2>, dw_grid(g), dim3(DW_THREADS), 0, stream, g, x, w, bias, y, act, 0, 0, stat_partials);
+    SGX_CHECK_LAUNCH("dwconv3x3_fwd");
+    return SGX_OK;
+}
+extern "C" int32_t sgx_dwconv3x3_bwd_data(const sgx_conv_desc* d, const float* dy, const float* w, float* dx, int32_t accumulate, void* stream) {
+    int32_t rc = dw_check(d, "dwconv3x3_bwd_data");
+    if (rc) return rc;
+    SGX_CHECK_ARG(dy && w && dx, "dwconv3x3_bwd_data: null pointer");
+    SGX_CHECK_ARG(DW_ALIGNED(dy) && DW_ALIGNED(w) && DW_ALIGNED(dx), "dwconv3x3_bwd_data: operands must be 16-byte aligned");
+    // columns are dx pixels; the window walks dy
+    const DwGeom g = dw_geom(d->N, d->Ho, d->Wo, d->H, d->W, d->C, d->y_ld_pix, d->y_ld_img, d->x_ld_pix, d->x_ld_img, DW_MIN_THREADS);
+    if (d->stride == 1) {  // a 3x3 pad-1 convolution of dy with the taps reversed
+        SGX_LAUNCH(dwconv_fwd_kernel<1>, dw_grid(g), dim3(DW_THREADS), 0, stream, g, dy, w, (const float*)nullptr, dx, SGX_ACT_NONE, 1, accumulate ? 1 : 0,
+                   (float*)nullptr);
+    } else {
+        SGX_LAUNCH(dwconv_bwd_data_s2_kernel, dw_grid(g), dim3(DW_THREADS), 0, stream, g, dy, w, dx, accumulate ? 1 : 0);
+    }
+    SGX_CHECK_LAUNCH("dwconv3x3_bwd_data");
+    return SGX_OK;
+}
+// weight gradient: ~1024 workgroups (four per CU) unless the problem has fewer columns - every workgroup leaves a [9][C-strip] partial row,
+// so more of them only adds traffic (7 x 7 x 960 at batch 64: 112 row blocks, 3.9 MB of partials beside 24 MB of operands)
+#define DW_WGRAD_MIN_THREADS 65536
+#define DW_WGRAD_BLOCKS 1024
+static DwGeom dw_wgrad_geom(const sgx_conv_desc* d, int* nblk, long* per_blk) {
+    const DwGeom g = dw_geom(d->N, d->H, d->W, d->Ho, d->Wo, d->C, d->x_ld_pix, d->x_ld_img, d->y_ld_pix, d->y_ld_img, DW_WGRAD_MIN_THREADS);
+    long n = sgx_cdiv(g.items, g.PL);
+    // (SGX_STRIDE_GRID is made for grid-stride kernels whose result does not depend on the workgroup count.  Here it is borrowed to cap the
+    // row blocks at two on the host emulation - every emulated workgroup pays eighteen 256-thread barriers in the fold - and that DOES
+    // change the partition of the sum: the weight gradient's bits differ between chip and emulation (each is deterministic), and the fold
+    // kernel's loop over more than 64 rows runs on the chip only.)
+    const long cap = SGX_STRIDE_GRID(sgx_cdiv(DW_WGRAD_BLOCKS, g.ctiles));
+    if (n > cap) n = cap;
+    *per_blk = (g.items + n - 1) / n;
+    *nblk = sgx_cdiv(g.items, *per_blk);
+    return g;
+}
+extern "C" int64_t sgx_dwconv3x3_bwd_weight_workspace(const sgx_conv_desc* d) {
+    if (dw_check(d, "dwconv3x3_bwd_weight_workspace")) return 0;
+    int nblk;
+    long per_blk;
+    dw_wgrad_geom(d, &nblk, &per_blk);
+    return (int64_t)nblk * 9 * d->C * (int64_t)sizeof(float);
+}
+extern "C" int32_t sgx_dwconv3x3_bwd_weight(const sgx_conv_desc* d, const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes,
+                                            void* stream) {
+    int32_t rc = dw_check(d, "dwconv3x3_bwd_weight");
+    if (rc) return rc;
+    SGX_CHECK_ARG(x && dy && dw, "dwconv3x3_bwd_weight: null pointer");
+    SGX_CHECK_ARG(DW_ALIGNED(x) && DW_ALIGNED(dy) && DW_ALIGNED(dw), "dwconv3x3_bwd_weight: operands must be 16-byte aligned");
+    int nblk;
+    long per_blk;
+    const DwGeom g = dw_wgrad_geom(d, &nblk, &per_blk);
+    if (!ws || ws_bytes < (int64_t)nblk * 9 * d->C * (int64_t)sizeof(float) || ((uintptr_t)ws % 16) != 0)
+        SGX_FAIL(SGX_ERR_WORKSPACE, "dwconv3x3_bwd_weight: workspace too small or unaligned (sgx_dwconv3x3_bwd_weight_workspace)");
+    const dim3 grid((unsigned)nblk, (unsigned)g.ctiles);
+    if (d->stride == 1) SGX_LAUNCH(dwconv_wgrad_kernel<1>, grid, dim3(DW_THREADS), 0, stream, g, per_blk, x, dy, (float*)ws);
+    else SGX_LAUNCH(dwconv_wgrad_kernel<2>, grid, dim3(DW_THREADS), 0, stream, g, per_blk, x, dy, (float*)ws);
+    SGX_CHECK_LAUNCH("dwconv3x3_bwd_weight");
+    SGX_LAUNCH(dwconv_wgrad_fold_kernel, dim3((unsigned)sgx_cdiv(9L * d->C, 16)), dim3(DW_THREADS), 0, stream, (const float*)ws, nblk, 9 * d->C, dw);
+    SGX_CHECK_LAUNCH("dwconv3x3_bwd_weight (fold)");
     return SGX_OK;
 }

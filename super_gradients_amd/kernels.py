@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import ConvDesc, LossDesc, MatchDesc, NmsDesc, check, lib, ptr, stream
 
-ACT = {None: 0, "none": 0, "relu": 1, "silu": 2}
+ACT = {None: 0, "none": 0, "relu": 1, "silu": 2, "relu6": 3}  # relu6: the affine sweep, bn_bwd and the depthwise convolution; the rest reject it
 
 
 # --------------------------------------------------------------------------------------------- workspace
@@ -497,6 +497,64 @@ def conv2d_bwd_weight(x, dy, dw, dbias=None, stride=1, pad=0):
         d.wgrad_ws = lib().sgx_conv2d_bwd_weight_workspace(d.ref)
     ws = WORKSPACE.get(d.wgrad_ws, x.device)
     check(lib().sgx_conv2d_bwd_weight(d.ref, ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()), "sgx_conv2d_bwd_weight")
+
+
+# --------------------------------------------------------------------------------------------- depthwise 3x3 convolution
+def dw_empty(C, device) -> torch.Tensor:
+    """A depthwise filter: logical [C,1,3,3] (nn.Conv2d(groups=C)'s shape), stored [3][3][C]."""
+    return torch.empty(3, 3, C, device=device, dtype=torch.float32).permute(2, 0, 1).unsqueeze(1)
+
+
+def to_dw(w: torch.Tensor) -> torch.Tensor:
+    out = dw_empty(w.shape[0], w.device)
+    out.copy_(w)
+    return out
+
+
+def _chk_dw(w: torch.Tensor, C):
+    if tuple(w.shape) != (C, 1, 3, 3) or (w.stride(0), w.stride(2), w.stride(3)) != (1, 3 * C, C):
+        raise _lib.SgxError(f"depthwise filter must be logical [C,1,3,3] stored [3][3][C] for C={C}; got shape {tuple(w.shape)} strides {w.stride()}")
+
+
+def dwconv3x3_fwd(x, w, bias=None, out=None, act=None, stride=1, stat_partials=False):
+    """y = act(dwconv(x, w) + bias), 3x3 pad 1; stat_partials: also the BatchNorm statistics rows of y (then no bias / activation)."""
+    C = x.shape[3]
+    _chk_dw(w, C)
+    if out is None:
+        out = torch.empty(conv_out_shape(x, C, 3, 3, stride, 1), device=x.device, dtype=torch.float32)
+    d = conv_desc(x, C, 3, 3, stride, 1, out)
+    parts = None
+    if stat_partials:
+        nblk = lib().sgx_dwconv3x3_stat_blocks(d.ref)
+        if nblk <= 0:
+            check(-1, "sgx_dwconv3x3_stat_blocks")
+        parts = torch.empty(2, nblk, C, device=x.device, dtype=torch.float32)
+    check(lib().sgx_dwconv3x3_fwd(d.ref, ptr(x), ptr(w), ptr(bias), ptr(out), ACT[act], ptr(parts), stream()), "sgx_dwconv3x3_fwd")
+    return (out, parts) if stat_partials else out
+
+
+def dwconv3x3_bwd_data(dy, w, x_shape, stride=1, out=None, accumulate=False):
+    C = x_shape[3]
+    _chk_dw(w, C)
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("dwconv3x3_bwd_data: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
+    d = conv_desc(out, C, 3, 3, stride, 1, dy)
+    check(lib().sgx_dwconv3x3_bwd_data(d.ref, ptr(dy), ptr(w), ptr(out), int(accumulate), stream()), "sgx_dwconv3x3_bwd_data")
+    return out
+
+
+def dwconv3x3_bwd_weight(x, dy, dw, stride=1):
+    """dw (logical [C,1,3,3], stored [3][3][C]) += grad."""
+    C = x.shape[3]
+    _chk_dw(dw, C)
+    d = conv_desc(x, C, 3, 3, stride, 1, dy)
+    dws = getattr(d, "dw_wgrad_ws", None)
+    if dws is None:
+        dws = d.dw_wgrad_ws = lib().sgx_dwconv3x3_bwd_weight_workspace(d.ref)
+    ws = WORKSPACE.get(dws, x.device)
+    check(lib().sgx_dwconv3x3_bwd_weight(d.ref, ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel(), stream()), "sgx_dwconv3x3_bwd_weight")
 
 
 _TICKETS = {}

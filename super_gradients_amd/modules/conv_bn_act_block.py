@@ -13,7 +13,17 @@ from torch import nn
 
 from .. import kernels as K
 from .engine import SgxBlock
-from .layers import BatchNorm, ConvLayer, act_name
+from .layers import BatchNorm, ConvLayer, DepthwiseConvLayer, act_name
+
+
+def _conv_layer(in_channels, out_channels, kernel_size, stride, padding, groups):
+    """groups == 1: the implicit-GEMM ConvLayer; groups == in == out with a 3x3 pad-1 filter: the depthwise layer; anything else raises."""
+    if groups in (None, 1):
+        return ConvLayer(in_channels, out_channels, kernel_size, stride, padding, bias=False)
+    if groups == in_channels == out_channels and kernel_size == 3 and padding == 1:
+        return DepthwiseConvLayer(in_channels, stride)
+    raise NotImplementedError(f"grouped convolution on the HIP path: groups=1, or depthwise 3x3 pad 1 (groups == in_channels == out_channels); got groups={groups}, "
+                              f"{in_channels} -> {out_channels}, kernel {kernel_size}, padding {padding}")
 
 
 class _ConvBN(SgxBlock):
@@ -37,6 +47,13 @@ class _ConvBN(SgxBlock):
         w = conv._w
         if w is None:
             raise RuntimeError("prep_model_for_conversion needs a materialised model (the fold reads the arena views)")
+        if conv.depthwise:  # act(dwconv(x, w * s[c]) + t[c]): bias and activation (ReLU6 included) live in the depthwise epilogue
+            with torch.no_grad():
+                s = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
+                wf = K.dw_empty(w.shape[0], w.device)
+                wf.copy_(w.detach() * s.view(-1, 1, 1, 1))
+                self._folded = (wf, (bn.bias.detach() - bn.running_mean * s).contiguous())
+            return
         K_, C_, R_, S_ = w.shape
         if w.stride() != (R_ * S_ * C_, 1, S_ * C_, C_):
             # channel-padded filters (C % 4 != 0): the fp32 path keeps the general eval sequence; the half-precision path converts filters to
@@ -57,10 +74,15 @@ class _ConvBN(SgxBlock):
             self._folded = self._folded_half = None  # the weights are about to change
         return super().train(mode)
 
-    def fwd(self, x, out=None, post_add=None, post_scale=None):
+    def fwd(self, x, out=None, post_add=None, post_scale=None, residual=None):
         """post_add: tensor added AFTER the activation (pp_yolo_head.py:205 `stem_cls(feat, avg_feat) + feat`); its gradient is the
-        caller's (dy reaches it unchanged).  post_scale (half-precision inference only): a multiplier of post_add."""
+        caller's (dy reaches it unchanged).  post_scale (half-precision inference only): a multiplier of post_add.
+        residual (layers without activation only - MobileNetV2's linear bottleneck, mobilenetv2.py:95-97 `x + conv(x)`): added by the
+        BatchNorm's own affine sweep (r1 of sgx_affine_act_fwd), not by a pass of its own; its gradient is the caller's too."""
         conv, bn = self._parts()
+        if residual is not None:
+            if self.act is not None or post_add is not None or x.dtype == K.HALF:
+                raise RuntimeError("residual rides in the affine sweep of a layer without activation (fp32)")
         if x.dtype == K.HALF:  # half-precision inference: the folded deployment form, everything in ONE bf16 launch
             folded = self._folded if self._folded is not None else self._folded_half
             if self.training or folded is None:
@@ -75,26 +97,32 @@ class _ConvBN(SgxBlock):
             M = t.shape[0] * t.shape[1] * t.shape[2]
             scale, shift, mean, invstd = bn.scale_shift(parts, M, True)
             if post_add is None:
-                y = K.affine_act(t, scale, shift, act=self.act, out=out)
+                y = K.affine_act(t, scale, shift, r1=residual, act=self.act, out=out)
             else:
                 y = K.dual_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out)
             self._ctx = (x, t, scale, shift, mean, invstd)
             self._req = None
             return y
         if self._folded is not None and post_add is None:
-            return K.conv2d_fwd(x, self._folded[0], bias=self._folded[1], out=out, act=self.act, stride=conv.stride, pad=conv.padding)
+            if conv.depthwise and residual is None:
+                return K.dwconv3x3_fwd(x, self._folded[0], bias=self._folded[1], out=out, act=self.act, stride=conv.stride)
+            if self.act == "relu6":  # the conv epilogues do not carry ReLU6: conv + bias, then the sweep in place
+                t = K.conv2d_fwd(x, self._folded[0], bias=self._folded[1], stride=conv.stride, pad=conv.padding)
+                return K.affine_act(t, act=self.act, out=out if out is not None else t)
+            if not conv.depthwise:
+                return K.conv2d_fwd(x, self._folded[0], bias=self._folded[1], addend=residual, out=out, act=self.act, stride=conv.stride, pad=conv.padding)
         t = conv.conv(x)
         scale, shift, _, _ = bn.scale_shift(None, 0, False)
         if post_add is not None:
             return K.dual_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out if out is not None else t)
-        return K.affine_act(t, scale, shift, act=self.act, out=out if out is not None else t)
+        return K.affine_act(t, scale, shift, r1=residual, act=self.act, out=out if out is not None else t)
 
     def bn_reduce_request(self):
         """This layer's BatchNorm-backward reduce as a request for the data-gradient launch that finalises its output gradient (the caller
         hands it to that launch; bwd() then finds the partial sums ready and skips its own reduce sweep).  None when it cannot be handed over
         (synchronised BatchNorm reduces across ranks on its own path)."""
         conv, bn = self._parts()
-        if self._ctx is None or bn._synced() or not self._net.fuse_bn_reduce:
+        if self._ctx is None or bn._synced() or not self._net.fuse_bn_reduce or self.act == "relu6":  # (the data-gradient epilogues do not carry ReLU6)
             return None
         _, t, scale, shift, mean, _ = self._ctx
         self._req = K.BnReduceRequest(t, scale, shift, mean, self.act)
@@ -118,10 +146,8 @@ class Conv(_ConvBN):
 
     def __init__(self, input_channels, output_channels, kernel, stride, activation_type, padding: int = None, groups: int = None):
         super().__init__()
-        if groups not in (None, 1):
-            raise NotImplementedError("grouped convolution is outside the MI355X hot path (SURVEY.md 8: groups=1 only)")
         pad = kernel // 2 if padding is None else padding
-        self.conv = ConvLayer(input_channels, output_channels, kernel, stride, pad, bias=False)
+        self.conv = _conv_layer(input_channels, output_channels, kernel, stride, pad, groups)
         self.bn = BatchNorm(output_channels)
         self.act = act_name(activation_type)
 
@@ -140,17 +166,44 @@ class ConvBNAct(_ConvBN):
                  padding_mode="zeros", use_normalization=True, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True,
                  device=None, dtype=None, activation_kwargs=None):
         super().__init__()
-        if groups != 1 or dilation != 1 or padding_mode != "zeros" or not use_normalization or not affine or not track_running_stats:
-            raise NotImplementedError("ConvBNAct on the HIP path supports groups=1, dilation=1, zero padding, affine BN with running stats")
+        if dilation != 1 or padding_mode != "zeros" or not use_normalization or not affine or not track_running_stats:
+            raise NotImplementedError("ConvBNAct on the HIP path supports dilation=1, zero padding, affine BN with running stats")
         if bias:
             raise NotImplementedError("conv bias followed by BatchNorm is redundant; the HIP path implements bias=False (as all hot-path call sites use)")
         self.seq = _Seq()
-        self.seq.add_module("conv", ConvLayer(in_channels, out_channels, kernel_size, stride, padding, bias=False))
+        self.seq.add_module("conv", _conv_layer(in_channels, out_channels, kernel_size, stride, padding, groups))
         self.seq.add_module("bn", BatchNorm(out_channels, eps=eps, momentum=momentum))
         self.act = act_name(activation_type)
 
     def _parts(self):
         return self.seq.conv, self.seq.bn
+
+
+class ConvBNSeq(_ConvBN):
+    """nn.Sequential(nn.Conv2d(bias=False), nn.BatchNorm2d[, activation]) with the reference's numeric keys 0.weight, 1.* (mobilenetv2.py:39-44
+    conv_bn / conv_1x1_bn)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation_type=None, groups=1):
+        super().__init__()
+        self.add_module("0", _conv_layer(in_channels, out_channels, kernel_size, stride, padding, groups))
+        self.add_module("1", BatchNorm(out_channels))
+        self.act = act_name(activation_type)
+
+    def _parts(self):
+        return self._modules["0"], self._modules["1"]
+
+
+class ConvBNView(_ConvBN):
+    """conv -> BatchNorm -> activation over layers that are registered ELSEWHERE (the numbered entries of a reference nn.Sequential that holds
+    several such triples: InvertedResidual.conv, mobilenetv2.py:70-93).  Owns no parameter: it adds nothing to the state_dict."""
+
+    def __init__(self, conv, bn, activation_type=None):
+        super().__init__()
+        self._pair = (conv, bn)  # (a tuple: not registered as sub-modules)
+        self.act = act_name(activation_type)
+
+    def _parts(self):
+        return self._pair
 
 
 class ConvBNReLU(ConvBNAct):

@@ -1,3 +1,4 @@
 from .resnet import (BasicResNetBlock, Bottleneck, CifarResNet, ResNet, ResNet18, ResNet18Cifar, ResNet34, ResNet50, ResNet101,  # noqa: F401
                      ResNet152, ResNet50_3343)
 from .repvgg import (RepVGG, RepVggA0, RepVggA1, RepVggA2, RepVggB0, RepVggB1, RepVggB2, RepVggB3, RepVggCustom, RepVggD2SE)  # noqa: F401
+from .mobilenetv2 import CustomMobileNetV2, InvertedResidual, MobileNetV2, MobileNetV2_135, MobileNetV2Base  # noqa: F401
