@@ -380,7 +380,7 @@ int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float* x, int64_t
  * replaces, per block, F.batch_norm x2 + the two branch adds + the activation (modules/qarepvgg_block.py:184-204) and their backward.
  *   sgx_qarep_fwd_finalize  both BatchNorms' statistics from the moments (s = bn3(y) + u is affine in (y, u) per channel; fp64): running
  *                           statistics updated like nn.BatchNorm2d; cf[4][C] = operand rows of the forward sweep
- *                           out = act(cf0*y + cf1 + cf2*u + cf3)  (sgx_dual_affine_act_fwd(y, cf0, cf1, u, cf2, cf3));
+ *                           out = act(cf0*y + cf1 + cf2*u + cf3)  (sgx_tri_affine_act_fwd(y, cf0, cf1, u, cf2, cf3));
  *                           sv[8][C] = mean3, invstd3, scale3, shift3, mean_s, invstd_p, scale_p, shift_p for the backward.
  *                           ws: sgx_qarep_workspace(nblk, C) bytes (also covers the backward finalize).
  *   sgx_qarep_bwd_reduce    ONE sweep over (dout, y, u): partials4[4][sgx_stats_blocks(M)][C] = sum g, g*(s-mean_s), g*(y-mean3),
@@ -421,38 +421,25 @@ int32_t sgx_relu_bwd(const float* dy, int64_t dy_ld, const float* y, int64_t y_l
  * leave, bit for bit (same row blocks, same order), so sgx_bn_bwd_finalize takes them as they are.  x: the saved conv output of bn_n. */
 int32_t sgx_relu_bwd_bn_reduce(const float* dy, int64_t dy_ld, const float* y, int64_t y_ld, const float* x, int64_t x_ld,
                                const float* save_mean, float* g, int64_t g_ld, int64_t M, int32_t C, float* partials, void* stream);
-/* RepVGGBlock training forward (modules/repvgg_block.py:98-107: act(bn3(conv3x3 x) + bn1(conv1x1 x))) and the post-activation
- * residuals around it (csp_resnet.py:43-49 `x + y`, pp_yolo_head.py:205 `stem_cls(feat) + feat`) as ONE sweep:
- *   y = act(s1[c]*x1 + t1[c] [+ s2[c]*x2 + t2[c]]) [+ r_scale * r_scale_dev[0] * r]        x2 / r / r_scale_dev may be NULL.
- * The scaled form is the YOLO-NAS bottleneck's `alpha * x + cv2(cv1(x))` (yolo_stages.py:61-63) written by cv2's own sweep.            */
-int32_t sgx_dual_affine_act_fwd(const float* x1, int64_t x1_ld, const float* s1, const float* t1, const float* x2, int64_t x2_ld,
-                                const float* s2, const float* t2, const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev,
-                                float* y, int64_t y_ld, int64_t M, int32_t C, int32_t act, void* stream);
-/* its backward through the activation: g = dy * act'(s1*x1 + t1 [+ s2*x2 + t2]) - the upstream gradient both BatchNorm backward
- * passes (sgx_bn_bwd_*, act = none) then consume.                                                                            */
-int32_t sgx_dual_affine_act_bwd(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
-                                const float* x2, int64_t x2_ld, const float* s2, const float* t2, float* g, int64_t g_ld, int64_t M,
-                                int32_t C, int32_t act, void* stream);
-/* the same sweep also leaving the reduce rows of BOTH BatchNorm backward passes (round 5): partials4 = [4][sgx_stats_blocks(M)][C] =
- * sum g, sum g (x1 - mean1), sum g, sum g (x2 - mean2) - rows 0-1 are what sgx_bn_bwd_reduce(g, x1) would produce, rows 2-3 what
- * sgx_bn_bwd_reduce(g, x2) would (act = none): two passes over g and the saved conv outputs less per RepVGG block.                   */
-int32_t sgx_dual_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
-                                       const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2, const float* mean2,
-                                       float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials4, void* stream);
-/* RepVGGBlock with the identity-BatchNorm branch (the RepVGG classifiers' blocks with in == out, stride 1; modules/repvgg_block.py:94-103:
- * act(bn3(conv3x3 x) + alpha * bn1(conv1x1 x) + bn_id(x))) as ONE sweep:
- *   y = act(s1[c]*x1 + t1[c] [+ s2[c]*x2 + t2[c]] [+ s3[c]*x3 + t3[c]]) [+ r_scale * r_scale_dev[0] * r]     x2 / x3 / r may be NULL.
+/* The sum of one to three BatchNorm outputs, the activation and a post-activation residual as ONE sweep:
+ *   y = act(s1[c]*x1 + t1[c] [+ s2[c]*x2 + t2[c]] [+ s3[c]*x3 + t3[c]]) [+ r_scale * r_scale_dev[0] * r]     x2 / x3 / r / r_scale_dev may be NULL.
+ * Two branches: RepVGGBlock's training forward (modules/repvgg_block.py:98-107: act(bn3(conv3x3 x) + alpha * bn1(conv1x1 x))) and the
+ * QARepVGG forward sweep on its coefficient rows; three: the RepVGG classifiers' blocks with in == out, stride 1 (:94-103, x3 = the block's
+ * own input, the identity-BatchNorm branch); r: the residuals around the block (csp_resnet.py:43-49 `x + y`, pp_yolo_head.py:205
+ * `stem_cls(feat) + feat`), in its scaled form the YOLO-NAS bottleneck's `alpha * x + cv2(cv1(x))` (yolo_stages.py:61-63) written by cv2's
+ * own sweep.  A NULL branch gives the bits of a branch with zero scale and shift.
  * partials (may be NULL): [2][nblk][C] per-channel sum / sum of squares of the value STORED in y - the rows sgx_bn_finalize /
  * sgx_bn_reduce_sums consume; the next block's identity BatchNorm normalises exactly that tensor, so no statistics pass over it runs.
- * nblk: row blocks of the sweep, 0 = sgx_stats_blocks(M); y does not depend on it.  x3 NULL: sgx_dual_affine_act_fwd's y bit for bit. */
+ * nblk: row blocks of the sweep, 0 = sgx_stats_blocks(M); y does not depend on it.                                                      */
 int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const float* s1, const float* t1, const float* x2, int64_t x2_ld,
                                const float* s2, const float* t2, const float* x3, int64_t x3_ld, const float* s3, const float* t3,
                                const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev, float* y, int64_t y_ld, int64_t M,
                                int32_t C, int32_t act, float* partials, int32_t nblk, void* stream);
-/* its backward through the activation and the reduce rows of ALL THREE BatchNorm backward passes in one sweep:
- *   g = dy * act'(pre-activation, recomputed),   partials = [6][nblk][C] = sum g, sum g (x1 - mean1), sum g, sum g (x2 - mean2), sum g,
- *   sum g (x3 - mean3): rows 2i, 2i+1 are what sgx_bn_bwd_reduce(g, x_i) would produce (act = none).  x3 NULL: [4][nblk][C],
- * sgx_dual_affine_act_bwd_reduce's g and rows bit for bit.  nblk as above.                                                        */
+/* its backward through the activation and the reduce rows of EVERY branch's BatchNorm backward in one sweep (round 5):
+ *   g = dy * act'(pre-activation, recomputed from the saved conv outputs) - the upstream gradient the BatchNorm backward passes
+ *   (sgx_bn_bwd_*, act = none) then consume,   partials = [2 n][nblk][C] over the n branches that are present, in order (x2 / x3 may be
+ *   NULL): rows 2i, 2i+1 = sum g, sum g (x_i - mean_i) are what sgx_bn_bwd_reduce(g, x_i) would produce (act = none), bit for bit - one
+ *   pass over g and a saved conv output less per branch.  nblk as above.                                                               */
 int32_t sgx_tri_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
                                       const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2, const float* mean2,
                                       const float* x3, int64_t x3_ld, const float* s3, const float* t3, const float* mean3, float* g,

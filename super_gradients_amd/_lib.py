@@ -182,9 +182,6 @@ PROTOTYPES = {
     "sgx_dwconv3x3_bwd_data": (_i32, [_CD, _P, _P, _P, _i32, _P]),
     "sgx_dwconv3x3_bwd_weight_workspace": (_i64, [_CD]),
     "sgx_dwconv3x3_bwd_weight": (_i32, [_CD, _P, _P, _P, _P, _i64, _P]),
-    "sgx_dual_affine_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _f, _P, _P, _i64, _i64, _i32, _i32, _P]),
-    "sgx_dual_affine_act_bwd": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _i64, _i32, _i32, _P]),
-    "sgx_dual_affine_act_bwd_reduce": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _i64, _i32, _i32, _P, _P]),
     "sgx_tri_affine_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _f, _P, _P, _i64, _i64, _i32, _i32, _P, _i32, _P]),
     "sgx_tri_affine_act_bwd_reduce": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _i64, _i32, _i32,
                                              _P, _i32, _P]),

@@ -1,11 +1,15 @@
 // BatchNorm (training) statistics, the fused affine/residual/activation passes around it, and their
 // backward - HBM-bound row x channel sweeps over NHWC tensors (rows = pixels, columns = channels).
 //
-// One sweep skeleton serves all of them: a 256-thread workgroup owns a contiguous run of rows and a
-// strip of up to 256 channels; a thread owns one float4 channel group and every RL-th row, so a wave's
-// loads are 16-byte, channel-contiguous (coalesced), and per-channel reductions are lane-local until a
-// single LDS fold at the end.  Reductions are two-stage and deterministic: per-workgroup partials in
-// fp32, a tiny finalize kernel accumulating them in fp64 in a fixed order (no float atomics).
+// One sweep skeleton (sweep_kernel<F, NQ, ROWS>, launched by run_sweep) serves all of them: a 256-thread
+// workgroup owns a contiguous run of rows and a strip of up to 256 channels; a thread owns one float4
+// channel group and every RL-th row, so a wave's loads are 16-byte, channel-contiguous (coalesced), and
+// the NQ per-channel reductions are lane-local until a single LDS fold at the end.  What differs between
+// the sweeps is a functor F (loads, constants, arithmetic) and the number of rows ROWS a lane keeps in
+// flight.  Reductions are two-stage and deterministic: per-workgroup partials in fp32, a tiny finalize
+// kernel accumulating them in fp64 in a fixed order (no float atomics).  The sums of BatchNorm outputs
+// around a convolution - one, two or three branches, forward and backward - are one functor family
+// (BranchSum*, behind sgx_tri_affine_act_fwd / sgx_tri_affine_act_bwd_reduce).
 // Reference call sites: include/sgx_hip.h (BatchNorm section).
 #include "sgx_common.h"
 #include <atomic>
@@ -28,14 +32,15 @@ extern "C" int32_t sgx_stats_blocks(int64_t M) {
     return (int32_t)n;
 }
 
-static SweepGeom sweep_geom(long M, int C) {
+// nblk: the number of row blocks (0: sgx_stats_blocks(M)) - what a sweep stores does not depend on it, the count of its partial rows does
+static SweepGeom sweep_geom(long M, int C, int nblk = 0) {
     SweepGeom g;
     g.M = M;
     g.C = C;
     g.C4 = C / 4;
     g.CG = g.C4 < SW_MAXCG ? g.C4 : SW_MAXCG;
     g.RL = SW_THREADS / g.CG;
-    g.nblk = sgx_stats_blocks(M);
+    g.nblk = nblk > 0 ? nblk : sgx_stats_blocks(M);
     g.rows_per_blk = (int)((M + g.nblk - 1) / g.nblk);
     g.ctiles = (g.C4 + g.CG - 1) / g.CG;
     return g;
@@ -43,22 +48,26 @@ static SweepGeom sweep_geom(long M, int C) {
 
 // F: struct with  In load(long r, int c)  (all global loads of row r, channels c..c+3),  Cst consts(int c)  (the per-channel
 // constants of the lane's four channels - scale / shift / coefficient rows - loaded ONCE, ahead of the row loop) and
-// void apply(long r, int c, const In&, const Cst&, float4& q0, float4& q1)  (the arithmetic, the stores and up to two per-channel
+// void apply(long r, int c, const In&, const Cst&, float4 (&q)[max(NQ, 1)])  (the arithmetic, the stores and NQ per-channel
 // accumulations).  (Round 5: the constants used to be re-read inside apply for every row - the compiler cannot hoist them past the
 // row's stores, which may alias them for all it knows: 7 of the 9 load instructions per row of the BatchNorm-backward apply, 14 of 17
 // of the QARepVGG one, all L1 hits but each a trip through the texture path, which at 64 B/clk/CU was busier with them than with the
-// data.)  The split lets the sweep issue the loads of FOUR rows before the first store: with one row in flight
-// per lane these streaming kernels sat at ~40 % of the HBM rate (r1b profile) - latency-bound, not bandwidth-bound.
+// data.)  The split lets the sweep issue the loads of ROWS rows before the first store: with one row in flight
+// per lane these streaming kernels sat at ~40 % of the HBM rate (r1b profile) - latency-bound, not bandwidth-bound.  ROWS is 4 for the
+// sweeps over one or two tensors and 2 for those that read three or carry many constants (the registers of a row in flight).
 // In-place use (output aliasing an input) stays correct: a row is completely read before it is written, rows are disjoint.
-template <typename F, int NQ>
+// partials (NQ > 0; may be NULL: no reduction): [NQ][nblk][C], plane k = the lane sums of q[k] (fp32), met in ascending row-lane order in
+// fp64 and rounded once.  NQ == 0 reserves no LDS.
+template <typename F, int NQ, int ROWS>
 __global__ __launch_bounds__(SW_THREADS) void sweep_kernel(F f, SweepGeom g, float* partials) {
-    __shared__ float4 red[NQ > 0 ? NQ : 1][SW_THREADS];
     const int tid = threadIdx.x;
     const int cg = tid % g.CG, rl = tid / g.CG;
     const int c4 = blockIdx.y * g.CG + cg;
     const bool live = (rl < g.RL) && (c4 < g.C4);
     const int c = c4 * 4;
-    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+    float4 q[NQ > 0 ? NQ : 1];
+#pragma unroll
+    for (int k = 0; k < (NQ > 0 ? NQ : 1); ++k) q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live) {
         long r0 = (long)blockIdx.x * g.rows_per_blk;
         long r1 = r0 + g.rows_per_blk;
@@ -66,45 +75,46 @@ __global__ __launch_bounds__(SW_THREADS) void sweep_kernel(F f, SweepGeom g, flo
         long r = r0 + rl;
         const long st = g.RL;
         const typename F::Cst k = f.consts(c);
-        for (; r + 3 * st < r1; r += 4 * st) {
-            typename F::In i0 = f.load(r, c), i1 = f.load(r + st, c), i2 = f.load(r + 2 * st, c), i3 = f.load(r + 3 * st, c);
-            f.apply(r, c, i0, k, q0, q1);
-            f.apply(r + st, c, i1, k, q0, q1);
-            f.apply(r + 2 * st, c, i2, k, q0, q1);
-            f.apply(r + 3 * st, c, i3, k, q0, q1);
+        for (; r + (ROWS - 1) * st < r1; r += ROWS * st) {
+            typename F::In in[ROWS];
+#pragma unroll
+            for (int u = 0; u < ROWS; ++u) in[u] = f.load(r + u * st, c);
+#pragma unroll
+            for (int u = 0; u < ROWS; ++u) f.apply(r + u * st, c, in[u], k, q);
         }
         for (; r < r1; r += st) {
             typename F::In i0 = f.load(r, c);
-            f.apply(r, c, i0, k, q0, q1);
+            f.apply(r, c, i0, k, q);
         }
     }
-    if (NQ > 0 && partials) {
-        red[0][tid] = q0;
-        if (NQ > 1) red[NQ > 1 ? 1 : 0][tid] = q1;
+    if constexpr (NQ > 0) {
+        if (!partials) return;  // uniform across the workgroup
+        __shared__ float4 red[NQ][SW_THREADS];
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) red[k][tid] = q[k];
         __syncthreads();
         if (live && rl == 0) {
             // the lane sums meet in double: the partial row carries ONE fp32 rounding (random sign), not a chain of them - the per-channel
             // means the finalize kernels form from these rows (mean of g in the BatchNorm backward above all) are then good to ~1e-9 relative
-            double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int k = 0; k < g.RL; ++k) {
-                float4 a = red[0][k * g.CG + cg];
-                s0[0] += a.x; s0[1] += a.y; s0[2] += a.z; s0[3] += a.w;
-                if (NQ > 1) {
-                    float4 b = red[NQ > 1 ? 1 : 0][k * g.CG + cg];
-                    s1[0] += b.x; s1[1] += b.y; s1[2] += b.z; s1[3] += b.w;
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) {
+                double t[4] = {0.0, 0.0, 0.0, 0.0};
+                for (int j = 0; j < g.RL; ++j) {
+                    const float4 a = red[k][j * g.CG + cg];
+                    t[0] += a.x; t[1] += a.y; t[2] += a.z; t[3] += a.w;
                 }
+                sgx_st4(partials + ((long)k * g.nblk + blockIdx.x) * g.C + c, make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]));
             }
-            sgx_st4(partials + (long)blockIdx.x * g.C + c, make_float4((float)s0[0], (float)s0[1], (float)s0[2], (float)s0[3]));
-            if (NQ > 1) sgx_st4(partials + ((long)g.nblk + blockIdx.x) * g.C + c, make_float4((float)s1[0], (float)s1[1], (float)s1[2], (float)s1[3]));
         }
     }
 }
 
-template <typename F, int NQ>
-static int32_t run_sweep(const F& f, long M, int C, float* partials, void* stream, const char* what) {
+template <typename F, int NQ, int ROWS>
+static int32_t run_sweep(const F& f, long M, int C, float* partials, void* stream, const char* what, int nblk = 0) {
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "%s: need M>0 and C%%4==0 (C=%d)", what, C);
-    SweepGeom g = sweep_geom(M, C);
-    SGX_LAUNCH((sweep_kernel<F, NQ>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, f, g, partials);
+    SGX_CHECK_ARG(nblk >= 0 && nblk <= M, "%s: row blocks %d outside 0..M", what, nblk);
+    SweepGeom g = sweep_geom(M, C, nblk);
+    SGX_LAUNCH((sweep_kernel<F, NQ, ROWS>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, f, g, partials);
     SGX_CHECK_LAUNCH(what);
     return SGX_OK;
 }
@@ -117,16 +127,16 @@ struct StatsF {
     __device__ In load(long r, int c) const { return In{sgx_ld4(x + r * ld + c)}; }
     struct Cst {};
     __device__ Cst consts(int) const { return Cst{}; }
-    __device__ void apply(long, int, const In& in, const Cst&, float4& q0, float4& q1) const {
+    __device__ void apply(long, int, const In& in, const Cst&, float4 (&q)[2]) const {
         const float4 v = in.v;
-        q0.x += v.x; q0.y += v.y; q0.z += v.z; q0.w += v.w;
-        q1.x += v.x * v.x; q1.y += v.y * v.y; q1.z += v.z * v.z; q1.w += v.w * v.w;
+        q[0].x += v.x; q[0].y += v.y; q[0].z += v.z; q[0].w += v.w;
+        q[1].x += v.x * v.x; q[1].y += v.y * v.y; q[1].z += v.z * v.z; q[1].w += v.w * v.w;
     }
 };
 extern "C" int32_t sgx_channel_stats_partial(const float* x, int64_t M, int32_t C, int64_t ld, float* partials, void* stream) {
     SGX_CHECK_ARG(x && partials, "channel_stats: null pointer");
     StatsF f{x, ld};
-    return run_sweep<StatsF, 2>(f, M, C, partials, stream, "channel_stats");
+    return run_sweep<StatsF, 2, 4>(f, M, C, partials, stream, "channel_stats");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -418,7 +428,7 @@ struct AffineActF {
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         return Cst{scale ? sgx_ld4(scale + c) : z, scale ? sgx_ld4(shift + c) : z, (r1 && a1_dev) ? a1_dev[0] : a1};
     }
-    __device__ void apply(long r, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&q)[2]) const {
         float4 v = in.v;
         if (scale) {
             const float4 s = k.s, t = k.t;
@@ -433,8 +443,8 @@ struct AffineActF {
             const float4 u = in.u2;
             v.x += a2 * u.x; v.y += a2 * u.y; v.z += a2 * u.z; v.w += a2 * u.w;
         }
-        q0.x += v.x; q0.y += v.y; q0.z += v.z; q0.w += v.w;
-        q1.x += v.x * v.x; q1.y += v.y * v.y; q1.z += v.z * v.z; q1.w += v.w * v.w;
+        q[0].x += v.x; q[0].y += v.y; q[0].z += v.z; q[0].w += v.w;
+        q[1].x += v.x * v.x; q[1].y += v.y * v.y; q[1].z += v.z * v.z; q[1].w += v.w * v.w;
         float4 o = make_float4(sgx_act6(v.x, act), sgx_act6(v.y, act), sgx_act6(v.z, act), sgx_act6(v.w, act));
         sgx_st4(y + r * y_ld + c, o);
     }
@@ -446,7 +456,7 @@ extern "C" int32_t sgx_affine_act_fwd(const float* x, int64_t x_ld, const float*
     SGX_CHECK_ACT4(act, "affine_act");
     SGX_CHECK_ARG((scale == nullptr) == (shift == nullptr), "affine_act: scale and shift go together");
     AffineActF f{x, x_ld, scale, shift, r1, r1_ld, a1, a1_dev, r2, r2_ld, a2, y, y_ld, act};
-    return run_sweep<AffineActF, 2>(f, M, C, partials, stream, "affine_act");
+    return run_sweep<AffineActF, 2, 4>(f, M, C, partials, stream, "affine_act");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -459,14 +469,14 @@ struct BnBwdReduceF {
     __device__ In load(long r, int c) const { return In{sgx_ld4(dy + r * dy_ld + c), sgx_ld4(x + r * x_ld + c)}; }
     struct Cst { float4 s, t, mu; };
     __device__ Cst consts(int c) const { return Cst{sgx_ld4(scale + c), sgx_ld4(shift + c), sgx_ld4(mean + c)}; }
-    __device__ void apply(long, int, const In& in, const Cst& k, float4& q0, float4& q1) const {
+    __device__ void apply(long, int, const In& in, const Cst& k, float4 (&q)[2]) const {
         const float4 d = in.d, v = in.v;
         const float4 s = k.s, t = k.t, mu = k.mu;
         float gx = bn_masked(d.x, v.x, s.x, t.x, act), gy = bn_masked(d.y, v.y, s.y, t.y, act);
         float gz = bn_masked(d.z, v.z, s.z, t.z, act), gw = bn_masked(d.w, v.w, s.w, t.w, act);
-        q0.x += gx; q0.y += gy; q0.z += gz; q0.w += gw;
+        q[0].x += gx; q[0].y += gy; q[0].z += gz; q[0].w += gw;
         // centred second moment: sum g*(x - mean) (no large-term cancellation later, cf. ATen's batch_norm backward)
-        q1.x += gx * (v.x - mu.x); q1.y += gy * (v.y - mu.y); q1.z += gz * (v.z - mu.z); q1.w += gw * (v.w - mu.w);
+        q[1].x += gx * (v.x - mu.x); q[1].y += gy * (v.y - mu.y); q[1].z += gz * (v.z - mu.z); q[1].w += gw * (v.w - mu.w);
     }
 };
 extern "C" int32_t sgx_bn_bwd_reduce(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
@@ -474,7 +484,7 @@ extern "C" int32_t sgx_bn_bwd_reduce(const float* dy, int64_t dy_ld, const float
     SGX_CHECK_ARG(dy && x && scale && shift && save_mean && partials, "bn_bwd_reduce: null pointer");
     SGX_CHECK_ACT4(act, "bn_bwd_reduce");
     BnBwdReduceF f{dy, dy_ld, x, x_ld, scale, shift, save_mean, act};
-    return run_sweep<BnBwdReduceF, 2>(f, M, C, partials, stream, "bn_bwd_reduce");
+    return run_sweep<BnBwdReduceF, 2, 4>(f, M, C, partials, stream, "bn_bwd_reduce");
 }
 
 // src: the sums that define dx (all ranks' when BatchNorm is synchronised); loc: this rank's own sums, which is what dgamma / dbeta
@@ -538,8 +548,7 @@ struct BnBwdApplyF {
         return Cst{sgx_ld4(scale + c), sgx_ld4(shift + c), sgx_ld4(coef + c), sgx_ld4(coef + C + c), sgx_ld4(coef + 2 * C + c), sgx_ld4(coef + 3 * C + c),
                    sgx_ld4(coef + 4 * C + c)};
     }
-    __device__ void apply(long r, int c, const In& in, const Cst& kc, float4& q0, float4& q1) const {
-        (void)q0; (void)q1;
+    __device__ void apply(long r, int c, const In& in, const Cst& kc, float4 (&)[1]) const {
         const float4 d = in.d, v = in.v;
         const float4 s = kc.s, t = kc.t;
         const float4 c1 = kc.c1, mg = kc.mg, k = kc.k, mu = kc.mu, ml = kc.ml;
@@ -557,7 +566,7 @@ extern "C" int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float*
     SGX_CHECK_ARG(dy && x && scale && shift && coef && dx, "bn_bwd_apply: null pointer");
     SGX_CHECK_ACT4(act, "bn_bwd_apply");
     BnBwdApplyF f{dy, dy_ld, x, x_ld, scale, shift, coef, C, dx, dx_ld, g_out, g_ld, act};
-    return run_sweep<BnBwdApplyF, 0>(f, M, C, nullptr, stream, "bn_bwd_apply");
+    return run_sweep<BnBwdApplyF, 0, 4>(f, M, C, nullptr, stream, "bn_bwd_apply");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -566,7 +575,6 @@ extern "C" int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float*
 // errors it dropped), the workgroup folds its 256 (sum, error) pairs in fp64 into ONE value, and a single-workgroup second stage adds the
 // <= 6 144 workgroup values in fp64 in a fixed order (deterministic; the earlier form summed 2 x nblk x C fp32 partials with one workgroup:
 // 68 us per call at 160x160x96, r2k).
-template <int DUMMY>
 __global__ __launch_bounds__(SW_THREADS) void dot_kernel(const float* a, long a_ld, const float* b, long b_ld, SweepGeom g, double* out) {
     __shared__ double red[SW_THREADS];
     const int tid = threadIdx.x;
@@ -627,7 +635,7 @@ extern "C" int32_t sgx_dot(const float* a, int64_t a_ld, const float* b, int64_t
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "dot: need M>0 and C%%4==0 (C=%d)", C);
     if (ws_bytes < sgx_dot_workspace(M, C)) SGX_FAIL(SGX_ERR_WORKSPACE, "dot: workspace too small (sgx_dot_workspace)");
     SweepGeom g = sweep_geom(M, C);
-    SGX_LAUNCH((dot_kernel<0>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, a, (long)a_ld, b, (long)b_ld, g, (double*)ws);
+    SGX_LAUNCH(dot_kernel, dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, a, (long)a_ld, b, (long)b_ld, g, (double*)ws);
     SGX_CHECK_LAUNCH("dot");
     SGX_LAUNCH(dot_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, g.nblk * g.ctiles, scale, out, accumulate);
     SGX_CHECK_LAUNCH("dot_final");
@@ -642,8 +650,7 @@ struct AxpyF {
     }
     struct Cst { float s; };
     __device__ Cst consts(int) const { return Cst{a_dev ? a_dev[0] : a}; }
-    __device__ void apply(long r, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
-        (void)q0; (void)q1;
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&)[1]) const {
         const float s = k.s;
         const float4 v = in.v;
         float4 o = make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
@@ -658,7 +665,7 @@ extern "C" int32_t sgx_axpy(const float* x, int64_t x_ld, float a, const float* 
                             int32_t accumulate, void* stream) {
     SGX_CHECK_ARG(x && y, "axpy: null pointer");
     AxpyF f{x, x_ld, a, a_dev, y, y_ld, accumulate};
-    return run_sweep<AxpyF, 0>(f, M, C, nullptr, stream, "axpy");
+    return run_sweep<AxpyF, 0, 4>(f, M, C, nullptr, stream, "axpy");
 }
 
 // g = dy where the (post-activation) output y is positive: backward of a ReLU that sits AFTER a residual add
@@ -669,8 +676,7 @@ struct ReluBwdF {
     __device__ In load(long r, int c) const { return In{sgx_ld4(dy + r * dy_ld + c), sgx_ld4(y + r * y_ld + c)}; }
     struct Cst {};
     __device__ Cst consts(int) const { return Cst{}; }
-    __device__ void apply(long r, int c, const In& in, const Cst&, float4& q0, float4& q1) const {
-        (void)q0; (void)q1;
+    __device__ void apply(long r, int c, const In& in, const Cst&, float4 (&)[1]) const {
         const float4 d = in.d, v = in.v;
         sgx_st4(g + r * g_ld + c, make_float4(v.x > 0.f ? d.x : 0.f, v.y > 0.f ? d.y : 0.f, v.z > 0.f ? d.z : 0.f, v.w > 0.f ? d.w : 0.f));
     }
@@ -679,7 +685,7 @@ extern "C" int32_t sgx_relu_bwd(const float* dy, int64_t dy_ld, const float* y, 
                                 void* stream) {
     SGX_CHECK_ARG(dy && y && g, "relu_bwd: null pointer");
     ReluBwdF f{dy, dy_ld, y, y_ld, g, g_ld};
-    return run_sweep<ReluBwdF, 0>(f, M, C, nullptr, stream, "relu_bwd");
+    return run_sweep<ReluBwdF, 0, 4>(f, M, C, nullptr, stream, "relu_bwd");
 }
 
 // The same mask AND the BatchNorm-backward reduce of the layer underneath in one sweep (round 6): out = relu(bn(conv) + shortcut) hands
@@ -691,97 +697,19 @@ struct ReluBwdBnReduceF {
     __device__ In load(long r, int c) const { return In{sgx_ld4(dy + r * dy_ld + c), sgx_ld4(y + r * y_ld + c), sgx_ld4(x + r * x_ld + c)}; }
     struct Cst { float4 mu; };
     __device__ Cst consts(int c) const { return Cst{sgx_ld4(mean + c)}; }
-    __device__ void apply(long r, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&q)[2]) const {
         const float4 d = in.d, v = in.v, u = in.u, mu = k.mu;
         const float4 o = make_float4(v.x > 0.f ? d.x : 0.f, v.y > 0.f ? d.y : 0.f, v.z > 0.f ? d.z : 0.f, v.w > 0.f ? d.w : 0.f);
         sgx_st4(g + r * g_ld + c, o);
-        q0.x += o.x; q0.y += o.y; q0.z += o.z; q0.w += o.w;
-        q1.x += o.x * (u.x - mu.x); q1.y += o.y * (u.y - mu.y); q1.z += o.z * (u.z - mu.z); q1.w += o.w * (u.w - mu.w);
+        q[0].x += o.x; q[0].y += o.y; q[0].z += o.z; q[0].w += o.w;
+        q[1].x += o.x * (u.x - mu.x); q[1].y += o.y * (u.y - mu.y); q[1].z += o.z * (u.z - mu.z); q[1].w += o.w * (u.w - mu.w);
     }
 };
 extern "C" int32_t sgx_relu_bwd_bn_reduce(const float* dy, int64_t dy_ld, const float* y, int64_t y_ld, const float* x, int64_t x_ld,
                                           const float* save_mean, float* g, int64_t g_ld, int64_t M, int32_t C, float* partials, void* stream) {
     SGX_CHECK_ARG(dy && y && x && save_mean && g && partials, "relu_bwd_bn_reduce: null pointer");
     ReluBwdBnReduceF f{dy, dy_ld, y, y_ld, x, x_ld, save_mean, g, g_ld};
-    return run_sweep<ReluBwdBnReduceF, 2>(f, M, C, partials, stream, "relu_bwd_bn_reduce");
-}
-
-// RepVGG-style two-branch BatchNorm sum + activation (+ post-activation residual) in one sweep, and the gradient through the
-// activation (the pre-activation is recomputed from the two saved conv outputs; nothing else is stored).
-struct DualAffineF {
-    const float* x1; long x1_ld; const float* s1; const float* t1;
-    const float* x2; long x2_ld; const float* s2; const float* t2;
-    const float* r; long r_ld; float* y; long y_ld; int act;
-    float r_scale; const float* r_scale_dev;  // post-activation residual: y = act(..) + r_scale * r_scale_dev[0] * r
-    struct In { float4 a, b, u; };
-    __device__ In load(long row, int c) const {
-        In in;
-        in.a = sgx_ld4(x1 + row * x1_ld + c);
-        in.b = x2 ? sgx_ld4(x2 + row * x2_ld + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        in.u = r ? sgx_ld4(r + row * r_ld + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        return in;
-    }
-    struct Cst { float4 s, t, p, q; float sc; };
-    __device__ Cst consts(int c) const {
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        return Cst{sgx_ld4(s1 + c), sgx_ld4(t1 + c), x2 ? sgx_ld4(s2 + c) : z, x2 ? sgx_ld4(t2 + c) : z, r_scale * ((r && r_scale_dev) ? r_scale_dev[0] : 1.f)};
-    }
-    __device__ float4 pre(const Cst& k, const float4& a, const float4& b) const {
-        const float4 s = k.s, t = k.t;
-        float4 v = make_float4(s.x * a.x + t.x, s.y * a.y + t.y, s.z * a.z + t.z, s.w * a.w + t.w);
-        if (x2) {
-            const float4 p = k.p, q = k.q;
-            v.x += p.x * b.x + q.x; v.y += p.y * b.y + q.y; v.z += p.z * b.z + q.z; v.w += p.w * b.w + q.w;
-        }
-        return v;
-    }
-    __device__ void apply(long row, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
-        (void)q0; (void)q1;
-        float4 v = pre(k, in.a, in.b);
-        float4 o = make_float4(sgx_act(v.x, act), sgx_act(v.y, act), sgx_act(v.z, act), sgx_act(v.w, act));
-        if (r) {
-            const float sc = k.sc;
-            o.x += sc * in.u.x; o.y += sc * in.u.y; o.z += sc * in.u.z; o.w += sc * in.u.w;
-        }
-        sgx_st4(y + row * y_ld + c, o);
-    }
-};
-extern "C" int32_t sgx_dual_affine_act_fwd(const float* x1, int64_t x1_ld, const float* s1, const float* t1, const float* x2, int64_t x2_ld,
-                                           const float* s2, const float* t2, const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev,
-                                           float* y, int64_t y_ld, int64_t M, int32_t C, int32_t act, void* stream) {
-    SGX_CHECK_ARG(x1 && s1 && t1 && y, "dual_affine_act_fwd: null pointer");
-    SGX_CHECK_ACT3(act, "dual_affine_act_fwd");
-    SGX_CHECK_ARG(!x2 || (s2 && t2), "dual_affine_act_fwd: second branch needs scale and shift");
-    DualAffineF f{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, r, r_ld, y, y_ld, act, r_scale, r_scale_dev};
-    return run_sweep<DualAffineF, 0>(f, M, C, nullptr, stream, "dual_affine_act_fwd");
-}
-struct DualAffineBwdF {
-    DualAffineF p; const float* dy; long dy_ld; float* g; long g_ld;
-    struct In { float4 a, b, d; };
-    __device__ In load(long row, int c) const {
-        In in;
-        in.a = sgx_ld4(p.x1 + row * p.x1_ld + c);
-        in.b = p.x2 ? sgx_ld4(p.x2 + row * p.x2_ld + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        in.d = sgx_ld4(dy + row * dy_ld + c);
-        return in;
-    }
-    typedef DualAffineF::Cst Cst;
-    __device__ Cst consts(int c) const { return p.consts(c); }
-    __device__ void apply(long row, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
-        (void)q0; (void)q1;
-        float4 v = p.pre(k, in.a, in.b);
-        sgx_st4(g + row * g_ld + c, make_float4(in.d.x * sgx_act_grad(v.x, p.act), in.d.y * sgx_act_grad(v.y, p.act),
-                                                 in.d.z * sgx_act_grad(v.z, p.act), in.d.w * sgx_act_grad(v.w, p.act)));
-    }
-};
-extern "C" int32_t sgx_dual_affine_act_bwd(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
-                                           const float* x2, int64_t x2_ld, const float* s2, const float* t2, float* g, int64_t g_ld, int64_t M,
-                                           int32_t C, int32_t act, void* stream) {
-    SGX_CHECK_ARG(dy && x1 && s1 && t1 && g, "dual_affine_act_bwd: null pointer");
-    SGX_CHECK_ACT3(act, "dual_affine_act_bwd");
-    SGX_CHECK_ARG(!x2 || (s2 && t2), "dual_affine_act_bwd: second branch needs scale and shift");
-    DualAffineBwdF f{DualAffineF{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, nullptr, 0, nullptr, 0, act, 1.f, nullptr}, dy, dy_ld, g, g_ld};
-    return run_sweep<DualAffineBwdF, 0>(f, M, C, nullptr, stream, "dual_affine_act_bwd");
+    return run_sweep<ReluBwdBnReduceF, 2, 4>(f, M, C, partials, stream, "relu_bwd_bn_reduce");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -790,62 +718,17 @@ extern "C" int32_t sgx_dual_affine_act_bwd(const float* dy, int64_t dy_ld, const
 //     s = bn3(y) + u          out = act(post_bn(s))
 // Both BatchNorms are finalised from the FIVE per-channel moments the convolution epilogue leaves (sum y, y^2, u0, u0^2, y*u0, u0 = u - b1):
 // s is an affine function of (y, u) per channel, so mean / variance of s follow from the moments of (y, u) - no pass over s for its
-// statistics, and s itself is never written: the forward is ONE sweep, out = act(a*y + scp*u + c) (sgx_dual_affine_act_fwd with the
+// statistics, and s itself is never written: the forward is ONE sweep, out = act(a*y + scp*u + c) (sgx_tri_affine_act_fwd with the
 // coefficient rows cf), instead of two sweeps and a residual read.  Backward: ONE reduce sweep (4 sums) + ONE apply sweep that writes the
 // upstream gradients of BOTH convolutions, instead of two reduce and two apply sweeps:
 //     g = dout * act'(z),  ds = cp * ((g - mean g) - shat * mean(g * shat)),  dy = c3 * (ds - mean ds - yhat * mean(ds * yhat))
 // with mean ds = 0 (a BatchNorm's input gradient sums to zero per channel) and mean(ds * yhat) = cp * (mean(g * yhat) - mean(g * shat) *
 // mean(shat * yhat)): every mean comes out of the one reduce sweep.  Reference arithmetic: modules/qarepvgg_block.py:184-204.
 // ---------------------------------------------------------------------------------------------
-template <typename F, int NQ>
-__global__ __launch_bounds__(SW_THREADS) void sweepq_kernel(F f, SweepGeom g, float* partials) {
-    __shared__ float4 red[NQ][SW_THREADS];
-    const int tid = threadIdx.x;
-    const int cg = tid % g.CG, rl = tid / g.CG;
-    const int c4 = blockIdx.y * g.CG + cg;
-    const bool live = (rl < g.RL) && (c4 < g.C4);
-    const int c = c4 * 4;
-    float4 q[NQ];
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) {
-        long r0 = (long)blockIdx.x * g.rows_per_blk;
-        long r1 = r0 + g.rows_per_blk;
-        if (r1 > g.M) r1 = g.M;
-        long r = r0 + rl;
-        const long st = g.RL;
-        const typename F::Cst k = f.consts(c);
-        for (; r + st < r1; r += 2 * st) {  // three tensors per row: two rows of loads in flight per lane
-            typename F::In i0 = f.load(r, c), i1 = f.load(r + st, c);
-            f.apply(r, c, i0, k, q);
-            f.apply(r + st, c, i1, k, q);
-        }
-        for (; r < r1; r += st) {
-            typename F::In i0 = f.load(r, c);
-            f.apply(r, c, i0, k, q);
-        }
-    }
-    if (!partials) return;  // no reduction (apply sweeps): uniform across the workgroup
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) red[k][tid] = q[k];
-    __syncthreads();
-    if (live && rl == 0) {
-#pragma unroll
-        for (int k = 0; k < NQ; ++k) {
-            double t[4] = {0.0, 0.0, 0.0, 0.0};  // (lane sums meet in double: see sweep_kernel)
-            for (int j = 0; j < g.RL; ++j) {
-                const float4 a = red[k][j * g.CG + cg];
-                t[0] += a.x; t[1] += a.y; t[2] += a.z; t[3] += a.w;
-            }
-            sgx_st4(partials + ((long)k * g.nblk + blockIdx.x) * g.C + c, make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]));
-        }
-    }
-}
-
 extern "C" int64_t sgx_qarep_workspace(int32_t nblk, int32_t C) { return (int64_t)5 * cr_slices(nblk) * C * (int64_t)sizeof(double) + 256; }
 
 // sv rows: 0 mean3, 1 invstd3, 2 scale3, 3 shift3, 4 mean_s, 5 invstd_p, 6 scale_p, 7 shift_p;  cf rows: 0 a = scale_p * scale3, 1 c = scale_p * shift3 +
-// shift_p, 2 scale_p, 3 zeros  (out = act(cf0 * y + cf1 + cf2 * u + cf3): the operand rows of sgx_dual_affine_act_fwd)
+// shift_p, 2 scale_p, 3 zeros  (out = act(cf0 * y + cf1 + cf2 * u + cf3): the operand rows of sgx_tri_affine_act_fwd)
 __global__ void qarep_fwd_finalize_kernel(ColSrc src, long M, int C, const float* bias1, const float* g3, const float* b3, float eps3, float mom3,
                                           float* rm3, float* rv3, const float* gp, const float* bp, float epsp, float momp, float* rmp, float* rvp,
                                           float* cf, float* sv) {
@@ -939,12 +822,8 @@ extern "C" int32_t sgx_qarep_bwd_reduce(const float* dout, int64_t d_ld, const f
                                         const float* sv, int64_t M, int32_t C, int32_t act, float* partials4, void* stream) {
     SGX_CHECK_ARG(dout && y && u && cf && sv && partials4, "qarep_bwd_reduce: null pointer");
     SGX_CHECK_ACT3(act, "qarep_bwd_reduce");
-    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "qarep_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
     QarepBwdReduceF f{QarepBwdBase{dout, d_ld, y, y_ld, u, u_ld, cf, sv, C, act}};
-    SweepGeom g = sweep_geom(M, C);
-    SGX_LAUNCH((sweepq_kernel<QarepBwdReduceF, 4>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, f, g, partials4);
-    SGX_CHECK_LAUNCH("qarep_bwd_reduce");
-    return SGX_OK;
+    return run_sweep<QarepBwdReduceF, 4, 2>(f, M, C, partials4, stream, "qarep_bwd_reduce");  // (three tensors per row: two rows in flight)
 }
 // cb rows: 0 cp = gamma_p * invstd_p, 1 mean g, 2 kp = invstd_p^2 * mean(g * (s - mean_s)), 3 c3 = gamma3 * invstd3, 4 k3 = invstd3^2 * mean(ds * (y - mean3))
 __global__ void qarep_bwd_finalize_kernel(ColSrc src, long M, int C, const float* gamma3, const float* gammap, const float* sv, float* dgamma3,
@@ -1011,103 +890,97 @@ extern "C" int32_t sgx_qarep_bwd_apply(const float* dout, int64_t d_ld, const fl
                                        int32_t act, void* stream) {
     SGX_CHECK_ARG(dout && y && u && cf && sv && cb && ds && dy, "qarep_bwd_apply: null pointer");
     SGX_CHECK_ACT3(act, "qarep_bwd_apply");
-    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "qarep_bwd_apply: need M>0 and C%%4==0 (C=%d)", C);
     QarepBwdApplyF f{QarepBwdBase{dout, d_ld, y, y_ld, u, u_ld, cf, sv, C, act}, cb, ds, ds_ld, dy, dy_ld};
-    SweepGeom g = sweep_geom(M, C);
-    SGX_LAUNCH((sweepq_kernel<QarepBwdApplyF, 1>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, f, g, (float*)nullptr);
-    SGX_CHECK_LAUNCH("qarep_bwd_apply");
-    return SGX_OK;
+    return run_sweep<QarepBwdApplyF, 0, 2>(f, M, C, nullptr, stream, "qarep_bwd_apply");
 }
 
-// RepVGG two-branch block, backward through the activation AND the reduce of both BatchNorm backward passes in one sweep (round 5):
-//   g = dy * act'(s1*x1 + t1 + s2*x2 + t2)   (written: both BatchNorm backward applies read it),
-//   partials [4][blocks][C] = sum g, sum g (x1 - mean1), sum g, sum g (x2 - mean2)   - i.e. the two [2][blocks][C] row sets sgx_bn_bwd_reduce
-// would have produced for (g, x1) and (g, x2) with two more passes over g and the saved conv outputs (modules/repvgg_block.py:94-104:
-// PP-YOLOE runs ~30 such blocks per step).  The sums are taken from the SAME g values that are stored.
-struct DualAffineBwdReduceF {
-    DualAffineF p; const float* dy; long dy_ld; float* g; long g_ld; const float* mean1; const float* mean2;
-    struct In { float4 a, b, d; };
-    struct Cst { DualAffineF::Cst k; float4 m1, m2; };
-    __device__ In load(long row, int c) const {
-        return In{sgx_ld4(p.x1 + row * p.x1_ld + c), sgx_ld4(p.x2 + row * p.x2_ld + c), sgx_ld4(dy + row * dy_ld + c)};
-    }
-    __device__ Cst consts(int c) const { return Cst{p.consts(c), sgx_ld4(mean1 + c), sgx_ld4(mean2 + c)}; }
-    __device__ void apply(long row, int c, const In& in, const Cst& k, float4 (&q)[4]) const {
-        const float4 v = p.pre(k.k, in.a, in.b);
-        const float4 o = make_float4(in.d.x * sgx_act_grad(v.x, p.act), in.d.y * sgx_act_grad(v.y, p.act), in.d.z * sgx_act_grad(v.z, p.act),
-                                     in.d.w * sgx_act_grad(v.w, p.act));
-        sgx_st4(g + row * g_ld + c, o);
-        q[0].x += o.x; q[0].y += o.y; q[0].z += o.z; q[0].w += o.w;
-        q[1].x += o.x * (in.a.x - k.m1.x); q[1].y += o.y * (in.a.y - k.m1.y); q[1].z += o.z * (in.a.z - k.m1.z); q[1].w += o.w * (in.a.w - k.m1.w);
-        q[2].x += o.x; q[2].y += o.y; q[2].z += o.z; q[2].w += o.w;
-        q[3].x += o.x * (in.b.x - k.m2.x); q[3].y += o.y * (in.b.y - k.m2.y); q[3].z += o.z * (in.b.z - k.m2.z); q[3].w += o.w * (in.b.w - k.m2.w);
-    }
+// RepVGG-style branch sum: the BatchNorms of one to three tensors added, the activation, and a post-activation residual in ONE sweep
+//   y = act(s1*x1 + t1 [+ s2*x2 + t2] [+ s3*x3 + t3]) [+ r_scale * r_scale_dev[0] * r]
+// (two branches: RepVGGBlock's 3x3 + 1x1 and the QARepVGG forward with its coefficient rows; three: x3 = the block's own input, the
+// identity BatchNorm branch of the classifiers' blocks, modules/repvgg_block.py:94-103 of the reference; one: a BatchNorm + activation with
+// the residual added AFTER the activation), and its backward through the activation, which recomputes the pre-activation from the saved
+// conv outputs (nothing else is stored).  One functor each, the branch count a template parameter: a sweep carries the registers of the
+// operands it has and no others.  The pre-activation is the same statements in the same order for every count - v = s1*a + t1;
+// v += s2*b + t2; v += s3*e + t3 - so a null branch and a branch with zero scale and shift give the same bits (x + 0.0 is exact).
+struct Branch {
+    const float* x; long ld; const float* s; const float* t; const float* mean;  // (mean: the backward's, else null)
 };
-extern "C" int32_t sgx_dual_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
-                                                  const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2,
-                                                  const float* mean2, float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials4,
-                                                  void* stream) {
-    SGX_CHECK_ARG(dy && x1 && s1 && t1 && mean1 && x2 && s2 && t2 && mean2 && g && partials4, "dual_affine_act_bwd_reduce: null pointer");
-    SGX_CHECK_ACT3(act, "dual_affine_act_bwd_reduce");
-    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "dual_affine_act_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
-    DualAffineBwdReduceF f{DualAffineF{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, nullptr, 0, nullptr, 0, act, 1.f, nullptr}, dy, dy_ld, g, g_ld, mean1, mean2};
-    SweepGeom gm = sweep_geom(M, C);
-    SGX_LAUNCH((sweepq_kernel<DualAffineBwdReduceF, 4>), dim3(gm.nblk, gm.ctiles), dim3(SW_THREADS), 0, stream, f, gm, partials4);
-    SGX_CHECK_LAUNCH("dual_affine_act_bwd_reduce");
-    return SGX_OK;
-}
-
-// RepVGG three-branch block (the classifiers' blocks with in == out, stride 1: modules/repvgg_block.py:94-103 of the reference):
-//   y = act(s1*x1 + t1 [+ s2*x2 + t2] [+ s3*x3 + t3]) [+ r_scale * r]      x3 = the block's own input (identity BatchNorm branch)
-// in ONE sweep, which on request also leaves the per-channel sum y, sum y^2 partial rows of the value it STORES ([2][nblk][C], the layout
-// of sgx_affine_act_fwd's): the next block's identity BatchNorm normalises exactly this tensor, so no statistics pass over it runs.
-// The first two branches are DualAffineF's arithmetic, statement for statement: a null third branch gives its result bit for bit.
-// nblk: the number of row blocks (0: sgx_stats_blocks(M)) - the stored values do not depend on it, the partial rows' count does.
-static SweepGeom sweep_geom_rows(long M, int C, int nblk) {
-    SweepGeom g = sweep_geom(M, C);
-    if (nblk > 0) {
-        g.nblk = nblk;
-        g.rows_per_blk = (int)((M + g.nblk - 1) / g.nblk);
-    }
-    return g;
-}
-struct TriAffineF {
-    DualAffineF p; const float* x3; long x3_ld; const float* s3; const float* t3;
-    struct In { float4 a, b, e, u; };
-    struct Cst { DualAffineF::Cst k; float4 s, t; };
-    __device__ In load(long row, int c) const {
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        In in;
-        in.a = sgx_ld4(p.x1 + row * p.x1_ld + c);
-        in.b = p.x2 ? sgx_ld4(p.x2 + row * p.x2_ld + c) : z;
-        in.e = x3 ? sgx_ld4(x3 + row * x3_ld + c) : z;
-        in.u = p.r ? sgx_ld4(p.r + row * p.r_ld + c) : z;
-        return in;
+template <int NB>
+struct BranchSum {
+    Branch b[NB]; int act;
+    struct Cst { float4 s[NB], t[NB]; };
+    __device__ void load(long row, int c, float4 (&x)[NB]) const {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) x[i] = sgx_ld4(b[i].x + row * b[i].ld + c);
     }
     __device__ Cst consts(int c) const {
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        return Cst{p.consts(c), x3 ? sgx_ld4(s3 + c) : z, x3 ? sgx_ld4(t3 + c) : z};
+        Cst k;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) k.s[i] = sgx_ld4(b[i].s + c), k.t[i] = sgx_ld4(b[i].t + c);
+        return k;
     }
-    __device__ float4 pre(const Cst& k, const float4& a, const float4& b, const float4& e) const {
-        float4 v = p.pre(k.k, a, b);
-        if (x3) {
-            const float4 s = k.s, t = k.t;
+    __device__ float4 pre(const Cst& k, const float4 (&x)[NB]) const {
+        float4 v = make_float4(k.s[0].x * x[0].x + k.t[0].x, k.s[0].y * x[0].y + k.t[0].y, k.s[0].z * x[0].z + k.t[0].z, k.s[0].w * x[0].w + k.t[0].w);
+#pragma unroll
+        for (int i = 1; i < NB; ++i) {
+            const float4 s = k.s[i], t = k.t[i], e = x[i];
             v.x += s.x * e.x + t.x; v.y += s.y * e.y + t.y; v.z += s.z * e.z + t.z; v.w += s.w * e.w + t.w;
         }
         return v;
     }
-    __device__ void apply(long row, int c, const In& in, const Cst& k, float4& q0, float4& q1) const {
-        float4 v = pre(k, in.a, in.b, in.e);
-        float4 o = make_float4(sgx_act(v.x, p.act), sgx_act(v.y, p.act), sgx_act(v.z, p.act), sgx_act(v.w, p.act));
-        if (p.r) {
-            const float sc = k.k.sc;
-            o.x += sc * in.u.x; o.y += sc * in.u.y; o.z += sc * in.u.z; o.w += sc * in.u.w;
+};
+// the branches that are present moved to the front, in order -> their count
+static int present(Branch (&br)[3]) {
+    int nb = 0;
+    for (int i = 0; i < 3; ++i)
+        if (br[i].x) br[nb++] = br[i];
+    return nb;
+}
+template <int NB>
+static BranchSum<NB> branch_sum(const Branch* br, int act) {
+    BranchSum<NB> p;
+    for (int i = 0; i < NB; ++i) p.b[i] = br[i];
+    p.act = act;
+    return p;
+}
+
+// Forward.  STATS: also the per-channel sum y, sum y^2 partial rows of the value it STORES ([2][nblk][C], the layout of sgx_affine_act_fwd's):
+// the next block's identity BatchNorm normalises exactly this tensor, so no statistics pass over it runs.
+struct BranchSumOut {
+    const float* r; long r_ld; float r_scale; const float* r_scale_dev; float* y; long y_ld;
+};
+template <int NB, bool STATS>
+struct BranchSumFwdF {
+    BranchSum<NB> p; BranchSumOut o;
+    struct In { float4 x[NB], u; };
+    struct Cst { typename BranchSum<NB>::Cst k; float sc; };
+    __device__ In load(long row, int c) const {
+        In in;
+        p.load(row, c, in.x);
+        in.u = o.r ? sgx_ld4(o.r + row * o.r_ld + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        return in;
+    }
+    __device__ Cst consts(int c) const { return Cst{p.consts(c), o.r_scale * ((o.r && o.r_scale_dev) ? o.r_scale_dev[0] : 1.f)}; }
+    __device__ void apply(long row, int c, const In& in, const Cst& k, float4 (&q)[STATS ? 2 : 1]) const {
+        const float4 v = p.pre(k.k, in.x);
+        float4 y = make_float4(sgx_act(v.x, p.act), sgx_act(v.y, p.act), sgx_act(v.z, p.act), sgx_act(v.w, p.act));
+        if (o.r) {
+            const float sc = k.sc;
+            y.x += sc * in.u.x; y.y += sc * in.u.y; y.z += sc * in.u.z; y.w += sc * in.u.w;
         }
-        sgx_st4(p.y + row * p.y_ld + c, o);
-        q0.x += o.x; q0.y += o.y; q0.z += o.z; q0.w += o.w;
-        q1.x += o.x * o.x; q1.y += o.y * o.y; q1.z += o.z * o.z; q1.w += o.w * o.w;
+        sgx_st4(o.y + row * o.y_ld + c, y);
+        if constexpr (STATS) {
+            q[0].x += y.x; q[0].y += y.y; q[0].z += y.z; q[0].w += y.w;
+            q[1].x += y.x * y.x; q[1].y += y.y * y.y; q[1].z += y.z * y.z; q[1].w += y.w * y.w;
+        }
     }
 };
+template <int NB>
+static int32_t branch_sum_fwd(const Branch* br, int act, const BranchSumOut& o, long M, int C, float* partials, int nblk, void* stream) {
+    const BranchSum<NB> p = branch_sum<NB>(br, act);
+    if (partials) return run_sweep<BranchSumFwdF<NB, true>, 2, 4>({p, o}, M, C, partials, stream, "tri_affine_act_fwd", nblk);
+    return run_sweep<BranchSumFwdF<NB, false>, 0, 4>({p, o}, M, C, nullptr, stream, "tri_affine_act_fwd", nblk);
+}
 extern "C" int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const float* s1, const float* t1, const float* x2, int64_t x2_ld,
                                           const float* s2, const float* t2, const float* x3, int64_t x3_ld, const float* s3, const float* t3,
                                           const float* r, int64_t r_ld, float r_scale, const float* r_scale_dev, float* y, int64_t y_ld, int64_t M,
@@ -1116,67 +989,73 @@ extern "C" int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const 
     SGX_CHECK_ACT3(act, "tri_affine_act_fwd");
     SGX_CHECK_ARG(!x2 || (s2 && t2), "tri_affine_act_fwd: second branch needs scale and shift");
     SGX_CHECK_ARG(!x3 || (s3 && t3), "tri_affine_act_fwd: third branch needs scale and shift");
-    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "tri_affine_act_fwd: need M>0 and C%%4==0 (C=%d)", C);
-    SGX_CHECK_ARG(nblk >= 0 && nblk <= M, "tri_affine_act_fwd: row blocks %d outside 0..M", nblk);
-    TriAffineF f{DualAffineF{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, r, r_ld, y, y_ld, act, r_scale, r_scale_dev}, x3, x3_ld, s3, t3};
-    SweepGeom g = sweep_geom_rows(M, C, nblk);
-    SGX_LAUNCH((sweep_kernel<TriAffineF, 2>), dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, f, g, partials);
-    SGX_CHECK_LAUNCH("tri_affine_act_fwd");
-    return SGX_OK;
+    Branch br[3] = {{x1, x1_ld, s1, t1, nullptr}, {x2, x2_ld, s2, t2, nullptr}, {x3, x3_ld, s3, t3, nullptr}};
+    const int nb = present(br);
+    const BranchSumOut o{r, r_ld, r_scale, r_scale_dev, y, y_ld};
+    return nb == 1 ? branch_sum_fwd<1>(br, act, o, M, C, partials, nblk, stream)
+         : nb == 2 ? branch_sum_fwd<2>(br, act, o, M, C, partials, nblk, stream)
+                   : branch_sum_fwd<3>(br, act, o, M, C, partials, nblk, stream);
 }
 
-// Its backward through the activation AND the reduce rows of all three BatchNorm backward passes in one sweep:
-//   g = dy * act'(pre)   (written),   partials [6][nblk][C] = sum g, sum g (x1 - mean1), sum g, sum g (x2 - mean2), sum g, sum g (x3 - mean3)
-// - three [2][nblk][C] row sets as sgx_bn_bwd_reduce(g, x_i) (act = none) leaves them, bit for bit: the sums take the g values that are STORED,
-// so the product dy * act' is rounded before it is added (no contraction there: an fma would add the unrounded product, which is not the
-// stored g as soon as act' is not 0 or 1).  x3 NULL: DualAffineBwdReduceF itself runs - partials [4][nblk][C],
-// sgx_dual_affine_act_bwd_reduce's result bit for bit.
-struct TriAffineBwdReduceF {
-    TriAffineF p; const float* dy; long dy_ld; float* g; long g_ld; const float* mean1; const float* mean2; const float* mean3;
-    struct In { float4 a, b, e, d; };
-    struct Cst { TriAffineF::Cst k; float4 m1, m2, m3; };
+// Backward through the activation AND the reduce rows of every branch's BatchNorm backward in one sweep (round 5; PP-YOLOE runs ~30 such
+// blocks per step):   g = dy * act'(pre)   (written: the BatchNorm backward applies read it),
+//   partials [2 NB][nblk][C] = sum g, sum g (x_i - mean_i) for each branch that is present, in order
+// - one [2][nblk][C] row set per branch as sgx_bn_bwd_reduce(g, x_i) (act = none) leaves it, bit for bit, with no further pass over g and the
+// saved conv outputs.  The sums take the g values that are STORED, so the product dy * act' is rounded before it is added (no contraction
+// there: an fma would add the unrounded product, which is not the stored g as soon as act' is not 0 or 1).
+template <int NB>
+struct BranchSumBwdReduceF {
+    BranchSum<NB> p; const float* dy; long dy_ld; float* g; long g_ld;
+    struct In { float4 x[NB], d; };
+    struct Cst { typename BranchSum<NB>::Cst k; float4 m[NB]; };
     __device__ In load(long row, int c) const {
-        return In{sgx_ld4(p.p.x1 + row * p.p.x1_ld + c), sgx_ld4(p.p.x2 + row * p.p.x2_ld + c), sgx_ld4(p.x3 + row * p.x3_ld + c),
-                  sgx_ld4(dy + row * dy_ld + c)};
+        In in;
+        p.load(row, c, in.x);
+        in.d = sgx_ld4(dy + row * dy_ld + c);
+        return in;
     }
-    __device__ Cst consts(int c) const { return Cst{p.consts(c), sgx_ld4(mean1 + c), sgx_ld4(mean2 + c), sgx_ld4(mean3 + c)}; }
+    __device__ Cst consts(int c) const {
+        Cst k;
+        k.k = p.consts(c);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) k.m[i] = sgx_ld4(p.b[i].mean + c);
+        return k;
+    }
     __device__ float4 grad(const float4& d, const float4& v) const {
 #pragma clang fp contract(off)
-        return make_float4(d.x * sgx_act_grad(v.x, p.p.act), d.y * sgx_act_grad(v.y, p.p.act), d.z * sgx_act_grad(v.z, p.p.act),
-                           d.w * sgx_act_grad(v.w, p.p.act));
+        return make_float4(d.x * sgx_act_grad(v.x, p.act), d.y * sgx_act_grad(v.y, p.act), d.z * sgx_act_grad(v.z, p.act), d.w * sgx_act_grad(v.w, p.act));
     }
-    __device__ void apply(long row, int c, const In& in, const Cst& k, float4 (&q)[6]) const {
-        const float4 o = grad(in.d, p.pre(k.k, in.a, in.b, in.e));
+    __device__ void apply(long row, int c, const In& in, const Cst& k, float4 (&q)[2 * NB]) const {
+        const float4 o = grad(in.d, p.pre(k.k, in.x));
         sgx_st4(g + row * g_ld + c, o);
-        q[0].x += o.x; q[0].y += o.y; q[0].z += o.z; q[0].w += o.w;
-        q[1].x += o.x * (in.a.x - k.m1.x); q[1].y += o.y * (in.a.y - k.m1.y); q[1].z += o.z * (in.a.z - k.m1.z); q[1].w += o.w * (in.a.w - k.m1.w);
-        q[2].x += o.x; q[2].y += o.y; q[2].z += o.z; q[2].w += o.w;
-        q[3].x += o.x * (in.b.x - k.m2.x); q[3].y += o.y * (in.b.y - k.m2.y); q[3].z += o.z * (in.b.z - k.m2.z); q[3].w += o.w * (in.b.w - k.m2.w);
-        q[4].x += o.x; q[4].y += o.y; q[4].z += o.z; q[4].w += o.w;
-        q[5].x += o.x * (in.e.x - k.m3.x); q[5].y += o.y * (in.e.y - k.m3.y); q[5].z += o.z * (in.e.z - k.m3.z); q[5].w += o.w * (in.e.w - k.m3.w);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const float4 e = in.x[i], m = k.m[i];
+            q[2 * i].x += o.x; q[2 * i].y += o.y; q[2 * i].z += o.z; q[2 * i].w += o.w;
+            q[2 * i + 1].x += o.x * (e.x - m.x); q[2 * i + 1].y += o.y * (e.y - m.y); q[2 * i + 1].z += o.z * (e.z - m.z); q[2 * i + 1].w += o.w * (e.w - m.w);
+        }
     }
 };
+template <int NB>
+static int32_t branch_sum_bwd_reduce(const Branch* br, int act, const float* dy, long dy_ld, float* g, long g_ld, long M, int C, float* partials,
+                                     int nblk, void* stream) {
+    // (three tensors and up per row: two rows of loads in flight per lane)
+    return run_sweep<BranchSumBwdReduceF<NB>, 2 * NB, 2>({branch_sum<NB>(br, act), dy, dy_ld, g, g_ld}, M, C, partials, stream, "tri_affine_act_bwd_reduce", nblk);
+}
 extern "C" int32_t sgx_tri_affine_act_bwd_reduce(const float* dy, int64_t dy_ld, const float* x1, int64_t x1_ld, const float* s1, const float* t1,
                                                  const float* mean1, const float* x2, int64_t x2_ld, const float* s2, const float* t2,
                                                  const float* mean2, const float* x3, int64_t x3_ld, const float* s3, const float* t3,
                                                  const float* mean3, float* g, int64_t g_ld, int64_t M, int32_t C, int32_t act, float* partials,
                                                  int32_t nblk, void* stream) {
-    SGX_CHECK_ARG(dy && x1 && s1 && t1 && mean1 && x2 && s2 && t2 && mean2 && g && partials, "tri_affine_act_bwd_reduce: null pointer");
+    SGX_CHECK_ARG(dy && x1 && s1 && t1 && mean1 && g && partials, "tri_affine_act_bwd_reduce: null pointer");
     SGX_CHECK_ACT3(act, "tri_affine_act_bwd_reduce");
+    SGX_CHECK_ARG(!x2 || (s2 && t2 && mean2), "tri_affine_act_bwd_reduce: second branch needs scale, shift and mean");
     SGX_CHECK_ARG(!x3 || (s3 && t3 && mean3), "tri_affine_act_bwd_reduce: third branch needs scale, shift and mean");
-    SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "tri_affine_act_bwd_reduce: need M>0 and C%%4==0 (C=%d)", C);
-    SGX_CHECK_ARG(nblk >= 0 && nblk <= M, "tri_affine_act_bwd_reduce: row blocks %d outside 0..M", nblk);
-    const DualAffineF two{x1, x1_ld, s1, t1, x2, x2_ld, s2, t2, nullptr, 0, nullptr, 0, act, 1.f, nullptr};
-    SweepGeom gm = sweep_geom_rows(M, C, nblk);
-    if (x3) {
-        TriAffineBwdReduceF f{TriAffineF{two, x3, x3_ld, s3, t3}, dy, dy_ld, g, g_ld, mean1, mean2, mean3};
-        SGX_LAUNCH((sweepq_kernel<TriAffineBwdReduceF, 6>), dim3(gm.nblk, gm.ctiles), dim3(SW_THREADS), 0, stream, f, gm, partials);
-    } else {
-        DualAffineBwdReduceF f{two, dy, dy_ld, g, g_ld, mean1, mean2};
-        SGX_LAUNCH((sweepq_kernel<DualAffineBwdReduceF, 4>), dim3(gm.nblk, gm.ctiles), dim3(SW_THREADS), 0, stream, f, gm, partials);
-    }
-    SGX_CHECK_LAUNCH("tri_affine_act_bwd_reduce");
-    return SGX_OK;
+    Branch br[3] = {{x1, x1_ld, s1, t1, mean1}, {x2, x2_ld, s2, t2, mean2}, {x3, x3_ld, s3, t3, mean3}};
+    const int nb = present(br);
+    return nb == 1 ? branch_sum_bwd_reduce<1>(br, act, dy, dy_ld, g, g_ld, M, C, partials, nblk, stream)
+         : nb == 2 ? branch_sum_bwd_reduce<2>(br, act, dy, dy_ld, g, g_ld, M, C, partials, nblk, stream)
+                   : branch_sum_bwd_reduce<3>(br, act, dy, dy_ld, g, g_ld, M, C, partials, nblk, stream);
 }
 
 struct ColsumF {
@@ -1188,10 +1067,9 @@ struct ColsumF {
     }
     struct Cst {};
     __device__ Cst consts(int) const { return Cst{}; }
-    __device__ void apply(long, int, const In& in, const Cst&, float4& q0, float4& q1) const {
-        (void)q1;
+    __device__ void apply(long, int, const In& in, const Cst&, float4 (&q)[1]) const {
         const float4 v = in.v;
-        q0.x += v.x; q0.y += v.y; q0.z += v.z; q0.w += v.w;
+        q[0].x += v.x; q[0].y += v.y; q[0].z += v.z; q[0].w += v.w;
     }
 };
 __global__ void colsum_finalize_kernel(ColSrc src, int C, float* out, int accumulate) {
@@ -1211,7 +1089,7 @@ extern "C" int32_t sgx_colsum(const float* x, int64_t ld, int64_t M, int32_t C, 
                               int32_t accumulate, float* ws, void* stream) {
     SGX_CHECK_ARG(x && out && ws && rows_per_img > 0, "colsum: bad args");
     ColsumF f{x, ld, rows_per_img, ld_img};
-    int32_t rc = run_sweep<ColsumF, 1>(f, M, C, ws, stream, "colsum");
+    int32_t rc = run_sweep<ColsumF, 1, 4>(f, M, C, ws, stream, "colsum");
     if (rc) return rc;
     const int nblk = sgx_stats_blocks(M);
     const int64_t part_bytes = ((int64_t)nblk * C * (int64_t)sizeof(float) + 255) & ~255L;

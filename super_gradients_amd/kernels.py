@@ -884,49 +884,11 @@ def relu_bwd_bn_reduce(dy, y, x, save_mean):
     return g, parts
 
 
-def dual_affine_act(x1, s1, t1, x2=None, s2=None, t2=None, post_add=None, act=None, out=None, post_scale=None):
-    """y = act(s1*x1 + t1 [+ s2*x2 + t2]) [+ post_scale * post_add]   (RepVGG two-branch BatchNorm sum; post-activation residual;
-    post_scale: a float or a one-element device tensor, default 1)."""
-    ps_dev = post_scale if torch.is_tensor(post_scale) else None
-    ps = 1.0 if post_scale is None or ps_dev is not None else float(post_scale)
-    M, ld1 = rows(x1)
-    C = x1.shape[3]
-    if out is None:
-        out = torch.empty(x1.shape, device=x1.device, dtype=torch.float32)
-    check(lib().sgx_dual_affine_act_fwd(ptr(x1), ld1, ptr(s1), ptr(t1), ptr(x2), rows(x2)[1] if x2 is not None else 0, ptr(s2), ptr(t2), ptr(post_add),
-                                        rows(post_add)[1] if post_add is not None else 0, ps, ptr(ps_dev), ptr(out), rows(out)[1], M, C, ACT[act],
-                                        stream()), "sgx_dual_affine_act_fwd")
-    return out
-
-
-def dual_affine_act_bwd(dy, x1, s1, t1, x2=None, s2=None, t2=None, act=None, out=None):
-    """g = dy * act'(s1*x1 + t1 [+ s2*x2 + t2])."""
-    M, ld1 = rows(x1)
-    C = x1.shape[3]
-    if out is None:
-        out = torch.empty(x1.shape, device=x1.device, dtype=torch.float32)
-    check(lib().sgx_dual_affine_act_bwd(ptr(dy), rows(dy)[1], ptr(x1), ld1, ptr(s1), ptr(t1), ptr(x2), rows(x2)[1] if x2 is not None else 0, ptr(s2), ptr(t2),
-                                        ptr(out), rows(out)[1], M, C, ACT[act], stream()), "sgx_dual_affine_act_bwd")
-    return out
-
-
-def dual_affine_act_bwd_reduce(dy, x1, s1, t1, mean1, x2, s2, t2, mean2, act=None, out=None):
-    """g = dy * act'(s1*x1 + t1 + s2*x2 + t2) AND the reduce rows of both BatchNorm backward passes -> (g, parts1, parts2), each parts [2, blocks, C]
-    as bn_bwd(parts=...) takes them (sum g, sum g (x - mean))."""
-    M, ld1 = rows(x1)
-    C = x1.shape[3]
-    if out is None:
-        out = torch.empty(x1.shape, device=x1.device, dtype=torch.float32)
-    parts = torch.empty(4, stats_blocks(M), C, device=x1.device, dtype=torch.float32)
-    check(lib().sgx_dual_affine_act_bwd_reduce(ptr(dy), rows(dy)[1], ptr(x1), ld1, ptr(s1), ptr(t1), ptr(mean1), ptr(x2), rows(x2)[1], ptr(s2), ptr(t2), ptr(mean2),
-                                               ptr(out), rows(out)[1], M, C, ACT[act], ptr(parts), stream()), "sgx_dual_affine_act_bwd_reduce")
-    return out, parts[0:2], parts[2:4]
-
-
 def tri_affine_act(x1, s1, t1, x2=None, s2=None, t2=None, x3=None, s3=None, t3=None, post_add=None, act=None, out=None, post_scale=None,
                    want_stats=False, blocks=None):
-    """y = act(s1*x1 + t1 [+ s2*x2 + t2] [+ s3*x3 + t3]) [+ post_scale * post_add]   (RepVGG three-branch BatchNorm sum: x3 is the block's own
-    input, the identity-BatchNorm branch).  want_stats: -> (y, parts), parts [2, blocks, C] = the per-channel sum / sum of squares rows of the
+    """y = act(s1*x1 + t1 [+ s2*x2 + t2] [+ s3*x3 + t3]) [+ post_scale * post_add]   (RepVGG BatchNorm sum of one to three branches: x3 is the
+    block's own input, the identity-BatchNorm branch; post-activation residual; post_scale: a float or a one-element device tensor, default
+    1).  want_stats: -> (y, parts), parts [2, blocks, C] = the per-channel sum / sum of squares rows of the
     stored y, as bn_finalize takes them.  blocks: row blocks of the sweep (default stats_blocks(M)); y does not depend on it."""
     ps_dev = post_scale if torch.is_tensor(post_scale) else None
     ps = 1.0 if post_scale is None or ps_dev is not None else float(post_scale)
@@ -943,19 +905,22 @@ def tri_affine_act(x1, s1, t1, x2=None, s2=None, t2=None, x3=None, s3=None, t3=N
     return (out, parts) if want_stats else out
 
 
-def tri_affine_act_bwd_reduce(dy, x1, s1, t1, mean1, x2, s2, t2, mean2, x3=None, s3=None, t3=None, mean3=None, act=None, out=None, blocks=None):
-    """g = dy * act'(s1*x1 + t1 + s2*x2 + t2 [+ s3*x3 + t3]) AND the reduce rows of all BatchNorm backward passes -> (g, parts1, parts2, parts3),
-    each parts [2, blocks, C] as bn_bwd(parts=...) takes them (sum g, sum g (x - mean)); parts3 is None without the third branch."""
+def tri_affine_act_bwd_reduce(dy, x1, s1, t1, mean1, x2=None, s2=None, t2=None, mean2=None, x3=None, s3=None, t3=None, mean3=None, act=None, out=None,
+                              blocks=None):
+    """g = dy * act'(s1*x1 + t1 [+ s2*x2 + t2] [+ s3*x3 + t3]) AND the reduce rows of every branch's BatchNorm backward -> (g, parts1, parts2,
+    parts3), each parts [2, blocks, C] as bn_bwd(parts=...) takes them (sum g, sum g (x - mean)); None for a branch that is absent."""
     M, ld1 = rows(x1)
     C = x1.shape[3]
     if out is None:
         out = torch.empty(x1.shape, device=x1.device, dtype=torch.float32)
     nblk = stats_blocks(M) if blocks is None else int(blocks)
-    parts = torch.empty(6 if x3 is not None else 4, nblk, C, device=x1.device, dtype=torch.float32)
-    check(lib().sgx_tri_affine_act_bwd_reduce(ptr(dy), rows(dy)[1], ptr(x1), ld1, ptr(s1), ptr(t1), ptr(mean1), ptr(x2), rows(x2)[1], ptr(s2), ptr(t2),
-                                              ptr(mean2), ptr(x3), rows(x3)[1] if x3 is not None else 0, ptr(s3), ptr(t3), ptr(mean3), ptr(out),
-                                              rows(out)[1], M, C, ACT[act], ptr(parts), nblk, stream()), "sgx_tri_affine_act_bwd_reduce")
-    return out, parts[0:2], parts[2:4], (parts[4:6] if x3 is not None else None)
+    have = [x is not None for x in (x1, x2, x3)]
+    parts = torch.empty(2 * sum(have), nblk, C, device=x1.device, dtype=torch.float32)
+    check(lib().sgx_tri_affine_act_bwd_reduce(ptr(dy), rows(dy)[1], ptr(x1), ld1, ptr(s1), ptr(t1), ptr(mean1), ptr(x2), rows(x2)[1] if have[1] else 0,
+                                              ptr(s2), ptr(t2), ptr(mean2), ptr(x3), rows(x3)[1] if have[2] else 0, ptr(s3), ptr(t3), ptr(mean3),
+                                              ptr(out), rows(out)[1], M, C, ACT[act], ptr(parts), nblk, stream()), "sgx_tri_affine_act_bwd_reduce")
+    pairs = iter(parts.split(2))  # (the rows of the branches that are present, in order)
+    return (out,) + tuple(next(pairs) if h else None for h in have)
 
 
 GATE = {None: 0, "none": 0, "hardsigmoid": 1, "sigmoid": 2}

@@ -99,7 +99,7 @@ class _ConvBN(SgxBlock):
             if post_add is None:
                 y = K.affine_act(t, scale, shift, r1=residual, act=self.act, out=out)
             else:
-                y = K.dual_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out)
+                y = K.tri_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out)
             self._ctx = (x, t, scale, shift, mean, invstd)
             self._req = None
             return y
@@ -114,7 +114,7 @@ class _ConvBN(SgxBlock):
         t = conv.conv(x)
         scale, shift, _, _ = bn.scale_shift(None, 0, False)
         if post_add is not None:
-            return K.dual_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out if out is not None else t)
+            return K.tri_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out if out is not None else t)
         return K.affine_act(t, scale, shift, r1=residual, act=self.act, out=out if out is not None else t)
 
     def bn_reduce_request(self):

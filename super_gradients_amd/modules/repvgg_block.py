@@ -9,7 +9,7 @@ identity-BatchNorm branch `no_conv_branch` wherever use_residual_connection and 
 but its first); `build_residual_branches=False`: the deployment form built directly (only rbr_reparam.{weight,bias}, inference-only).
 
 Kernel sequence (training): the two convolutions run side by side (1x1 on the side stream), each emitting its BatchNorm partial
-statistics from the conv epilogue; two tiny finalizes; ONE sweep computes act(s3*t3 + b3 + s1*t1 + b1) [+ residual] - the reference
+statistics from the conv epilogue; two tiny finalizes; ONE sweep computes act(s3*t3 + b3 + s1*t1 + b1 [+ sI*x + bI]) [+ residual] - the reference
 runs 2 conv + 2 BN + add + activation (+ add).  Backward: one sweep for the gradient through the activation (pre-activation
 recomputed from the saved conv outputs) that also leaves the reduce rows of both BatchNorm backward passes (round 5), then the two
 BatchNorm backward applies in place over t3 / t1, weight gradients on the side stream, and the 1x1 data gradient accumulated into the
@@ -86,53 +86,28 @@ class RepVGGBlock(SgxBlock):
             return y if post_add is None else K.affine_act(y, r1=post_add, out=out if out is not None else y)
         c3, bn3, c1, bn1 = self.branch_3x3.conv, self.branch_3x3.bn, self.branch_1x1.conv, self.branch_1x1.bn
         bni = self.no_conv_branch
-        if bni is not None or want_stats:
-            return self._fwd_three(x, out, post_add, x_stats, want_stats)
-        if self.training:
-            t1 = torch.empty(K.conv_out_shape(x, self.out_channels, 1, 1, self.stride, 0), device=x.device, dtype=torch.float32)
-            _, parts1 = self._net.fork_side(lambda: c1.conv(x, out=t1, stats=True), x, t1)
-            t3, parts3 = c3.conv(x, stats=True)
-            M = t3.shape[0] * t3.shape[1] * t3.shape[2]
-            s3, b3, m3, i3 = bn3.scale_shift(parts3, M, True)
-            self._net.join_side()
-            s1, b1, m1, i1 = bn1.scale_shift(parts1, M, True)
-            s1a, b1a = self._scaled(s1, b1)  # alpha * bn1(.) = (alpha s1) t1 + alpha b1: alpha rides in the sweep's per-channel constants
-            y = K.dual_affine_act(t3, s3, b3, t1, s1a, b1a, post_add=post_add, act=self.act, out=out)
-            self._ctx = (x, t3, t1, s3, b3, m3, i3, s1, b1, m1, i1)
-            return y
-        t3, t1 = c3.conv(x), c1.conv(x)
-        s3, b3, _, _ = bn3.scale_shift(None, 0, False)
-        s1, b1, _, _ = bn1.scale_shift(None, 0, False)
-        s1, b1 = self._scaled(s1, b1)
-        return K.dual_affine_act(t3, s3, b3, t1, s1, b1, post_add=post_add, act=self.act, out=out if out is not None else t3)
-
-    def _fwd_three(self, x, out, post_add, x_stats, want_stats):
-        """The forms the RepVGG classifiers run: the identity-BatchNorm branch as third operand of the sweep and / or the output's statistics
-        rows out of it (a two-branch block whose consumer has an identity branch: the first block of a stage)."""
-        c3, bn3, c1, bn1 = self.branch_3x3.conv, self.branch_3x3.bn, self.branch_1x1.conv, self.branch_1x1.bn
-        bni = self.no_conv_branch
+        xi = x if bni is not None else None  # the identity-BatchNorm branch: the block's input as third operand of the sweep
+        si = bi = mi = ii = None
         if not self.training:
             t3, t1 = c3.conv(x), c1.conv(x)
             s3, b3, _, _ = bn3.scale_shift(None, 0, False)
             s1, b1, _, _ = bn1.scale_shift(None, 0, False)
             s1, b1 = self._scaled(s1, b1)
-            si, bi = bni.scale_shift(None, 0, False)[:2] if bni is not None else (None, None)
-            return K.tri_affine_act(t3, s3, b3, t1, s1, b1, x if bni is not None else None, si, bi, post_add=post_add, act=self.act,
-                                    out=out if out is not None else t3)
+            if bni is not None:
+                si, bi = bni.scale_shift(None, 0, False)[:2]
+            return K.tri_affine_act(t3, s3, b3, t1, s1, b1, xi, si, bi, post_add=post_add, act=self.act, out=out if out is not None else t3)
         t1 = torch.empty(K.conv_out_shape(x, self.out_channels, 1, 1, self.stride, 0), device=x.device, dtype=torch.float32)
         _, parts1 = self._net.fork_side(lambda: c1.conv(x, out=t1, stats=True), x, t1)
         t3, parts3 = c3.conv(x, stats=True)
         M = t3.shape[0] * t3.shape[1] * t3.shape[2]
-        si = bi = mi = ii = None
         if bni is not None:  # (stride 1: the input has the output's M rows)
             si, bi, mi, ii = bni.scale_shift(x_stats if x_stats is not None else K.channel_stats_partial(x), M, True)
         s3, b3, m3, i3 = bn3.scale_shift(parts3, M, True)
         self._net.join_side()
         s1, b1, m1, i1 = bn1.scale_shift(parts1, M, True)
-        s1a, b1a = self._scaled(s1, b1)
-        y = K.tri_affine_act(t3, s3, b3, t1, s1a, b1a, x if bni is not None else None, si, bi, post_add=post_add, act=self.act, out=out,
-                             want_stats=want_stats)
-        if want_stats:
+        s1a, b1a = self._scaled(s1, b1)  # alpha * bn1(.) = (alpha s1) t1 + alpha b1: alpha rides in the sweep's per-channel constants
+        y = K.tri_affine_act(t3, s3, b3, t1, s1a, b1a, xi, si, bi, post_add=post_add, act=self.act, out=out, want_stats=want_stats)
+        if want_stats:  # (the first block of a classifier's stage has no identity branch, but its consumer has)
             y, self._out_stats = y
         self._ctx = (x, t3, t1, s3, b3, m3, i3, s1, b1, m1, i1, si, bi, mi, ii)
         return y
@@ -145,21 +120,16 @@ class RepVGGBlock(SgxBlock):
 
     def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
         c3, bn3, c1, bn1 = self.branch_3x3.conv, self.branch_3x3.bn, self.branch_1x1.conv, self.branch_1x1.bn
-        (x, t3, t1, s3, b3, m3, i3, s1, b1, m1, i1), idn = self._ctx[:11], self._ctx[11:]
+        x, t3, t1, s3, b3, m3, i3, s1, b1, m1, i1, si, bi, mi, ii = self._ctx
         self._ctx = None
         bni = self.no_conv_branch
         s1a, b1a = self._scaled(s1, b1)
-        # one sweep: the gradient through the activation AND the reduce rows of both BatchNorm backward passes (round 5: two passes over
-        # g and the saved conv outputs less per block)
-        dxi = None
-        if bni is not None:
-            # ... and of the identity BatchNorm's: the sweep reads x as well; that branch's input gradient is one BatchNorm-backward apply,
-            # summed into dx by the 3x3 data gradient's epilogue
-            si, bi, mi, ii = idn
-            g, parts3, parts1, partsi = K.tri_affine_act_bwd_reduce(dy, t3, s3, b3, m3, t1, s1a, b1a, m1, x, si, bi, mi, act=self.act)
-            dxi = bni.backward(g, x, si, bi, mi, ii, None, parts=partsi)
-        else:
-            g, parts3, parts1 = K.dual_affine_act_bwd_reduce(dy, t3, s3, b3, m3, t1, s1a, b1a, m1, act=self.act)
+        # one sweep: the gradient through the activation AND the reduce rows of the BatchNorm backward passes (round 5: two passes over
+        # g and the saved conv outputs less per block) ... and of the identity BatchNorm's where there is one: the sweep reads x as well
+        g, parts3, parts1, partsi = K.tri_affine_act_bwd_reduce(dy, t3, s3, b3, m3, t1, s1a, b1a, m1, x if bni is not None else None, si, bi, mi,
+                                                                act=self.act)
+        # the identity branch's input gradient is one BatchNorm-backward apply, summed into dx by the 3x3 data gradient's epilogue
+        dxi = bni.backward(g, x, si, bi, mi, ii, None, parts=partsi) if bni is not None else None
         if isinstance(self.alpha, torch.Tensor):
             # The BatchNorm backward is linear in its upstream gradient (alpha g here): run it on g with scratch parameter gradients, then
             #   d gamma1 = alpha dg', d beta1 = alpha db', d t1 = alpha dt1'   and   d alpha = <g, bn1(t1)> = sum_c (gamma1 dg' + beta1 db')

@@ -275,11 +275,13 @@ def test_relu6_is_rejected_where_it_is_not_implemented(backend):
     with pytest.raises(_lib.SgxError, match="activation"):
         K.conv2d_fwd(x, K.to_ohwi(torch.randn(c, c, 1, 1, generator=g).to(backend)), act="relu6")
     with pytest.raises(_lib.SgxError, match="activation"):
-        K.dual_affine_act(x, ones, ones, act="relu6")
-    with pytest.raises(_lib.SgxError, match="activation"):
         K.tri_affine_act(x, ones, ones, act="relu6")
     with pytest.raises(_lib.SgxError, match="activation"):
-        K.dual_affine_act_bwd(x, x, ones, ones, act="relu6")
+        K.tri_affine_act(x, ones, ones, x, ones, ones, act="relu6", want_stats=True)
+    with pytest.raises(_lib.SgxError, match="activation"):
+        K.tri_affine_act_bwd_reduce(x, x, ones, ones, ones, act="relu6")
+    with pytest.raises(_lib.SgxError, match="activation"):
+        K.tri_affine_act_bwd_reduce(x, x, ones, ones, ones, x, ones, ones, ones, act="relu6")
     # statistics together with bias / activation: rejected by the depthwise forward
     wk = K.to_dw(torch.randn(c, 1, 3, 3, generator=g).to(backend))
     with pytest.raises(_lib.SgxError, match="statistics"):

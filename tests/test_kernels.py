@@ -747,11 +747,12 @@ def test_nms_large_topk(backend):
 # --------------------------------------------------------------------------------------------- PP-YOLOE pieces
 @pytest.mark.parametrize("act", ["silu", "relu", None])
 def test_dual_affine_act(backend, act):
-    """RepVGG two-branch BN sum + activation (+ post-activation residual), and the gradient through the activation."""
+    """RepVGG two-branch BN sum + activation (+ post-activation residual), and the gradient through the activation; the one-branch forms."""
     n, h, w, c = _sizes(backend, (3, 37, 29, 96), (2, 5, 3, 8))
     g = torch.Generator().manual_seed(11)
     x1, x2, r, dy = (torch.randn(n, c, h, w, generator=g) for _ in range(4))
     s1, t1, s2, t2 = (torch.randn(c, generator=g) for _ in range(4))
+    mu1, mu2 = (torch.randn(c, generator=g) * 0.2 for _ in range(2))
     f = {"silu": F.silu, "relu": F.relu, None: lambda v: v}[act]
     v = lambda t: t.view(1, c, 1, 1)  # noqa: E731
     pre = (x1 * v(s1) + v(t1) + x2 * v(s2) + v(t2)).requires_grad_(True)
@@ -759,14 +760,27 @@ def test_dual_affine_act(backend, act):
     (gref,) = torch.autograd.grad(ref, pre, dy)
     d = lambda t: t.to(backend)  # noqa: E731
     out = empty_nhwc(n, h, w, c, backend, ld_pix=c + 8, c_off=4)
-    K.dual_affine_act(to_nhwc(x1, backend, ld_pix=c + 4), d(s1), d(t1), to_nhwc(x2, backend), d(s2), d(t2), post_add=to_nhwc(r, backend), act=act, out=out)
-    assert_close(to_nchw_cpu(out), ref.detach(), TOL, f"dual_affine_act {act}")
-    gg = K.dual_affine_act_bwd(to_nhwc(dy, backend), to_nhwc(x1, backend), d(s1), d(t1), to_nhwc(x2, backend, ld_pix=c + 12, c_off=8), d(s2), d(t2), act=act)
-    assert_close(to_nchw_cpu(gg), gref, TOL, f"dual_affine_act_bwd {act}")
+    K.tri_affine_act(to_nhwc(x1, backend, ld_pix=c + 4), d(s1), d(t1), to_nhwc(x2, backend), d(s2), d(t2), post_add=to_nhwc(r, backend), act=act, out=out)
+    assert_close(to_nchw_cpu(out), ref.detach(), TOL, f"two-branch sum {act}")
+    gg = K.tri_affine_act_bwd_reduce(to_nhwc(dy, backend), to_nhwc(x1, backend), d(s1), d(t1), d(mu1), to_nhwc(x2, backend, ld_pix=c + 12, c_off=8), d(s2),
+                                     d(t2), d(mu2), act=act)[0]
+    assert_close(to_nchw_cpu(gg), gref, TOL, f"two-branch gradient {act}")
     # single branch + post-activation residual (pp_yolo_head.py:205)
-    ref1 = f(x1 * v(s1) + v(t1)) + r
-    y1 = K.dual_affine_act(to_nhwc(x1, backend), d(s1), d(t1), post_add=to_nhwc(r, backend), act=act)
-    assert_close(to_nchw_cpu(y1), ref1, TOL, f"single affine + post add {act}")
+    pre1 = (x1 * v(s1) + v(t1)).requires_grad_(True)
+    ref1 = f(pre1) + r
+    y1 = K.tri_affine_act(to_nhwc(x1, backend), d(s1), d(t1), post_add=to_nhwc(r, backend), act=act)
+    assert_close(to_nchw_cpu(y1), ref1.detach(), TOL, f"single affine + post add {act}")
+    # ... and its backward: g, and ONE pair of reduce rows - what bn_bwd's own reduce sweep leaves for (g, x1): bn_bwd(parts=...) gives the same bits
+    (gref1,) = torch.autograd.grad(ref1, pre1, dy)
+    a1 = to_nhwc(x1, backend, ld_pix=c + 4)
+    g1, p1, p2, p3 = K.tri_affine_act_bwd_reduce(to_nhwc(dy, backend), a1, d(s1), d(t1), d(mu1), act=act)
+    assert_close(to_nchw_cpu(g1), gref1, TOL, f"single-branch gradient {act}")
+    assert p2 is None and p3 is None and tuple(p1.shape) == (2, K.stats_blocks(n * h * w), c)
+    gam, inv = torch.rand(c, generator=g) + 0.5, torch.rand(c, generator=g) + 0.5
+    dg0, db0, dg1, db1 = (torch.zeros(c, device=backend) for _ in range(4))
+    dx0 = K.bn_bwd(g1, a1, d(s1), d(t1), d(gam), d(mu1), d(inv), dg0, db0, act=None)
+    dx1 = K.bn_bwd(g1, a1, d(s1), d(t1), d(gam), d(mu1), d(inv), dg1, db1, act=None, parts=p1)
+    assert torch.equal(dx0.cpu(), dx1.cpu()) and torch.equal(dg0.cpu(), dg1.cpu()) and torch.equal(db0.cpu(), db1.cpu())
 
 
 @pytest.mark.parametrize("gate", ["hardsigmoid", "sigmoid"])

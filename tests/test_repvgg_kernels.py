@@ -1,5 +1,5 @@
-"""The RepVGG three-branch sweeps (csrc/bn.hip: sgx_tri_affine_act_fwd, sgx_tri_affine_act_bwd_reduce) against plain torch, the two-branch
-entry points they extend (bit for bit with a null third branch), and across launch geometries."""
+"""The RepVGG branch-sum sweeps (csrc/bn.hip: sgx_tri_affine_act_fwd, sgx_tri_affine_act_bwd_reduce) against plain torch, with fewer than three
+branches (a null branch is a branch of zero scale and shift, bit for bit), and across launch geometries."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -13,7 +13,10 @@ ACTS = {"relu": F.relu, "silu": F.silu, None: lambda t: t}
 
 
 def _shape(backend, c):
-    """RepVggA0's stage widths; rows: several row blocks on the chip, a few rows of one block on the emulation."""
+    """RepVggA0's stage widths; rows: several row blocks on the chip, a few rows of one block on the emulation.  c = 4: one channel group,
+    256 row lanes, most of them idle; c = 260: 65 channel groups = two channel strips, the second with one live group."""
+    if c == 4:
+        return (1, 3, 5, 4)
     if backend.type == "cuda":
         return (3, 23, 19, c) if c < 1000 else (2, 7, 7, c)
     return (2, 5, 3, c) if c < 1000 else (1, 3, 2, c)
@@ -41,7 +44,7 @@ def _finalized(parts, M, backend):
     return mean.cpu().double(), 1.0 / invstd.cpu().double() ** 2 - eps
 
 
-@pytest.mark.parametrize("c", [48, 96, 1280])
+@pytest.mark.parametrize("c", [4, 48, 96, 260, 1280])
 @pytest.mark.parametrize("act", ["relu", "silu", None])
 @pytest.mark.parametrize("post_add,stats", [(False, False), (True, True), (False, True), (True, False)])
 def test_tri_affine_act_forward(backend, c, act, post_add, stats):
@@ -69,7 +72,7 @@ def test_tri_affine_act_forward(backend, c, act, post_add, stats):
         assert_close(parts[0].sum(0).cpu(), stored.sum((0, 2, 3)).float(), 1e-4, "sum y")
 
 
-@pytest.mark.parametrize("c", [48, 96, 1280])
+@pytest.mark.parametrize("c", [4, 48, 96, 260, 1280])
 @pytest.mark.parametrize("act", ["relu", "silu", None])
 def test_tri_affine_act_bwd_reduce(backend, c, act):
     """g = dy act'(pre) and the reduce rows of the three BatchNorm backward passes: against autograd in fp64, and against bn_bwd's own
@@ -102,28 +105,41 @@ def test_tri_affine_act_bwd_reduce(backend, c, act):
 @pytest.mark.parametrize("act", ["relu", "silu", None])
 @pytest.mark.parametrize("post_add", [False, True])
 def test_null_third_branch_is_the_two_branch_sweep(backend, act, post_add):
-    """Without the identity operand the new entry points give sgx_dual_affine_act_fwd's / sgx_dual_affine_act_bwd_reduce's results bit for bit
-    (the statistics output does not change what is stored either)."""
+    """A null branch is a branch with zero scale and shift, bit for bit (adding +0.0 is exact, and this data has no -0.0 pre-activation): for
+    y, for g and for the reduce rows of the branches that remain - without the third operand and without the second.  The statistics output
+    does not change what is stored either."""
     n, h, w, c = _shape(backend, 96)
-    (t3, t1, _, r, dy), sb, means = _case(n, h, w, c, 5)
+    (t3, t1, x, r, dy), sb, means = _case(n, h, w, c, 5)
     d = lambda v: v.to(backend)  # noqa: E731
-    a, b = to_nhwc(t3, backend, ld_pix=c + 4), to_nhwc(t1, backend)
+    a, b, e = to_nhwc(t3, backend, ld_pix=c + 4), to_nhwc(t1, backend), to_nhwc(x, backend, ld_pix=c + 12, c_off=8)
+    zero = torch.zeros(c, device=backend)
     rr = to_nhwc(r, backend) if post_add else None
-    y2 = K.dual_affine_act(a, d(sb[0][0]), d(sb[0][1]), b, d(sb[1][0]), d(sb[1][1]), post_add=rr, act=act)
-    y3 = K.tri_affine_act(a, d(sb[0][0]), d(sb[0][1]), b, d(sb[1][0]), d(sb[1][1]), post_add=rr, act=act)
-    y3s, parts = K.tri_affine_act(a, d(sb[0][0]), d(sb[0][1]), b, d(sb[1][0]), d(sb[1][1]), post_add=rr, act=act, want_stats=True)
-    assert torch.equal(y2.cpu(), y3.cpu()) and torch.equal(y2.cpu(), y3s.cpu())
+    one, two = (a, d(sb[0][0]), d(sb[0][1])), (a, d(sb[0][0]), d(sb[0][1]), b, d(sb[1][0]), d(sb[1][1]))
+    y2 = K.tri_affine_act(*two, post_add=rr, act=act)
+    y2s, parts = K.tri_affine_act(*two, post_add=rr, act=act, want_stats=True)
+    assert torch.equal(y2.cpu(), y2s.cpu())
     assert_close(parts[0].sum(0).cpu(), y2.cpu().double().sum((0, 1, 2)).float(), 1e-4, "sum y")
-    y1 = K.dual_affine_act(a, d(sb[0][0]), d(sb[0][1]), post_add=rr, act=act)
-    assert torch.equal(y1.cpu(), K.tri_affine_act(a, d(sb[0][0]), d(sb[0][1]), post_add=rr, act=act).cpu())
+    y3, parts3 = K.tri_affine_act(*two, e, zero, zero, post_add=rr, act=act, want_stats=True)
+    assert torch.equal(y2.cpu(), y3.cpu()) and torch.equal(parts.cpu(), parts3.cpu())
+    assert torch.equal(y2.cpu(), K.tri_affine_act(*two, e, zero, zero, post_add=rr, act=act).cpu())
+    y1 = K.tri_affine_act(*one, post_add=rr, act=act)
+    assert torch.equal(y1.cpu(), K.tri_affine_act(*one, b, zero, zero, post_add=rr, act=act).cpu())
     dyd = to_nhwc(dy, backend)
-    g2, q3, q1 = K.dual_affine_act_bwd_reduce(dyd, a, d(sb[0][0]), d(sb[0][1]), d(means[0]), b, d(sb[1][0]), d(sb[1][1]), d(means[1]), act=act)
-    g3, p3, p1, pi = K.tri_affine_act_bwd_reduce(dyd, a, d(sb[0][0]), d(sb[0][1]), d(means[0]), b, d(sb[1][0]), d(sb[1][1]), d(means[1]), act=act)
+    m = [d(v) for v in means]
+    one, two = one + (m[0],), two[:3] + (m[0],) + two[3:] + (m[1],)
+    g2, p3, p1, pi = K.tri_affine_act_bwd_reduce(dyd, *two, act=act)
     assert pi is None
+    g3, q3, q1, qi = K.tri_affine_act_bwd_reduce(dyd, *two, e, zero, zero, m[2], act=act)
+    assert qi is not None
     assert torch.equal(g2.cpu(), g3.cpu()) and torch.equal(q3.cpu(), p3.cpu()) and torch.equal(q1.cpu(), p1.cpu())
+    g1, r3, r1, ri = K.tri_affine_act_bwd_reduce(dyd, *one, act=act)
+    assert r1 is None and ri is None
+    g1z, z3, z1, zi = K.tri_affine_act_bwd_reduce(dyd, *one, b, zero, zero, m[1], act=act)
+    assert zi is None and z1 is not None
+    assert torch.equal(g1.cpu(), g1z.cpu()) and torch.equal(r3.cpu(), z3.cpu())
 
 
-@pytest.mark.parametrize("c", [48, 1280])
+@pytest.mark.parametrize("c", [4, 48, 260, 1280])
 def test_launch_geometry_does_not_change_the_result(backend, c):
     """Three row-block counts: the stored y / g are the same bits (a lane's arithmetic does not depend on the grid), and a repeated launch on
     one geometry repeats its partial rows exactly (fixed order, no atomics).  The partial rows are one per row block, so their count follows the

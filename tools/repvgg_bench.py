@@ -3,10 +3,10 @@
     python tools/repvgg_bench.py [--iters 50] [--repeats 5] [--batch 64] [--no-step]
 Shapes: the identity blocks of RepVggA0 and RepVggB1 at 224 x 224 (stage 1-3; stage 4 is a single stride-2 block).
   forward   fused:    sgx_tri_affine_act_fwd with the statistics rows                              reads t3, t1, x      writes y
-            composed: dual_affine_act (no activation) -> affine_act(x) + residual + ReLU -> channel_stats_partial(y)
+            composed: the two-branch sweep (no activation) -> affine_act(x) + residual + ReLU -> channel_stats_partial(y)
                                                                                                     reads t3, t1, x, tmp, y   writes tmp, y
   backward  fused:    sgx_tri_affine_act_bwd_reduce                                                 reads dy, t3, t1, x  writes g
-            composed: dual_affine_act_bwd_reduce -> sgx_bn_bwd_reduce(g, x)                         reads dy, t3, t1, g, x   writes g
+            composed: the two-branch reduce sweep -> sgx_bn_bwd_reduce(g, x)                   reads dy, t3, t1, g, x   writes g
             (the composed backward cannot form the three-term pre-activation: it is timed for its traffic, not compared for its values)
 Method: every shape warmed up; the two versions alternate inside each repeat; device events around `iters` launches; median and the
 min..max spread over the repeats; bytes = the tensors listed above, 4 B an element.  Measurement tool: product library, GPU only."""
@@ -79,7 +79,7 @@ def main():
             K.tri_affine_act(t3, sc[0], sh[0], t1, sc[1], sh[1], x, sc[2], sh[2], act="relu", out=y, want_stats=True)
 
         def fwd_composed():
-            K.dual_affine_act(t3, sc[0], sh[0], t1, sc[1], sh[1], act=None, out=tmp)
+            K.tri_affine_act(t3, sc[0], sh[0], t1, sc[1], sh[1], act=None, out=tmp)
             K.affine_act(x, sc[2], sh[2], r1=tmp, act="relu", out=y)
             K.channel_stats_partial(y)
 
@@ -87,7 +87,7 @@ def main():
             K.tri_affine_act_bwd_reduce(dy, t3, sc[0], sh[0], mu[0], t1, sc[1], sh[1], mu[1], x, sc[2], sh[2], mu[2], act="relu", out=g)
 
         def bwd_composed():
-            K.dual_affine_act_bwd_reduce(dy, t3, sc[0], sh[0], mu[0], t1, sc[1], sh[1], mu[1], act="relu", out=g)
+            K.tri_affine_act_bwd_reduce(dy, t3, sc[0], sh[0], mu[0], t1, sc[1], sh[1], mu[1], act="relu", out=g)
             check(lib().sgx_bn_bwd_reduce(ptr(g), rows(g)[1], ptr(x), rows(x)[1], ptr(sc[2]), ptr(sh[2]), ptr(mu[2]), M, c, K.ACT[None], ptr(parts2),
                                           stream()), "sgx_bn_bwd_reduce")
 

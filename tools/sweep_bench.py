@@ -32,7 +32,7 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / args.iters
 
-    print(f"{'shape':<22}{'MB/tensor':>10} | " + " | ".join(f"{n:>24}" for n in ("affine_act (r+w)", "bn_bwd (2r, 2r+w)", "dual_affine (2r+w)", "qarep_bwd (3r, 3r+2w)", "axpy acc (2r+w)")) + "   us, TB/s")
+    print(f"{'shape':<22}{'MB/tensor':>10} | " + " | ".join(f"{n:>24}" for n in ("affine_act (r+w)", "bn_bwd (2r, 2r+w)", "branch sum (2r+w)", "qarep_bwd (3r, 3r+2w)", "axpy acc (2r+w)")) + "   us, TB/s")
     for n, h, w, c in shapes:
         x = torch.randn(n, h, w, c, device=dev)
         y = torch.empty_like(x)
@@ -48,7 +48,7 @@ def main():
         cols.append((t, 2 * nb))
         t = timed(lambda: K.bn_bwd(dy, x, sc, sh, gam, mean, inv, dg, db, act="relu", dx_out=y))
         cols.append((t, 5 * nb))
-        t = timed(lambda: K.dual_affine_act(x, sc, sh, u, sc, sh, act="relu", out=y))
+        t = timed(lambda: K.tri_affine_act(x, sc, sh, u, sc, sh, act="relu", out=y))
         cols.append((t, 3 * nb))
         cols.append((float("nan"), 0))
         t = timed(lambda: K.axpy(x, out=y, accumulate=True))
