@@ -39,6 +39,8 @@ extern "C" {
 #define SGX_ACT_SILU 2
 #define SGX_ACT_RELU6 3 /* min(max(v, 0), 6), derivative 1 on 0 < v < 6 (nn.ReLU6): sgx_affine_act_fwd, sgx_bn_bwd_reduce / _apply and the depthwise
                          * convolution implement it; every other entry point that takes an activation rejects it (SGX_ERR_BAD_ARG) */
+#define SGX_ACT_HSWISH 4 /* v * min(max(v + 3, 0), 6) / 6 (MobileNetV3's h_swish); derivative 0 for v <= -3, 1 for v >= 3, (2 v + 3) / 6 between.
+                          * Implemented where SGX_ACT_RELU6 is, and by the sgx_bn_gate_act_* sweeps; rejected elsewhere */
 
 int32_t sgx_version(void);
 const char* sgx_last_error(void);
@@ -376,6 +378,12 @@ int32_t sgx_bn_bwd_finalize(const float* partials, int32_t nblk, int64_t M, int3
 int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale,
                          const float* shift, const float* coef, float* dx, int64_t dx_ld, float* g_out, int64_t g_ld,
                          int64_t M, int32_t C, int32_t act, void* stream);
+/* Dropout in training (nn.Dropout): y = x * mask / (1 - p) over an [M][C] matrix (C % 4 == 0), 0 <= p < 1.  The mask comes from
+ * Philox-4x32-10 keyed by `seed` with counter (index of the element's 4-channel group, offset): element (r, c) is kept when word c % 4 of
+ * block r * C / 4 + c / 4 is >= floor(p * 2^32).  Nothing is stored: the backward dx = dy * mask / (1 - p) is the same call with the same
+ * (seed, offset).  The decision does not depend on strides or launch geometry; p == 0 copies x bit for bit.                        */
+int32_t sgx_dropout_fwd(const float* x, int64_t x_ld, float* y, int64_t y_ld, int64_t M, int32_t C, float p, uint64_t seed, uint64_t offset,
+                        void* stream);
 /* QARepVGG block, training form, on sgx_conv2d_fwd_dual's outputs (y = conv3x3(x), u = conv1x1(x; alpha*W1 + I) + b1, five moment planes):
  * replaces, per block, F.batch_norm x2 + the two branch adds + the activation (modules/qarepvgg_block.py:184-204) and their backward.
  *   sgx_qarep_fwd_finalize  both BatchNorms' statistics from the moments (s = bn3(y) + u is affine in (y, u) per channel; fp64): running
@@ -491,6 +499,20 @@ int64_t sgx_dwconv3x3_bwd_weight_workspace(const sgx_conv_desc* d);
 int32_t sgx_dwconv3x3_bwd_weight(const sgx_conv_desc* d, const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes,
                                  void* stream);
 
+/* Depthwise 5x5 convolution, pad 2, stride 1 or 2: nn.Conv2d(C, C, 5, stride, 2, groups=C, bias=False) of
+ *   training/models/classification_models/mobilenetv3.py:88,104 and its backward.  The contracts of the 3x3 namesakes above with
+ * R == S == 5, pad == 2; filter storage [5][5][C].  Stride-2 data gradient: the taps of matching parity, two or three per axis.
+ * sgx_debug_set_dwconv5x5_form: which forward runs - 0 (default) the register window at two channels per lane, 1 the LDS patch; the
+ * count of statistics rows follows the form (query sgx_dwconv5x5_stat_blocks after setting it).  A measurement switch.          */
+int32_t sgx_dwconv5x5_stat_blocks(const sgx_conv_desc* d);
+int32_t sgx_dwconv5x5_fwd(const sgx_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int32_t act,
+                          float* stat_partials, void* stream);
+int32_t sgx_dwconv5x5_bwd_data(const sgx_conv_desc* d, const float* dy, const float* w, float* dx, int32_t accumulate, void* stream);
+int64_t sgx_dwconv5x5_bwd_weight_workspace(const sgx_conv_desc* d);
+int32_t sgx_dwconv5x5_bwd_weight(const sgx_conv_desc* d, const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes,
+                                 void* stream);
+int32_t sgx_debug_set_dwconv5x5_form(int32_t form);
+
 /* ---------------------------------------------------------------------------------------------
  * Squeeze-excitation gates and nearest up-sampling of PP-YOLOE:
  *   EffectiveSEBlock.forward  modules/se_blocks.py:39-42     x * hardsigmoid(project(mean_hw(x)))
@@ -517,6 +539,26 @@ int32_t sgx_upsample2x_fwd(int32_t N, int32_t H, int32_t W, int32_t C, const flo
                            int64_t y_ld_pix, int64_t y_ld_img, void* stream);
 int32_t sgx_upsample2x_bwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img,
                            float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
+
+/* BatchNorm -> squeeze-excitation gate -> activation as fused sweeps (MobileNetV3's expanded InvertedResidual: dw -> BN -> SELayer -> act,
+ * classification_models/mobilenetv3.py:103-108).  z = scale[c] * x + shift[c] (scale == shift == NULL: z = x, the folded eval form),
+ * s = f(pre[n][c]) (SGX_GATE_*), y = act(s * z) (any SGX_ACT_*).  Rows are the N * HW pixels, uniformly strided (x_ld ...); row r belongs
+ * to image r / HW.  The means SELayer takes of z are affine in sgx_image_colsum's means of x: z is never stored.
+ *   _fwd       y = act(s * z), one pass.
+ *   _bwd_gate  dpre[n][c] = f'(pre) * sum over the image's pixels of gv * z, gv = dy * act'(s * z); two-stage, deterministic
+ *              (ws: sgx_bn_gate_act_bwd_gate_workspace bytes).
+ *   _bwd_data  dz = gv * s + dmean[n][c] / HW (dmean may be NULL), stored; partials != NULL: also [2][sgx_stats_blocks(N * HW)][C] rows
+ *              sum dz, sum dz * (x - save_mean) - bit for bit the rows sgx_bn_bwd_reduce(dz, x, act = NONE) writes, so
+ *              sgx_bn_bwd_finalize + sgx_bn_bwd_apply(act = NONE) finish the BatchNorm backward without a reduce sweep.            */
+int32_t sgx_bn_gate_act_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
+                            float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, int32_t act, void* stream);
+int64_t sgx_bn_gate_act_bwd_gate_workspace(int32_t N, int32_t HW, int32_t C);
+int32_t sgx_bn_gate_act_bwd_gate(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                 const float* pre, int32_t gate, int32_t act, float* dpre, int32_t N, int32_t HW, int32_t C, void* ws,
+                                 int64_t ws_bytes, void* stream);
+int32_t sgx_bn_gate_act_bwd_data(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                 const float* pre, int32_t gate, int32_t act, const float* dmean, float* dz, int64_t dz_ld,
+                                 const float* save_mean, float* partials, int32_t N, int32_t HW, int32_t C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detection head decode, PPYoloELoss (assigner + VFL/GIoU/DFL with hand-written backward), NMS.

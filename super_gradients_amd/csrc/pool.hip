@@ -361,9 +361,10 @@ struct DwGeom {
     long i_ld_pix, i_ld_img, o_ld_pix, o_ld_img;  // strides of the tensor the window walks / of the tensor indexed by output pixels
 };
 // Hi x Wi: the map the window walks, Ho x Wo: the map a column belongs to
-static DwGeom dw_geom(int N, int Hi, int Wi, int Ho, int Wo, int C, long i_ld_pix, long i_ld_img, long o_ld_pix, long o_ld_img, long min_threads) {
+// vec: channels per lane (4: the 3x3 kernels' float4 groups; 2: the 5x5 kernels' float2 groups - C4 then counts pairs)
+static DwGeom dw_geom(int N, int Hi, int Wi, int Ho, int Wo, int C, long i_ld_pix, long i_ld_img, long o_ld_pix, long o_ld_img, long min_threads, int vec = 4) {
     DwGeom g;
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.C = C; g.C4 = C / 4;
+    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.C = C; g.C4 = C / vec;
     g.ctiles = sgx_cdiv(g.C4, 64);
     g.CG = sgx_cdiv(g.C4, g.ctiles);  // (1296 channels: six strips of 54 groups, not five of 64 and one of 4)
     g.PL = DW_THREADS / g.CG;
@@ -601,12 +602,13 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_wgrad_fold_kernel(const flo
 }
 
 #define DW_ALIGNED(p) (((uintptr_t)(p) % 16) == 0)
-static int32_t dw_check(const sgx_conv_desc* d, const char* what) {
+static int32_t dw_check(const sgx_conv_desc* d, const char* what, int k = 3) {
     SGX_CHECK_ARG(d, "%s: null descriptor", what);
     SGX_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "%s: bad dims N=%d H=%d W=%d C=%d", what, d->N, d->H, d->W, d->C);
     SGX_CHECK_ARG(d->C % 4 == 0, "%s: C=%d must be a multiple of 4 (16-byte channel groups)", what, d->C);
     SGX_CHECK_ARG(d->K == d->C, "%s: depthwise means K == C (one filter per channel), got K=%d C=%d", what, d->K, d->C);
-    SGX_CHECK_ARG(d->R == 3 && d->S == 3 && d->pad == 1, "%s: only the 3x3 pad-1 filter is built, got R=%d S=%d pad=%d", what, d->R, d->S, d->pad);
+    if (k == 3) SGX_CHECK_ARG(d->R == 3 && d->S == 3 && d->pad == 1, "%s: only the 3x3 pad-1 filter is built, got R=%d S=%d pad=%d", what, d->R, d->S, d->pad);
+    else SGX_CHECK_ARG(d->R == k && d->S == k && d->pad == k / 2, "%s: the %dx%d pad-%d filter, got R=%d S=%d pad=%d", what, k, k, k / 2, d->R, d->S, d->pad);
     SGX_CHECK_ARG(d->stride == 1 || d->stride == 2, "%s: stride %d is not built (1 or 2)", what, d->stride);
     SGX_CHECK_ARG(d->Ho == (d->H - 1) / d->stride + 1 && d->Wo == (d->W - 1) / d->stride + 1, "%s: Ho/Wo do not match (H+2p-R)/s+1", what);
     SGX_CHECK_ARG(d->x_ld_pix >= d->C && d->y_ld_pix >= d->C && d->x_ld_pix % 4 == 0 && d->y_ld_pix % 4 == 0 && d->x_ld_img % 4 == 0 && d->y_ld_img % 4 == 0,
@@ -695,5 +697,408 @@ extern "C" int32_t sgx_dwconv3x3_bwd_weight(const sgx_conv_desc* d, const float*
     SGX_CHECK_LAUNCH("dwconv3x3_bwd_weight");
     SGX_LAUNCH(dwconv_wgrad_fold_kernel, dim3((unsigned)sgx_cdiv(9L * d->C, 16)), dim3(DW_THREADS), 0, stream, (const float*)ws, nblk, 9 * d->C, dw);
     SGX_CHECK_LAUNCH("dwconv3x3_bwd_weight (fold)");
+    return SGX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Depthwise 5x5 convolution, pad 2, stride 1 or 2 (MobileNetV3's nn.Conv2d(C, C, 5, stride, 2, groups = C)).  Filter [5][5][C].
+// The 3x3 scheme (window rows and taps in registers, one float4 channel group per lane) would need 25 + 25 float4s: 200 registers before
+// any addressing.  Two forms of the forward are built (DESIGN.md 16.5 has the measurements that chose between them):
+//   register window: the same geometry and walk with TWO channels per lane (float2 groups: 25 + 25 float2s, 100 registers; a wave still
+//     reads contiguous pixel rows, 512 bytes per 64 lanes); also the stride-1 data gradient (reversed taps) and, with its 25 accumulators,
+//     the weight gradient;
+//   LDS patch: a workgroup owns a TH x TW tile of output pixels of CG float4 channel groups, stages the (TH * stride + 4) x (TW * stride + 4)
+//     input patch once (zeros outside the map) and every lane reads its 25 window elements from LDS - each input element is fetched from
+//     global memory once per workgroup; the taps stay in registers (25 float4s).
+// The stride-2 data gradient is a gather over the taps of matching parity: three or two per axis.
+#define DW5_K 5
+#define DW5_TAPS 25
+__device__ __forceinline__ float2 dw_ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
+__device__ __forceinline__ void dw_st2(float* p, float2 v) { *reinterpret_cast<float2*>(p) = v; }
+__device__ __forceinline__ void dw_fma2(float2& a, const float2& x, const float2& w) {
+    a.x = fmaf(x.x, w.x, a.x); a.y = fmaf(x.y, w.y, a.y);
+}
+// the five window columns wi0 .. wi0 + 4 of input row hi (zeros outside the map, or when !on)
+__device__ __forceinline__ void dw5_ldrow(const float* __restrict__ xb, const DwGeom& g, int hi, int wi0, bool on, float2 (&r)[DW5_K]) {
+    const bool ok = on && hi >= 0 && hi < g.Hi;
+#pragma unroll
+    for (int s = 0; s < DW5_K; ++s) {
+        const int wi = wi0 + s;
+        r[s] = (ok && wi >= 0 && wi < g.Wi) ? dw_ld2(xb + ((long)hi * g.Wi + wi) * g.i_ld_pix) : make_float2(0.f, 0.f);
+    }
+}
+__device__ __forceinline__ void dw2_fold_store(float2 (&red)[DW_THREADS], const DwGeom& g, int tid, int cg, int pl, bool lane_ok, float2 q, float* dst) {
+    red[tid] = q;
+    __syncthreads();
+    if (lane_ok && pl == 0) {
+        double s[2] = {0.0, 0.0};
+        for (int k = 0; k < g.PL; ++k) {
+            const float2 a = red[k * g.CG + cg];
+            s[0] += a.x; s[1] += a.y;
+        }
+        dw_st2(dst, make_float2((float)s[0], (float)s[1]));
+    }
+    __syncthreads();
+}
+
+// Register-window forward (see dwconv_fwd_kernel: the same arguments and walk; g.C4 counts channel PAIRS here).
+template <int ST>
+__global__ __launch_bounds__(DW_THREADS) void dwconv5_fwd_kernel(DwGeom g, const float* __restrict__ x, const float* __restrict__ w,
+                                                                 const float* __restrict__ bias, float* __restrict__ y, int act, int flip, int accumulate,
+                                                                 float* __restrict__ partials) {
+    __shared__ float2 red[DW_THREADS];
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c2 = blockIdx.y * g.CG + cg, c = c2 * 2;
+    const long item = (long)blockIdx.x * g.PL + pl;
+    const bool lane_ok = pl < g.PL && c2 < g.C4;
+    float2 q0 = make_float2(0.f, 0.f), q1 = q0;
+    if (lane_ok && item < g.items) {
+        const DwCol k = dw_column(g, item);
+        float2 wt[DW5_TAPS];
+#pragma unroll
+        for (int t = 0; t < DW5_TAPS; ++t) wt[t] = dw_ld2(w + (long)(flip ? DW5_TAPS - 1 - t : t) * g.C + c);
+        const float2 b = bias ? dw_ld2(bias + c) : make_float2(0.f, 0.f);
+        const float* __restrict__ xb = x + (long)k.img * g.i_ld_img + c;
+        float* __restrict__ yb = y + (long)k.img * g.o_ld_img + c;
+        const int wi0 = k.col * ST - 2;
+        const int ho0 = k.strip * g.TH, ho1 = min(g.Ho, ho0 + g.TH);
+        float2 r[DW5_K][DW5_K], nx[ST][DW5_K];
+#pragma unroll
+        for (int i = 0; i < DW5_K; ++i) dw5_ldrow(xb, g, ho0 * ST - 2 + i, wi0, true, r[i]);
+        for (int ho = ho0; ho < ho1; ++ho) {
+            const bool more = ho + 1 < ho1;
+            const int hn = (ho + 1) * ST - 2;  // first window row of the next output row: its last ST rows are new
+#pragma unroll
+            for (int u = 0; u < ST; ++u) dw5_ldrow(xb, g, hn + DW5_K - ST + u, wi0, more, nx[u]);
+            float2 v = make_float2(0.f, 0.f);
+#pragma unroll
+            for (int i = 0; i < DW5_K; ++i)
+#pragma unroll
+                for (int s = 0; s < DW5_K; ++s) dw_fma2(v, r[i][s], wt[i * DW5_K + s]);
+            q0.x += v.x; q0.y += v.y;
+            q1.x += v.x * v.x; q1.y += v.y * v.y;
+            float* yp = yb + ((long)ho * g.Wo + k.col) * g.o_ld_pix;
+            if (accumulate) {
+                const float2 u = dw_ld2(yp);
+                v.x += u.x; v.y += u.y;
+            }
+            v.x += b.x; v.y += b.y;
+            dw_st2(yp, make_float2(sgx_act6(v.x, act), sgx_act6(v.y, act)));
+#pragma unroll
+            for (int s = 0; s < DW5_K; ++s) {
+#pragma unroll
+                for (int i = 0; i < DW5_K - ST; ++i) r[i][s] = r[i + ST][s];
+#pragma unroll
+                for (int u = 0; u < ST; ++u) r[DW5_K - ST + u][s] = nx[u][s];
+            }
+        }
+    }
+    if (partials) {
+        dw2_fold_store(red, g, tid, cg, pl, lane_ok, q0, partials + (long)blockIdx.x * g.C + c);
+        dw2_fold_store(red, g, tid, cg, pl, lane_ok, q1, partials + ((long)gridDim.x + blockIdx.x) * g.C + c);
+    }
+}
+
+// LDS-patch forward.  Tile geometry: b carries the strides, extents and CG / PL / TH / nstrips / ctiles (C4 = float4 groups, lane = (pixel
+// lane, channel group), channel groups fastest); TW output columns per tile, wtiles of them per row, patch PH x PW pixels.
+struct Dw5Tile {
+    DwGeom b;
+    int TW, wtiles, PH, PW;
+};
+#define DW5_LDS_CG 8  // float4 channel groups per workgroup: 128 contiguous bytes per pixel, 12 x 20 x 128 B = 30 KB of patch
+template <int ST>
+__global__ __launch_bounds__(DW_THREADS) void dwconv5_fwd_lds_kernel(Dw5Tile t, const float* __restrict__ x, const float* __restrict__ w,
+                                                                     const float* __restrict__ bias, float* __restrict__ y, int act,
+                                                                     float* __restrict__ partials) {
+    SGX_DYN_SMEM(float, patch);  // [PH][PW][CG] float4
+    __shared__ float4 red[DW_THREADS];
+    const DwGeom& g = t.b;
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c4 = blockIdx.y * g.CG + cg, c = c4 * 4;
+    const bool lane_ok = pl < g.PL && c4 < g.C4;
+    const int wt_i = blockIdx.x % t.wtiles, rest = blockIdx.x / t.wtiles;
+    const int strip = rest % g.nstrips, img = rest / g.nstrips;
+    const int ho0 = strip * g.TH, wo0 = wt_i * t.TW;
+    const int hi0 = ho0 * ST - 2, wi0 = wo0 * ST - 2;
+    if (lane_ok) {
+        const float* __restrict__ xb = x + (long)img * g.i_ld_img + c;
+        for (int p = pl; p < t.PH * t.PW; p += g.PL) {
+            const int hi = hi0 + p / t.PW, wi = wi0 + p % t.PW;
+            const bool in = hi >= 0 && hi < g.Hi && wi >= 0 && wi < g.Wi;
+            sgx_st4(patch + ((long)p * g.CG + cg) * 4, in ? sgx_ld4(xb + ((long)hi * g.Wi + wi) * g.i_ld_pix) : make_float4(0.f, 0.f, 0.f, 0.f));
+        }
+    }
+    __syncthreads();
+    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+    if (lane_ok) {
+        float4 wt[DW5_TAPS];
+#pragma unroll
+        for (int k = 0; k < DW5_TAPS; ++k) wt[k] = sgx_ld4(w + (long)k * g.C + c);
+        const float4 b = bias ? sgx_ld4(bias + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float* __restrict__ yb = y + (long)img * g.o_ld_img + c;
+        for (int o = pl; o < g.TH * t.TW; o += g.PL) {
+            const int orow = o / t.TW, ocol = o % t.TW;
+            const int ho = ho0 + orow, wo = wo0 + ocol;
+            if (ho >= g.Ho || wo >= g.Wo) continue;
+            const float* pp = patch + ((long)(orow * ST * t.PW + ocol * ST) * g.CG + cg) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int i = 0; i < DW5_K; ++i)
+#pragma unroll
+                for (int s = 0; s < DW5_K; ++s) dw_fma(v, sgx_ld4(pp + (long)(i * t.PW + s) * g.CG * 4), wt[i * DW5_K + s]);
+            q0.x += v.x; q0.y += v.y; q0.z += v.z; q0.w += v.w;
+            q1.x += v.x * v.x; q1.y += v.y * v.y; q1.z += v.z * v.z; q1.w += v.w * v.w;
+            v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+            sgx_st4(yb + ((long)ho * g.Wo + wo) * g.o_ld_pix, make_float4(sgx_act6(v.x, act), sgx_act6(v.y, act), sgx_act6(v.z, act), sgx_act6(v.w, act)));
+        }
+    }
+    if (partials) {
+        dw_fold_store(red, g, tid, cg, pl, lane_ok, q0, partials + (long)blockIdx.x * g.C + c);
+        dw_fold_store(red, g, tid, cg, pl, lane_ok, q1, partials + ((long)gridDim.x + blockIdx.x) * g.C + c);
+    }
+}
+
+// Data gradient at stride 2, gather form.  Column = (image, strip of TH dx rows, dx column wi); g.Hi x g.Wi is the dy map, g.Ho x g.Wo the dx
+// map (TH even: strips start at even rows).  dx(hi, wi) takes the taps (r, s) with ho = (hi + 2 - r) / 2, wo = (wi + 2 - s) / 2 whole:
+// columns j = 0 .. 2 at wo = ((wi + 2) >> 1) - j with s = 2 j + (wi & 1) (odd wi has two); rows alike - the pair hi = 2 k, 2 k + 1 reads the dy
+// rows k - 1, k, k + 1 (even: r = 4, 2, 0; odd: r = 3, 1): walking down, every dy row is loaded once per strip.
+// the dy columns base, base - 1, base - 2 of row ho (zeros where the row or the column does not exist, or when !on)
+__device__ __forceinline__ void dw5_ldrow_s2(const float* __restrict__ gb, const DwGeom& g, int ho, int base, unsigned cv, bool on, float2 (&a)[3]) {
+    const bool ok = on && ho >= 0 && ho < g.Hi;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = (ok && ((cv >> j) & 1u)) ? dw_ld2(gb + ((long)ho * g.Wi + (base - j)) * g.i_ld_pix) : make_float2(0.f, 0.f);
+}
+__global__ __launch_bounds__(DW_THREADS) void dwconv5_bwd_data_s2_kernel(DwGeom g, const float* __restrict__ dy, const float* __restrict__ w,
+                                                                         float* __restrict__ dx, int accumulate) {
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c2 = blockIdx.y * g.CG + cg, c = c2 * 2;
+    const long item = (long)blockIdx.x * g.PL + pl;
+    if (!(pl < g.PL && c2 < g.C4 && item < g.items)) return;
+    const DwCol k = dw_column(g, item);
+    const int wi = k.col, po = wi & 1, base = (wi + 2) >> 1;
+    const float2 z = make_float2(0.f, 0.f);
+    unsigned cv = 0u;  // bit j: column j exists
+    float2 wt[DW5_K][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int s = 2 * j + po;
+        if (s < DW5_K && base - j >= 0 && base - j < g.Wi) cv |= 1u << j;
+#pragma unroll
+        for (int r = 0; r < DW5_K; ++r) wt[r][j] = s < DW5_K ? dw_ld2(w + (long)(r * DW5_K + s) * g.C + c) : z;
+    }
+    const float* __restrict__ gb = dy + (long)k.img * g.i_ld_img + c;
+    float* px = dx + (long)k.img * g.o_ld_img + c + (long)wi * g.o_ld_pix;
+    const long xrow_ld = (long)g.Wo * g.o_ld_pix;
+    const int hi0 = k.strip * g.TH, hi1 = min(g.Ho, hi0 + g.TH);
+    int kk = hi0 >> 1;
+    float2 a0[3], a1[3], a2[3], nx[3];
+    dw5_ldrow_s2(gb, g, kk - 1, base, cv, true, a0);
+    dw5_ldrow_s2(gb, g, kk, base, cv, true, a1);
+    dw5_ldrow_s2(gb, g, kk + 1, base, cv, true, a2);
+    for (int hi = hi0; hi < hi1; hi += 2, ++kk) {
+        const bool two = hi + 1 < hi1;
+        dw5_ldrow_s2(gb, g, kk + 2, base, cv, hi + 2 < hi1, nx);
+        float2 v = z;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            dw_fma2(v, a2[j], wt[0][j]);
+            dw_fma2(v, a1[j], wt[2][j]);
+            dw_fma2(v, a0[j], wt[4][j]);
+        }
+        float* p0 = px + hi * xrow_ld;
+        if (accumulate) {
+            const float2 u = dw_ld2(p0);
+            v.x += u.x; v.y += u.y;
+        }
+        dw_st2(p0, v);
+        if (two) {
+            float2 u = z;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                dw_fma2(u, a2[j], wt[1][j]);
+                dw_fma2(u, a1[j], wt[3][j]);
+            }
+            float* p1 = p0 + xrow_ld;
+            if (accumulate) {
+                const float2 o = dw_ld2(p1);
+                u.x += o.x; u.y += o.y;
+            }
+            dw_st2(p1, u);
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { a0[j] = a1[j]; a1[j] = a2[j]; a2[j] = nx[j]; }
+    }
+}
+
+// Weight gradient, stage 1 (see dwconv_wgrad_kernel): ONE partial row [25][C] per workgroup; the 25 accumulators of a lane's channel pair
+// meet in LDS five taps (one filter row) at a time.  Stage 2 is dwconv_wgrad_fold_kernel over 25 * C columns.
+template <int ST>
+__global__ __launch_bounds__(DW_THREADS) void dwconv5_wgrad_kernel(DwGeom g, long per_blk, const float* __restrict__ x, const float* __restrict__ dy,
+                                                                   float* __restrict__ ws) {
+    __shared__ float2 red[DW5_K][DW_THREADS];
+    const int tid = threadIdx.x, cg = tid % g.CG, pl = tid / g.CG;
+    const int c2 = blockIdx.y * g.CG + cg, c = c2 * 2;
+    const bool lane_ok = pl < g.PL && c2 < g.C4;
+    float2 acc[DW5_TAPS];
+#pragma unroll
+    for (int t = 0; t < DW5_TAPS; ++t) acc[t] = make_float2(0.f, 0.f);
+    if (lane_ok) {
+        const long i0 = (long)blockIdx.x * per_blk, i1 = i0 + per_blk < g.items ? i0 + per_blk : g.items;
+        for (long item = i0 + pl; item < i1; item += g.PL) {
+            const DwCol k = dw_column(g, item);
+            const float* __restrict__ xb = x + (long)k.img * g.i_ld_img + c;
+            const float* __restrict__ gb = dy + (long)k.img * g.o_ld_img + c;
+            const int wi0 = k.col * ST - 2;
+            const int ho0 = k.strip * g.TH, ho1 = min(g.Ho, ho0 + g.TH);
+            float2 r[DW5_K][DW5_K];
+#pragma unroll
+            for (int i = 0; i < DW5_K - ST; ++i) dw5_ldrow(xb, g, ho0 * ST - 2 + i, wi0, true, r[i]);
+            for (int ho = ho0; ho < ho1; ++ho) {
+#pragma unroll
+                for (int u = 0; u < ST; ++u) dw5_ldrow(xb, g, ho * ST - 2 + DW5_K - ST + u, wi0, true, r[DW5_K - ST + u]);
+                const float2 d = dw_ld2(gb + ((long)ho * g.Wo + k.col) * g.o_ld_pix);
+#pragma unroll
+                for (int i = 0; i < DW5_K; ++i)
+#pragma unroll
+                    for (int s = 0; s < DW5_K; ++s) dw_fma2(acc[i * DW5_K + s], r[i][s], d);
+#pragma unroll
+                for (int s = 0; s < DW5_K; ++s)
+#pragma unroll
+                    for (int i = 0; i < DW5_K - ST; ++i) r[i][s] = r[i + ST][s];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < DW5_K; ++i) {
+#pragma unroll
+        for (int s = 0; s < DW5_K; ++s) red[s][tid] = acc[i * DW5_K + s];
+        __syncthreads();
+        if (lane_ok)
+            for (int s = pl; s < DW5_K; s += g.PL) {  // the column lanes share the five folds (each in lane order, in double)
+                double t0 = 0.0, t1 = 0.0;
+                for (int k = 0; k < g.PL; ++k) {
+                    const float2 a = red[s][k * g.CG + cg];
+                    t0 += a.x; t1 += a.y;
+                }
+                dw_st2(ws + ((long)blockIdx.x * DW5_TAPS + i * DW5_K + s) * g.C + c, make_float2((float)t0, (float)t1));
+            }
+        __syncthreads();
+    }
+}
+
+// which forward runs: 0 the register window (the default: DESIGN.md 16.5), 1 the LDS patch - a measurement switch (tools/dwconv_bench.py)
+static std::atomic<int> g_dw5_form{0};
+extern "C" int32_t sgx_debug_set_dwconv5x5_form(int32_t form) {
+    SGX_CHECK_ARG(form == 0 || form == 1, "debug_set_dwconv5x5_form: 0 (register window) or 1 (LDS patch), got %d", form);
+    g_dw5_form = form;
+    return SGX_OK;
+}
+static DwGeom dw5_fwd_geom(const sgx_conv_desc* d) {
+    return dw_geom(d->N, d->H, d->W, d->Ho, d->Wo, d->C, d->x_ld_pix, d->x_ld_img, d->y_ld_pix, d->y_ld_img, DW_MIN_THREADS, 2);
+}
+static Dw5Tile dw5_tile(const sgx_conv_desc* d) {
+    Dw5Tile t;
+    DwGeom& g = t.b;
+    g.N = d->N; g.Hi = d->H; g.Wi = d->W; g.Ho = d->Ho; g.Wo = d->Wo; g.C = d->C; g.C4 = d->C / 4;
+    g.ctiles = sgx_cdiv(g.C4, DW5_LDS_CG);
+    g.CG = sgx_cdiv(g.C4, g.ctiles);
+    g.PL = DW_THREADS / g.CG;
+    g.TH = d->stride == 1 ? 8 : 4;
+    t.TW = d->stride == 1 ? 16 : 8;
+    if (t.TW > g.Wo) t.TW = g.Wo;
+    t.wtiles = sgx_cdiv(g.Wo, t.TW);
+    while (g.TH > 2 && (long)d->N * sgx_cdiv(g.Ho, g.TH) * t.wtiles * g.ctiles * DW_THREADS < DW_MIN_THREADS) g.TH >>= 1;
+    g.nstrips = sgx_cdiv(g.Ho, g.TH);
+    g.items = (long)d->N * g.nstrips * t.wtiles;  // workgroups per channel tile
+    t.PH = g.TH * d->stride + 4;
+    t.PW = t.TW * d->stride + 4;
+    g.i_ld_pix = d->x_ld_pix; g.i_ld_img = d->x_ld_img; g.o_ld_pix = d->y_ld_pix; g.o_ld_img = d->y_ld_img;
+    return t;
+}
+static int32_t dw5_lds_ok(const Dw5Tile& t, const char* what) {
+    SGX_CHECK_ARG(t.b.items < 0x7fffffffL && (long)t.PH * t.PW * t.b.CG * 16 <= 65536, "%s: tile outside the launch limits", what);
+    return SGX_OK;
+}
+
+extern "C" int32_t sgx_dwconv5x5_stat_blocks(const sgx_conv_desc* d) {
+    if (dw_check(d, "dwconv5x5_stat_blocks", 5)) return 0;
+    if (g_dw5_form == 1) return (int32_t)dw5_tile(d).b.items;
+    const DwGeom g = dw5_fwd_geom(d);
+    return (int32_t)sgx_cdiv(g.items, g.PL);
+}
+extern "C" int32_t sgx_dwconv5x5_fwd(const sgx_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int32_t act,
+                                     float* stat_partials, void* stream) {
+    int32_t rc = dw_check(d, "dwconv5x5_fwd", 5);
+    if (rc) return rc;
+    SGX_CHECK_ARG(x && w && y, "dwconv5x5_fwd: null pointer");
+    SGX_CHECK_ARG(DW_ALIGNED(x) && DW_ALIGNED(w) && DW_ALIGNED(y) && DW_ALIGNED(bias) && DW_ALIGNED(stat_partials), "dwconv5x5_fwd: operands must be 16-byte aligned");
+    SGX_CHECK_ACT4(act, "dwconv5x5_fwd");
+    SGX_CHECK_ARG(!stat_partials || (!bias && act == SGX_ACT_NONE), "dwconv5x5_fwd: statistics rows go with the plain convolution (no bias, no activation)");
+    if (g_dw5_form == 1) {
+        const Dw5Tile t = dw5_tile(d);
+        rc = dw5_lds_ok(t, "dwconv5x5_fwd");
+        if (rc) return rc;
+        const dim3 grid((unsigned)t.b.items, (unsigned)t.b.ctiles);
+        const unsigned lds = (unsigned)((long)t.PH * t.PW * t.b.CG * 16);
+        if (d->stride == 1) SGX_LAUNCH(dwconv5_fwd_lds_kernel<1>, grid, dim3(DW_THREADS), lds, stream, t, x, w, bias, y, act, stat_partials);
+        else SGX_LAUNCH(dwconv5_fwd_lds_kernel<2>, grid, dim3(DW_THREADS), lds, stream, t, x, w, bias, y, act, stat_partials);
+        SGX_CHECK_LAUNCH("dwconv5x5_fwd (LDS patch)");
+        return SGX_OK;
+    }
+    const DwGeom g = dw5_fwd_geom(d);
+    if (d->stride == 1) SGX_LAUNCH(dwconv5_fwd_kernel<1>, dw_grid(g), dim3(DW_THREADS), 0, stream, g, x, w, bias, y, act, 0, 0, stat_partials);
+    else SGX_LAUNCH(dwconv5_fwd_kernel<2>, dw_grid(g), dim3(DW_THREADS), 0, stream, g, x, w, bias, y, act, 0, 0, stat_partials);
+    SGX_CHECK_LAUNCH("dwconv5x5_fwd");
+    return SGX_OK;
+}
+extern "C" int32_t sgx_dwconv5x5_bwd_data(const sgx_conv_desc* d, const float* dy, const float* w, float* dx, int32_t accumulate, void* stream) {
+    int32_t rc = dw_check(d, "dwconv5x5_bwd_data", 5);
+    if (rc) return rc;
+    SGX_CHECK_ARG(dy && w && dx, "dwconv5x5_bwd_data: null pointer");
+    SGX_CHECK_ARG(DW_ALIGNED(dy) && DW_ALIGNED(w) && DW_ALIGNED(dx), "dwconv5x5_bwd_data: operands must be 16-byte aligned");
+    // columns are dx pixels; the window walks dy
+    const DwGeom g = dw_geom(d->N, d->Ho, d->Wo, d->H, d->W, d->C, d->y_ld_pix, d->y_ld_img, d->x_ld_pix, d->x_ld_img, DW_MIN_THREADS, 2);
+    if (d->stride == 1) {  // a 5x5 pad-2 convolution of dy with the taps reversed
+        SGX_LAUNCH(dwconv5_fwd_kernel<1>, dw_grid(g), dim3(DW_THREADS), 0, stream, g, dy, w, (const float*)nullptr, dx, SGX_ACT_NONE, 1, accumulate ? 1 : 0,
+                   (float*)nullptr);
+    } else {
+        SGX_LAUNCH(dwconv5_bwd_data_s2_kernel, dw_grid(g), dim3(DW_THREADS), 0, stream, g, dy, w, dx, accumulate ? 1 : 0);
+    }
+    SGX_CHECK_LAUNCH("dwconv5x5_bwd_data");
+    return SGX_OK;
+}
+static DwGeom dw5_wgrad_geom(const sgx_conv_desc* d, int* nblk, long* per_blk) {
+    const DwGeom g = dw_geom(d->N, d->H, d->W, d->Ho, d->Wo, d->C, d->x_ld_pix, d->x_ld_img, d->y_ld_pix, d->y_ld_img, DW_WGRAD_MIN_THREADS, 2);
+    long n = sgx_cdiv(g.items, g.PL);
+    const long cap = SGX_STRIDE_GRID(sgx_cdiv(DW_WGRAD_BLOCKS, g.ctiles));  // (see dw_wgrad_geom: two row blocks on the host emulation)
+    if (n > cap) n = cap;
+    *per_blk = (g.items + n - 1) / n;
+    *nblk = sgx_cdiv(g.items, *per_blk);
+    return g;
+}
+extern "C" int64_t sgx_dwconv5x5_bwd_weight_workspace(const sgx_conv_desc* d) {
+    if (dw_check(d, "dwconv5x5_bwd_weight_workspace", 5)) return 0;
+    int nblk;
+    long per_blk;
+    dw5_wgrad_geom(d, &nblk, &per_blk);
+    return (int64_t)nblk * DW5_TAPS * d->C * (int64_t)sizeof(float);
+}
+extern "C" int32_t sgx_dwconv5x5_bwd_weight(const sgx_conv_desc* d, const float* x, const float* dy, float* dw, void* ws, int64_t ws_bytes,
+                                            void* stream) {
+    int32_t rc = dw_check(d, "dwconv5x5_bwd_weight", 5);
+    if (rc) return rc;
+    SGX_CHECK_ARG(x && dy && dw, "dwconv5x5_bwd_weight: null pointer");
+    SGX_CHECK_ARG(DW_ALIGNED(x) && DW_ALIGNED(dy) && DW_ALIGNED(dw), "dwconv5x5_bwd_weight: operands must be 16-byte aligned");
+    int nblk;
+    long per_blk;
+    const DwGeom g = dw5_wgrad_geom(d, &nblk, &per_blk);
+    if (!ws || ws_bytes < (int64_t)nblk * DW5_TAPS * d->C * (int64_t)sizeof(float) || ((uintptr_t)ws % 16) != 0)
+        SGX_FAIL(SGX_ERR_WORKSPACE, "dwconv5x5_bwd_weight: workspace too small or unaligned (sgx_dwconv5x5_bwd_weight_workspace)");
+    const dim3 grid((unsigned)nblk, (unsigned)g.ctiles);
+    if (d->stride == 1) SGX_LAUNCH(dwconv5_wgrad_kernel<1>, grid, dim3(DW_THREADS), 0, stream, g, per_blk, x, dy, (float*)ws);
+    else SGX_LAUNCH(dwconv5_wgrad_kernel<2>, grid, dim3(DW_THREADS), 0, stream, g, per_blk, x, dy, (float*)ws);
+    SGX_CHECK_LAUNCH("dwconv5x5_bwd_weight");
+    SGX_LAUNCH(dwconv_wgrad_fold_kernel, dim3((unsigned)sgx_cdiv((long)DW5_TAPS * d->C, 16)), dim3(DW_THREADS), 0, stream, (const float*)ws, nblk, DW5_TAPS * d->C, dw);
+    SGX_CHECK_LAUNCH("dwconv5x5_bwd_weight (fold)");
     return SGX_OK;
 }

@@ -7,6 +7,7 @@
 // The per-image reductions are two-stage and deterministic: a (image, pixel chunk, channel strip) grid leaves fp32 partial rows,
 // a finalize kernel adds them in fp64 in chunk order.  No atomics.
 #include "sgx_common.h"
+#include "sgx_sweep.h"
 
 #define SE_THREADS 256
 #define SE_MAXCG 64      // float4 channel groups per workgroup strip
@@ -203,4 +204,131 @@ extern "C" int32_t sgx_upsample2x_bwd(int32_t N, int32_t H, int32_t W, int32_t C
                (long)dy_ld_img, dx, (long)dx_ld_pix, (long)dx_ld_img, accumulate);
     SGX_CHECK_LAUNCH("upsample2x_bwd");
     return SGX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// BatchNorm -> squeeze-excitation gate -> activation as fused sweeps (MobileNetV3's expanded block: dw -> BN -> SE -> act,
+// classification_models/mobilenetv3.py:103-108).  z = scale[c] * x + shift[c] (NULL scale / shift: z = x, the folded eval form),
+// s = f(pre[n][c]), y = act(s * z).  The per-image means the SE layer needs are affine in the means of x (sgx_image_colsum on the raw
+// convolution output, mapped through scale / shift on the [N,C] matrix): z is never stored.  Rows are pixels, uniformly strided across
+// images (row r belongs to image r / HW).  The data-gradient sweep runs on bn.hip's skeleton: its reduce rows are sgx_bn_bwd_reduce's.
+struct GateZ {
+    float4 s, t;
+    int on;
+    __device__ float4 z(const float4& v) const { return on ? make_float4(s.x * v.x + t.x, s.y * v.y + t.y, s.z * v.z + t.z, s.w * v.w + t.w) : v; }
+};
+__device__ __forceinline__ GateZ gate_z(const float* scale, const float* shift, int c) {
+    const float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    return GateZ{scale ? sgx_ld4(scale + c) : o, scale ? sgx_ld4(shift + c) : o, scale ? 1 : 0};
+}
+__device__ __forceinline__ float4 se_gate4(const float4& p, int gate) { return make_float4(se_gate(p.x, gate), se_gate(p.y, gate), se_gate(p.z, gate), se_gate(p.w, gate)); }
+// gv = dy * act'(s * z)
+__device__ __forceinline__ float4 gate_gv(const float4& d, const float4& z, const float4& s, int act) {
+    return make_float4(d.x * sgx_act6_grad(s.x * z.x, act), d.y * sgx_act6_grad(s.y * z.y, act), d.z * sgx_act6_grad(s.z * z.z, act),
+                       d.w * sgx_act6_grad(s.w * z.w, act));
+}
+
+struct BnGateActFwdF {
+    const float* x; long x_ld; const float* scale; const float* shift; const float* pre; int gate; sgx_fastdiv hw; int C;
+    float* y; long y_ld; int act;
+    struct In { float4 v, p; };
+    __device__ In load(long r, int c) const { return In{sgx_ld4(x + r * x_ld + c), sgx_ld4(pre + (long)sgx_fdiv((int)r, hw) * C + c)}; }
+    typedef GateZ Cst;
+    __device__ Cst consts(int c) const { return gate_z(scale, shift, c); }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&)[1]) const {
+        const float4 z = k.z(in.v), s = se_gate4(in.p, gate);
+        sgx_st4(y + r * y_ld + c, make_float4(sgx_act6(s.x * z.x, act), sgx_act6(s.y * z.y, act), sgx_act6(s.z * z.z, act), sgx_act6(s.w * z.w, act)));
+    }
+};
+#define SE_CHECK_GATE_SWEEP(what)                                                                                                        \
+    SGX_CHECK_ARG(N > 0 && HW > 0 && C > 0 && C % 4 == 0 && (long)N * HW < 0x7fffffffL, "%s: bad dims N=%d HW=%d C=%d", what, N, HW, C);   \
+    SGX_CHECK_ARG(gate >= SGX_GATE_NONE && gate <= SGX_GATE_SIGMOID, "%s: unknown gate %d", what, gate);                                  \
+    SGX_CHECK_ACT4(act, what);                                                                                                           \
+    SGX_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", what)
+extern "C" int32_t sgx_bn_gate_act_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
+                                       float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, int32_t act, void* stream) {
+    SGX_CHECK_ARG(x && pre && y, "bn_gate_act_fwd: null pointer");
+    SE_CHECK_GATE_SWEEP("bn_gate_act_fwd");
+    BnGateActFwdF f{x, x_ld, scale, shift, pre, gate, sgx_make_fastdiv(HW), C, y, y_ld, act};
+    return run_sweep<BnGateActFwdF, 0, 4>(f, (long)N * HW, C, nullptr, stream, "bn_gate_act_fwd");
+}
+
+// d pre[n][c] = f'(pre) * sum over the image's pixels of gv * z: image_colsum's two stages (partials [N][chunks][C], fp64 finalize)
+__global__ __launch_bounds__(SE_THREADS) void bn_gate_bwd_colsum_kernel(SeGeom g, const float* dy, long dy_ld, const float* x, long x_ld, const float* scale,
+                                                                        const float* shift, const float* pre, int gate, int act, float* partials) {
+    __shared__ float4 red[SE_THREADS];
+    const int tid = threadIdx.x;
+    const int cg = tid % g.CG, rl = tid / g.CG;
+    const int c4 = blockIdx.y * g.CG + cg;
+    const int chunk = blockIdx.x % g.chunks, img = blockIdx.x / g.chunks;
+    const bool live = (rl < g.RL) && (c4 < g.C4);
+    const int c = c4 * 4;
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+        int p0 = chunk * SE_CHUNK_ROWS, p1 = p0 + SE_CHUNK_ROWS;
+        if (p1 > g.HW) p1 = g.HW;
+        const GateZ k = gate_z(scale, shift, c);
+        const float4 s = se_gate4(sgx_ld4(pre + (long)img * g.C + c), gate);
+        const long r0 = (long)img * g.HW;
+        for (int p = p0 + rl; p < p1; p += g.RL) {
+            const float4 z = k.z(sgx_ld4(x + (r0 + p) * x_ld + c));
+            const float4 gv = gate_gv(sgx_ld4(dy + (r0 + p) * dy_ld + c), z, s, act);
+            q.x += gv.x * z.x; q.y += gv.y * z.y; q.z += gv.z * z.z; q.w += gv.w * z.w;
+        }
+    }
+    red[tid] = q;
+    __syncthreads();
+    if (live && rl == 0) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int k = 0; k < g.RL; ++k) {
+            float4 a = red[k * g.CG + cg];
+            s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
+        }
+        sgx_st4(partials + ((long)img * g.chunks + chunk) * g.C + c, s);
+    }
+}
+extern "C" int64_t sgx_bn_gate_act_bwd_gate_workspace(int32_t N, int32_t HW, int32_t C) { return sgx_image_colsum_workspace(N, HW, C); }
+extern "C" int32_t sgx_bn_gate_act_bwd_gate(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                            const float* pre, int32_t gate, int32_t act, float* dpre, int32_t N, int32_t HW, int32_t C, void* ws,
+                                            int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(dy && x && pre && dpre && ws, "bn_gate_act_bwd_gate: null pointer");
+    SE_CHECK_GATE_SWEEP("bn_gate_act_bwd_gate");
+    if (ws_bytes < sgx_bn_gate_act_bwd_gate_workspace(N, HW, C)) SGX_FAIL(SGX_ERR_WORKSPACE, "bn_gate_act_bwd_gate: workspace too small (sgx_bn_gate_act_bwd_gate_workspace)");
+    SeGeom g = se_geom(N, HW, C);
+    SGX_LAUNCH(bn_gate_bwd_colsum_kernel, dim3((unsigned)((long)N * g.chunks), g.ctiles), dim3(SE_THREADS), 0, stream, g, dy, (long)dy_ld, x, (long)x_ld, scale,
+               shift, pre, gate, act, (float*)ws);
+    SGX_CHECK_LAUNCH("bn_gate_act_bwd_gate");
+    SGX_LAUNCH(image_colsum_finalize_kernel, dim3(sgx_cdiv((long)N * C, 256)), dim3(256), 0, stream, N, g.chunks, C, (const float*)ws, 1.f, pre, gate, dpre);
+    SGX_CHECK_LAUNCH("bn_gate_act_bwd_gate (finalize)");
+    return SGX_OK;
+}
+
+// dz = gv * s + dmean[n][c] / HW, stored; with `partials` also the rows sum dz, sum dz * (x - save_mean) of the BatchNorm backward
+struct BnGateActBwdDataF {
+    const float* dy; long dy_ld; const float* x; long x_ld; const float* scale; const float* shift; const float* pre; int gate; int act;
+    const float* dmean; float inv_hw; sgx_fastdiv hw; int C; float* dz; long dz_ld; const float* mean;
+    struct In { float4 d, v, p, m; };
+    __device__ In load(long r, int c) const {
+        const long o = (long)sgx_fdiv((int)r, hw) * C + c;
+        return In{sgx_ld4(dy + r * dy_ld + c), sgx_ld4(x + r * x_ld + c), sgx_ld4(pre + o), dmean ? sgx_ld4(dmean + o) : make_float4(0.f, 0.f, 0.f, 0.f)};
+    }
+    struct Cst { GateZ k; float4 mu; };
+    __device__ Cst consts(int c) const { return Cst{gate_z(scale, shift, c), mean ? sgx_ld4(mean + c) : make_float4(0.f, 0.f, 0.f, 0.f)}; }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&q)[2]) const {
+        const float4 v = in.v, mu = k.mu, z = k.k.z(v), s = se_gate4(in.p, gate);
+        const float4 gv = gate_gv(in.d, z, s, act);
+        const float gx = gv.x * s.x + in.m.x * inv_hw, gy = gv.y * s.y + in.m.y * inv_hw, gz = gv.z * s.z + in.m.z * inv_hw, gw = gv.w * s.w + in.m.w * inv_hw;
+        sgx_st4(dz + r * dz_ld + c, make_float4(gx, gy, gz, gw));
+        q[0].x += gx; q[0].y += gy; q[0].z += gz; q[0].w += gw;
+        q[1].x += gx * (v.x - mu.x); q[1].y += gy * (v.y - mu.y); q[1].z += gz * (v.z - mu.z); q[1].w += gw * (v.w - mu.w);
+    }
+};
+extern "C" int32_t sgx_bn_gate_act_bwd_data(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                            const float* pre, int32_t gate, int32_t act, const float* dmean, float* dz, int64_t dz_ld,
+                                            const float* save_mean, float* partials, int32_t N, int32_t HW, int32_t C, void* stream) {
+    SGX_CHECK_ARG(dy && x && pre && dz, "bn_gate_act_bwd_data: null pointer");
+    SE_CHECK_GATE_SWEEP("bn_gate_act_bwd_data");
+    SGX_CHECK_ARG(!partials || save_mean, "bn_gate_act_bwd_data: the reduce rows need save_mean");
+    BnGateActBwdDataF f{dy, dy_ld, x, x_ld, scale, shift, pre, gate, act, dmean, 1.f / (float)HW, sgx_make_fastdiv(HW), C, dz, dz_ld, save_mean};
+    return run_sweep<BnGateActBwdDataF, 2, 2>(f, (long)N * HW, C, partials, stream, "bn_gate_act_bwd_data");
 }

@@ -81,6 +81,7 @@ __device__ __forceinline__ int sgx_fdiv(int n, const sgx_fastdiv& f) {
 #define SGX_ACT_RELU 1
 #define SGX_ACT_SILU 2
 #define SGX_ACT_RELU6 3
+#define SGX_ACT_HSWISH 4
 
 __device__ __forceinline__ float sgx_act(float v, int act) {
     if (act == SGX_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -99,18 +100,22 @@ __device__ __forceinline__ float sgx_act_grad(float v, int act) {
 // The same two with ReLU6 (min(max(v, 0), 6); derivative 1 on 0 < v < 6 and 0 at both ends, ATen's hardtanh backward) - for the entry points
 // that implement it (the affine sweep, the BatchNorm backward, the depthwise convolution).  The convolution kernels keep sgx_act: their
 // code does not change with the fourth activation, and their entry points reject it (SGX_CHECK_ACT3).
+// Hard-swish lives here too and nowhere else: v * relu6(v + 3) / 6 (MobileNetV3's h_swish); derivative as autograd gives it through ReLU6:
+// 0 for v <= -3, 1 for v >= 3, (2 v + 3) / 6 between.
 __device__ __forceinline__ float sgx_act6(float v, int act) {
     if (act == SGX_ACT_RELU6) return fminf(fmaxf(v, 0.f), 6.f);
+    if (act == SGX_ACT_HSWISH) return v * (fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f);
     return sgx_act(v, act);
 }
 __device__ __forceinline__ float sgx_act6_grad(float v, int act) {
     if (act == SGX_ACT_RELU6) return (v > 0.f && v < 6.f) ? 1.f : 0.f;
+    if (act == SGX_ACT_HSWISH) return v <= -3.f ? 0.f : (v >= 3.f ? 1.f : (2.f * v + 3.f) / 6.f);
     return sgx_act_grad(v, act);
 }
 #define SGX_CHECK_ACT3(act, what) \
     SGX_CHECK_ARG((act) >= SGX_ACT_NONE && (act) <= SGX_ACT_SILU, "%s: activation code %d is not implemented by this entry point (none, relu, silu)", what, (int)(act))
 #define SGX_CHECK_ACT4(act, what) \
-    SGX_CHECK_ARG((act) >= SGX_ACT_NONE && (act) <= SGX_ACT_RELU6, "%s: unknown activation code %d", what, (int)(act))
+    SGX_CHECK_ARG((act) >= SGX_ACT_NONE && (act) <= SGX_ACT_HSWISH, "%s: unknown activation code %d", what, (int)(act))
 
 // ---- buffer (SRD) loads: 32-bit per-lane byte offset against a wave-uniform base, hardware bounds check ----------
 // An offset >= the buffer's byte count returns zeros: the conv kernels encode "this element is padding / outside the

@@ -14,7 +14,8 @@ import torch
 from . import _lib
 from ._lib import ConvDesc, LossDesc, MatchDesc, NmsDesc, check, lib, ptr, stream
 
-ACT = {None: 0, "none": 0, "relu": 1, "silu": 2, "relu6": 3}  # relu6: the affine sweep, bn_bwd and the depthwise convolution; the rest reject it
+# relu6 / hswish: the affine sweep, bn_bwd, the depthwise convolutions and the bn_gate_act sweeps; the rest reject them
+ACT = {None: 0, "none": 0, "relu": 1, "silu": 2, "relu6": 3, "hswish": 4}
 
 
 # --------------------------------------------------------------------------------------------- workspace
@@ -500,13 +501,14 @@ def conv2d_bwd_weight(x, dy, dw, dbias=None, stride=1, pad=0):
 
 
 # --------------------------------------------------------------------------------------------- depthwise 3x3 convolution
-def dw_empty(C, device) -> torch.Tensor:
-    """A depthwise filter: logical [C,1,3,3] (nn.Conv2d(groups=C)'s shape), stored [3][3][C]."""
-    return torch.empty(3, 3, C, device=device, dtype=torch.float32).permute(2, 0, 1).unsqueeze(1)
+def dw_empty(C, device, k=3) -> torch.Tensor:
+    """A depthwise filter: logical [C,1,k,k] (nn.Conv2d(groups=C)'s shape), stored [k][k][C]."""
+    return torch.empty(k, k, C, device=device, dtype=torch.float32).permute(2, 0, 1).unsqueeze(1)
 
 
 def to_dw(w: torch.Tensor) -> torch.Tensor:
-    out = dw_empty(w.shape[0], w.device)
+    """(the tap count comes from the shape: [C,1,3,3] or [C,1,5,5])"""
+    out = dw_empty(w.shape[0], w.device, w.shape[2])
     out.copy_(w)
     return out
 
@@ -555,6 +557,58 @@ def dwconv3x3_bwd_weight(x, dy, dw, stride=1):
         dws = d.dw_wgrad_ws = lib().sgx_dwconv3x3_bwd_weight_workspace(d.ref)
     ws = WORKSPACE.get(dws, x.device)
     check(lib().sgx_dwconv3x3_bwd_weight(d.ref, ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel(), stream()), "sgx_dwconv3x3_bwd_weight")
+
+
+# --------------------------------------------------------------------------------------------- depthwise 5x5 convolution
+def _chk_dw5(w: torch.Tensor, C):
+    if tuple(w.shape) != (C, 1, 5, 5) or (w.stride(0), w.stride(2), w.stride(3)) != (1, 5 * C, C):
+        raise _lib.SgxError(f"depthwise filter must be logical [C,1,5,5] stored [5][5][C] for C={C}; got shape {tuple(w.shape)} strides {w.stride()}")
+
+
+def dwconv5x5_fwd(x, w, bias=None, out=None, act=None, stride=1, stat_partials=False):
+    """y = act(dwconv(x, w) + bias), 5x5 pad 2; stat_partials: also the BatchNorm statistics rows of y (then no bias / activation)."""
+    C = x.shape[3]
+    _chk_dw5(w, C)
+    if out is None:
+        out = torch.empty(conv_out_shape(x, C, 5, 5, stride, 2), device=x.device, dtype=torch.float32)
+    d = conv_desc(x, C, 5, 5, stride, 2, out)
+    parts = None
+    if stat_partials:
+        nblk = lib().sgx_dwconv5x5_stat_blocks(d.ref)
+        if nblk <= 0:
+            check(-1, "sgx_dwconv5x5_stat_blocks")
+        parts = torch.empty(2, nblk, C, device=x.device, dtype=torch.float32)
+    check(lib().sgx_dwconv5x5_fwd(d.ref, ptr(x), ptr(w), ptr(bias), ptr(out), ACT[act], ptr(parts), stream()), "sgx_dwconv5x5_fwd")
+    return (out, parts) if stat_partials else out
+
+
+def dwconv5x5_bwd_data(dy, w, x_shape, stride=1, out=None, accumulate=False):
+    C = x_shape[3]
+    _chk_dw5(w, C)
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("dwconv5x5_bwd_data: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
+    d = conv_desc(out, C, 5, 5, stride, 2, dy)
+    check(lib().sgx_dwconv5x5_bwd_data(d.ref, ptr(dy), ptr(w), ptr(out), int(accumulate), stream()), "sgx_dwconv5x5_bwd_data")
+    return out
+
+
+def dwconv5x5_bwd_weight(x, dy, dw, stride=1):
+    """dw (logical [C,1,5,5], stored [5][5][C]) += grad."""
+    C = x.shape[3]
+    _chk_dw5(dw, C)
+    d = conv_desc(x, C, 5, 5, stride, 2, dy)
+    dws = getattr(d, "dw_wgrad_ws", None)
+    if dws is None:
+        dws = d.dw_wgrad_ws = lib().sgx_dwconv5x5_bwd_weight_workspace(d.ref)
+    ws = WORKSPACE.get(dws, x.device)
+    check(lib().sgx_dwconv5x5_bwd_weight(d.ref, ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel(), stream()), "sgx_dwconv5x5_bwd_weight")
+
+
+def set_dwconv5x5_form(form: str):
+    """Which 5x5 forward runs: "register" (the default) or "lds" - a measurement switch (tools/dwconv_bench.py)."""
+    check(lib().sgx_debug_set_dwconv5x5_form({"register": 0, "lds": 1}[form]), "sgx_debug_set_dwconv5x5_form")
 
 
 _TICKETS = {}
@@ -962,6 +1016,58 @@ def channel_gate(x, pre, gate, bias=None, bias_scale=1.0, out=None, accumulate=F
     yl, yi = nhwc_strides(out)
     check(lib().sgx_channel_gate(n, h * w, c, ptr(x), xl, xi, ptr(pre), GATE[gate], ptr(bias), float(bias_scale), ptr(out), yl, yi, int(accumulate), stream()),
           "sgx_channel_gate")
+    return out
+
+
+def _gate_rows(x):
+    n, h, w, c = x.shape
+    return n, h * w, c, rows(x)[1]
+
+
+def bn_gate_act_fwd(x, scale, shift, pre, gate, act=None, out=None):
+    """y = act(f(pre[n,c]) * (scale * x + shift)); scale = shift = None: z = x (the folded eval form)."""
+    n, hw, c, ld = _gate_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(lib().sgx_bn_gate_act_fwd(ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ptr(out), rows(out)[1], n, hw, c, ACT[act], stream()),
+          "sgx_bn_gate_act_fwd")
+    return out
+
+
+def bn_gate_act_bwd_gate(dy, x, scale, shift, pre, gate, act=None):
+    """dpre[n,c] = f'(pre) * sum_pixels gv * z, gv = dy * act'(f(pre) * z)."""
+    n, hw, c, ld = _gate_rows(x)
+    out = torch.empty(n, c, device=x.device, dtype=torch.float32)
+    ws = WORKSPACE.get(lib().sgx_bn_gate_act_bwd_gate_workspace(n, hw, c), x.device)
+    check(lib().sgx_bn_gate_act_bwd_gate(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(out), n, hw, c, ptr(ws),
+                                         ws.numel(), stream()), "sgx_bn_gate_act_bwd_gate")
+    return out
+
+
+def bn_gate_act_bwd_data(dy, x, scale, shift, pre, gate, act=None, dmean=None, save_mean=None, out=None, want_parts=False):
+    """dz = gv * f(pre) + dmean[n,c] / HW -> dz, or (dz, parts) with the BatchNorm-backward reduce rows of (dz, x) (bn_bwd(parts=...))."""
+    n, hw, c, ld = _gate_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    parts = torch.empty(2, stats_blocks(n * hw), c, device=x.device, dtype=torch.float32) if want_parts else None
+    check(lib().sgx_bn_gate_act_bwd_data(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(dmean), ptr(out),
+                                         rows(out)[1], ptr(save_mean), ptr(parts), n, hw, c, stream()), "sgx_bn_gate_act_bwd_data")
+    return (out, parts) if want_parts else out
+
+
+def dropout(x, p, seed, offset=0, out=None):
+    """y = x * mask / (1 - p) over a [M, C] matrix or an NHWC view; the backward is the same call on dy with the same (seed, offset)."""
+    if x.dim() == 2:
+        M, C = x.shape
+        ld = x.stride(0) if M > 1 else C
+        if x.stride(1) != 1 and C > 1:
+            raise _lib.SgxError("dropout: columns must be contiguous")
+    else:
+        (M, ld), C = rows(x), x.shape[3]
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    ldo = (out.stride(0) if out.shape[0] > 1 else C) if out.dim() == 2 else rows(out)[1]
+    check(lib().sgx_dropout_fwd(ptr(x), ld, ptr(out), ldo, M, C, float(p), int(seed), int(offset), stream()), "sgx_dropout_fwd")
     return out
 
 

@@ -17,12 +17,12 @@ from .layers import BatchNorm, ConvLayer, DepthwiseConvLayer, act_name
 
 
 def _conv_layer(in_channels, out_channels, kernel_size, stride, padding, groups):
-    """groups == 1: the implicit-GEMM ConvLayer; groups == in == out with a 3x3 pad-1 filter: the depthwise layer; anything else raises."""
+    """groups == 1: the implicit-GEMM ConvLayer; groups == in == out with a 3x3 pad-1 or 5x5 pad-2 filter: the depthwise layer; anything else raises."""
     if groups in (None, 1):
         return ConvLayer(in_channels, out_channels, kernel_size, stride, padding, bias=False)
-    if groups == in_channels == out_channels and kernel_size == 3 and padding == 1:
-        return DepthwiseConvLayer(in_channels, stride)
-    raise NotImplementedError(f"grouped convolution on the HIP path: groups=1, or depthwise 3x3 pad 1 (groups == in_channels == out_channels); got groups={groups}, "
+    if groups == in_channels == out_channels and (kernel_size, padding) in ((3, 1), (5, 2)):
+        return DepthwiseConvLayer(in_channels, stride, kernel_size)
+    raise NotImplementedError(f"grouped convolution on the HIP path: groups=1, or depthwise 3x3 pad 1 / 5x5 pad 2 (groups == in_channels == out_channels); got groups={groups}, "
                               f"{in_channels} -> {out_channels}, kernel {kernel_size}, padding {padding}")
 
 
@@ -30,6 +30,7 @@ class _ConvBN(SgxBlock):
     """Shared implementation; subclasses only choose where `conv`/`bn` are registered (key names)."""
 
     _folded = None  # (filter with the BatchNorm scale folded in, shift as bias): eval form set by prep_model_for_conversion
+    _gate = None  # (SELayer,) between BatchNorm and activation (ConvBNView(gate=...)): the block then runs on the fused bn_gate_act sweeps
     _folded_half = None  # the same for a channel-padded filter (C % 4 != 0: an RGB stem) - read by the half-precision path only, which re-lays filters out itself
 
     def _parts(self):
@@ -50,7 +51,7 @@ class _ConvBN(SgxBlock):
         if conv.depthwise:  # act(dwconv(x, w * s[c]) + t[c]): bias and activation (ReLU6 included) live in the depthwise epilogue
             with torch.no_grad():
                 s = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
-                wf = K.dw_empty(w.shape[0], w.device)
+                wf = K.dw_empty(w.shape[0], w.device, w.shape[2])
                 wf.copy_(w.detach() * s.view(-1, 1, 1, 1))
                 self._folded = (wf, (bn.bias.detach() - bn.running_mean * s).contiguous())
             return
@@ -83,6 +84,9 @@ class _ConvBN(SgxBlock):
         if residual is not None:
             if self.act is not None or post_add is not None or x.dtype == K.HALF:
                 raise RuntimeError("residual rides in the affine sweep of a layer without activation (fp32)")
+        gate = self._gate[0] if self._gate is not None else None
+        if gate is not None and (residual is not None or post_add is not None or x.dtype == K.HALF):
+            raise RuntimeError("a gate between BatchNorm and activation: fp32, no residual, no post_add")
         if x.dtype == K.HALF:  # half-precision inference: the folded deployment form, everything in ONE bf16 launch
             folded = self._folded if self._folded is not None else self._folded_half
             if self.training or folded is None:
@@ -96,17 +100,26 @@ class _ConvBN(SgxBlock):
             t, parts = conv.conv(x, stats=True)
             M = t.shape[0] * t.shape[1] * t.shape[2]
             scale, shift, mean, invstd = bn.scale_shift(parts, M, True)
-            if post_add is None:
+            if gate is not None:
+                y = gate.fwd_fused(t, scale, shift, self.act, out=out)
+            elif post_add is None:
                 y = K.affine_act(t, scale, shift, r1=residual, act=self.act, out=out)
             else:
                 y = K.tri_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out)
             self._ctx = (x, t, scale, shift, mean, invstd)
             self._req = None
             return y
+        if gate is not None:  # eval: dwconv + bias (folded) or the plain convolution, then the gate sweep with / without the BatchNorm affine
+            if self._folded is not None and conv.depthwise:
+                t = conv.conv_with(x, self._folded[0], self._folded[1])
+                return gate.fwd_fused(t, None, None, self.act, out=out if out is not None else t)
+            t = conv.conv(x)
+            scale, shift, _, _ = bn.scale_shift(None, 0, False)
+            return gate.fwd_fused(t, scale, shift, self.act, out=out if out is not None else t)
         if self._folded is not None and post_add is None:
             if conv.depthwise and residual is None:
-                return K.dwconv3x3_fwd(x, self._folded[0], bias=self._folded[1], out=out, act=self.act, stride=conv.stride)
-            if self.act == "relu6":  # the conv epilogues do not carry ReLU6: conv + bias, then the sweep in place
+                return conv.conv_with(x, self._folded[0], self._folded[1], out=out, act=self.act)
+            if self.act in ("relu6", "hswish"):  # the conv epilogues do not carry ReLU6 / hard-swish: conv + bias, then the sweep in place
                 t = K.conv2d_fwd(x, self._folded[0], bias=self._folded[1], stride=conv.stride, pad=conv.padding)
                 return K.affine_act(t, act=self.act, out=out if out is not None else t)
             if not conv.depthwise:
@@ -122,7 +135,8 @@ class _ConvBN(SgxBlock):
         hands it to that launch; bwd() then finds the partial sums ready and skips its own reduce sweep).  None when it cannot be handed over
         (synchronised BatchNorm reduces across ranks on its own path)."""
         conv, bn = self._parts()
-        if self._ctx is None or bn._synced() or not self._net.fuse_bn_reduce or self.act == "relu6":  # (the data-gradient epilogues do not carry ReLU6)
+        if self._ctx is None or bn._synced() or not self._net.fuse_bn_reduce or self.act in ("relu6", "hswish") or self._gate is not None:
+            # (the data-gradient epilogues carry neither ReLU6 nor hard-swish nor a gate)
             return None
         _, t, scale, shift, mean, _ = self._ctx
         self._req = K.BnReduceRequest(t, scale, shift, mean, self.act)
@@ -134,7 +148,11 @@ class _ConvBN(SgxBlock):
         (x, t, scale, shift, mean, invstd), self._ctx = self._ctx, None
         req, self._req = getattr(self, "_req", None), None
         parts = req.parts if req is not None else None
-        dt = bn.backward(dy, t, scale, shift, mean, invstd, self.act, dx_out=t, parts=parts)  # in place over the saved conv output
+        if self._gate is not None:  # dz and the BatchNorm-backward reduce rows from the gate's data-gradient sweep (in place over dy)
+            dz, parts = self._gate[0].bwd_fused(dy, t, scale, shift, mean, self.act)
+            dt = bn.backward(dz, t, scale, shift, mean, invstd, None, dx_out=t, parts=parts)
+        else:
+            dt = bn.backward(dy, t, scale, shift, mean, invstd, self.act, dx_out=t, parts=parts)  # in place over the saved conv output
         conv.wgrad(x, dt)
         if not need_dx:
             return None
@@ -197,10 +215,12 @@ class ConvBNView(_ConvBN):
     """conv -> BatchNorm -> activation over layers that are registered ELSEWHERE (the numbered entries of a reference nn.Sequential that holds
     several such triples: InvertedResidual.conv, mobilenetv2.py:70-93).  Owns no parameter: it adds nothing to the state_dict."""
 
-    def __init__(self, conv, bn, activation_type=None):
+    def __init__(self, conv, bn, activation_type=None, gate=None):
+        """gate: an SELayer (registered elsewhere too) that sits between the BatchNorm and the activation - y = act(se(bn(conv(x))))."""
         super().__init__()
         self._pair = (conv, bn)  # (a tuple: not registered as sub-modules)
         self.act = act_name(activation_type)
+        self._gate = (gate,) if gate is not None else None
 
     def _parts(self):
         return self._pair

@@ -178,10 +178,10 @@ class SgxNetwork(nn.Module):
                 view = flat.view(C_, 2, 2, K_).permute(0, 3, 1, 2)
                 gview = gflat.view(C_, 2, 2, K_).permute(0, 3, 1, 2)
                 s.kernel_view, s.grad_kernel_view = view, gview
-            elif s.kind == "dwconv":  # depthwise 3x3: logical [C,1,3,3], stored [3][3][C]
-                C_ = old.shape[0]
-                view = flat.view(3, 3, C_).permute(2, 0, 1).unsqueeze(1)
-                gview = gflat.view(3, 3, C_).permute(2, 0, 1).unsqueeze(1)
+            elif s.kind == "dwconv":  # depthwise k x k (3 or 5, from the shape): logical [C,1,k,k], stored [k][k][C]
+                C_, k_ = old.shape[0], old.shape[2]
+                view = flat.view(k_, k_, C_).permute(2, 0, 1).unsqueeze(1)
+                gview = gflat.view(k_, k_, C_).permute(2, 0, 1).unsqueeze(1)
                 s.kernel_view, s.grad_kernel_view = view, gview
             else:
                 view, gview = flat.view(old.shape), gflat.view(old.shape)

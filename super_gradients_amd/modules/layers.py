@@ -3,7 +3,7 @@ reference's Conv2d / BatchNorm2d / ReLU / ConvTranspose2d / MaxPool2d / Linear m
 
 Every class keeps the reference's parameter names and logical shapes (state_dict compatible):
   ConvLayer        nn.Conv2d                         weight [K,C,R,S] (+ bias)      modules/conv_bn_act_block.py:88
-  DepthwiseConvLayer nn.Conv2d(C, C, 3, s, 1, groups=C) weight [C,1,3,3]             classification_models/mobilenetv2.py:73,87
+  DepthwiseConvLayer nn.Conv2d(C, C, k, s, k // 2, groups=C) weight [C,1,k,k], k = 3 / 5  classification_models/mobilenetv2.py:73,87, mobilenetv3.py:88,104
   BatchNorm        nn.BatchNorm2d                    weight, bias, running_mean, running_var, num_batches_tracked
   ConvTranspose2x2 nn.ConvTranspose2d(k=2,s=2)       weight [C,K,2,2], bias          modules/sampling.py:72-73
   LinearLayer      nn.Linear                         weight [K,C], bias              classification_models/resnet.py:186
@@ -18,7 +18,7 @@ from torch import nn
 from .. import kernels as K
 from .engine import SgxBlock
 
-ACT_NAMES = {None: None, "none": None, "identity": None, "relu": "relu", "silu": "silu", "swish": "silu", "relu6": "relu6"}
+ACT_NAMES = {None: None, "none": None, "identity": None, "relu": "relu", "silu": "silu", "swish": "silu", "relu6": "relu6", "hswish": "hswish", "hardswish": "hswish"}
 
 
 def act_name(activation_type) -> str:
@@ -28,7 +28,7 @@ def act_name(activation_type) -> str:
     if isinstance(activation_type, str):
         key = activation_type.lower()
         if key not in ACT_NAMES:
-            raise ValueError(f"activation '{activation_type}' is not available on the HIP path (relu, relu6, silu, none)")
+            raise ValueError(f"activation '{activation_type}' is not available on the HIP path (relu, relu6, silu, hswish, none)")
         return ACT_NAMES[key]
     if isinstance(activation_type, type):
         if issubclass(activation_type, nn.ReLU6):  # (a subclass of nn.Hardtanh, not of nn.ReLU)
@@ -37,6 +37,8 @@ def act_name(activation_type) -> str:
             return "relu"
         if issubclass(activation_type, nn.SiLU):
             return "silu"
+        if issubclass(activation_type, nn.Hardswish):
+            return "hswish"
         if issubclass(activation_type, nn.Identity):
             return None
     raise ValueError(f"activation {activation_type!r} is not available on the HIP path (relu, relu6, silu, none)")
@@ -99,26 +101,30 @@ class ConvLayer(SgxBlock):
 
 
 class DepthwiseConvLayer(SgxBlock):
-    """Depthwise 3x3 convolution (pad 1, stride 1 or 2): parameters + the three depthwise kernels, with ConvLayer's interface.  The filter is
-    stored [3][3][C] in the arena (the parameter is the reference's [C,1,3,3] as a strided view).  Per-channel stencils: no transposed
-    filter for the data gradient, and the weight gradient (a per-channel reduction, not a GEMM) does not join the grouped queue."""
+    """Depthwise 3x3 (pad 1) or 5x5 (pad 2) convolution, stride 1 or 2: parameters + the three depthwise kernels, with ConvLayer's interface.
+    The filter is stored [k][k][C] in the arena (the parameter is the reference's [C,1,k,k] as a strided view).  Per-channel stencils: no
+    transposed filter for the data gradient, and the weight gradient (a per-channel reduction, not a GEMM) does not join the grouped queue."""
 
     _param_kinds = {"weight": "dwconv"}
     depthwise = True
 
-    def __init__(self, channels, stride=1):
+    def __init__(self, channels, stride=1, kernel_size=3):
         super().__init__()
+        if kernel_size not in (3, 5):
+            raise NotImplementedError(f"depthwise convolution on the HIP path: kernel size 3 or 5, got {kernel_size}")
         if stride not in (1, 2):
             raise NotImplementedError(f"depthwise convolution on the HIP path: stride 1 or 2, got {stride}")
         if channels % 4:
             raise NotImplementedError(f"depthwise convolution on the HIP path: channels must be a multiple of 4 (16-byte channel groups), got {channels}")
         self.in_channels = self.out_channels = channels
-        self.kernel_size, self.stride, self.padding = 3, stride, 1
-        w = torch.empty(channels, 1, 3, 3)
+        self.kernel_size, self.stride, self.padding = kernel_size, stride, kernel_size // 2
+        w = torch.empty(channels, 1, kernel_size, kernel_size)
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))  # nn.Conv2d default
         self.weight = nn.Parameter(w)
         self.register_parameter("bias", None)
         self._w = self._gw = None
+        self._fwd, self._dgrad, self._wgrad = ((K.dwconv3x3_fwd, K.dwconv3x3_bwd_data, K.dwconv3x3_bwd_weight) if kernel_size == 3 else
+                                               (K.dwconv5x5_fwd, K.dwconv5x5_bwd_data, K.dwconv5x5_bwd_weight))
 
     def on_materialize(self):
         slots = {s.param: s for s in self._net.slots}
@@ -128,10 +134,14 @@ class DepthwiseConvLayer(SgxBlock):
     def conv(self, x, out=None, act=None, addend=None, stats=False):
         if addend is not None:
             raise NotImplementedError("the depthwise convolution has no pre-activation addend")
-        return K.dwconv3x3_fwd(x, self._w, out=out, act=act, stride=self.stride, stat_partials=stats)
+        return self._fwd(x, self._w, out=out, act=act, stride=self.stride, stat_partials=stats)
+
+    def conv_with(self, x, w, bias, out=None, act=None):
+        """act(dwconv(x, w) + bias) with a filter that is not the parameter (the folded eval form)"""
+        return self._fwd(x, w, bias=bias, out=out, act=act, stride=self.stride)
 
     def wgrad(self, x, dy, bias_grad=True):
-        self._net.fork_side(lambda: K.dwconv3x3_bwd_weight(x, dy, self._gw, stride=self.stride), x, dy)
+        self._net.fork_side(lambda: self._wgrad(x, dy, self._gw, stride=self.stride), x, dy)
 
     def dgrad(self, dy, x_shape, out=None, accumulate=False, addend=None, reqs=None):
         if reqs:  # (the producing layer would skip its own reduce sweep and read rows nobody wrote)
@@ -142,7 +152,7 @@ class DepthwiseConvLayer(SgxBlock):
             else:
                 out = K.axpy(addend, out=out)
             accumulate = True
-        return K.dwconv3x3_bwd_data(dy, self._w, x_shape, stride=self.stride, out=out, accumulate=accumulate)
+        return self._dgrad(dy, self._w, x_shape, stride=self.stride, out=out, accumulate=accumulate)
 
 
 class BatchNorm(SgxBlock):

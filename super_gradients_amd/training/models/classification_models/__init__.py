@@ -2,3 +2,4 @@ from .resnet import (BasicResNetBlock, Bottleneck, CifarResNet, ResNet, ResNet18
                      ResNet152, ResNet50_3343)
 from .repvgg import (RepVGG, RepVggA0, RepVggA1, RepVggA2, RepVggB0, RepVggB1, RepVggB2, RepVggB3, RepVggCustom, RepVggD2SE)  # noqa: F401
 from .mobilenetv2 import CustomMobileNetV2, InvertedResidual, MobileNetV2, MobileNetV2_135, MobileNetV2Base  # noqa: F401
+from .mobilenetv3 import MobileNetV3, mobilenetv3_custom, mobilenetv3_large, mobilenetv3_small  # noqa: F401
