@@ -513,6 +513,26 @@ int32_t sgx_dwconv5x5_bwd_weight(const sgx_conv_desc* d, const float* x, const f
                                  void* stream);
 int32_t sgx_debug_set_dwconv5x5_form(int32_t form);
 
+/* Grouped 3x3 convolution, pad 1, stride 1 or 2, 1 < groups < C: nn.Conv2d(C, C, 3, stride, 1, groups=G, bias=False) of
+ *   training/models/classification_models/regnet.py (XBlock.conv_block_2) and resnext.py (GroupedConvBlock.conv2), and its backward.
+ * d: an sgx_conv_desc with K == C, R == S == 3, pad == 1, stride in {1, 2}; the descriptor itself carries no group count (other code reads
+ * it as "groups = 1"), so `groups` is an argument: C % groups == 0 and C / groups in {4, 8, 16, 32, 64}.  Anything else: SGX_ERR_BAD_ARG.
+ * Filter storage [K][3][3][cg], the dense layout with C := cg: the reference's [K, cg, 3, 3] parameter is a strided view of it.
+ * fp32 matrix pipe (16x16x4 tiles; below 16 channels per group a tile is block-diagonal).  Deterministic: no atomics, fixed fold orders.
+ * fwd: y = act(gconv(x, w) + bias), act none / relu / silu; stat_partials as in sgx_dwconv3x3_fwd with sgx_gconv3x3_stat_blocks rows.
+ * bwd_data: dx (+)= the data gradient, d describes the FORWARD problem; gather form (stride 2: one launch per parity class of dx pixels, the
+ *   taps of matching parity only); the filter is read transposed in the launch, so the workspace is 0 bytes and ws may be NULL.
+ * bwd_weight: dw += ...; per-workgroup partial filters in ws (sgx_gconv3x3_bwd_weight_workspace bytes, 16-byte aligned), then the fp64 fold. */
+int32_t sgx_gconv3x3_stat_blocks(const sgx_conv_desc* d, int32_t groups);
+int32_t sgx_gconv3x3_fwd(const sgx_conv_desc* d, int32_t groups, const float* x, const float* w, const float* bias, float* y,
+                         int32_t act, float* stat_partials, void* stream);
+int64_t sgx_gconv3x3_bwd_data_workspace(const sgx_conv_desc* d, int32_t groups);
+int32_t sgx_gconv3x3_bwd_data(const sgx_conv_desc* d, int32_t groups, const float* dy, const float* w, float* dx, int32_t accumulate,
+                              void* ws, int64_t ws_bytes, void* stream);
+int64_t sgx_gconv3x3_bwd_weight_workspace(const sgx_conv_desc* d, int32_t groups);
+int32_t sgx_gconv3x3_bwd_weight(const sgx_conv_desc* d, int32_t groups, const float* x, const float* dy, float* dw, void* ws,
+                                int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Squeeze-excitation gates and nearest up-sampling of PP-YOLOE:
  *   EffectiveSEBlock.forward  modules/se_blocks.py:39-42     x * hardsigmoid(project(mean_hw(x)))

@@ -188,6 +188,12 @@ PROTOTYPES = {
     "sgx_dwconv5x5_bwd_weight_workspace": (_i64, [_CD]),
     "sgx_dwconv5x5_bwd_weight": (_i32, [_CD, _P, _P, _P, _P, _i64, _P]),
     "sgx_debug_set_dwconv5x5_form": (_i32, [_i32]),
+    "sgx_gconv3x3_stat_blocks": (_i32, [_CD, _i32]),
+    "sgx_gconv3x3_fwd": (_i32, [_CD, _i32, _P, _P, _P, _P, _i32, _P, _P]),
+    "sgx_gconv3x3_bwd_data_workspace": (_i64, [_CD, _i32]),
+    "sgx_gconv3x3_bwd_data": (_i32, [_CD, _i32, _P, _P, _P, _i32, _P, _i64, _P]),
+    "sgx_gconv3x3_bwd_weight_workspace": (_i64, [_CD, _i32]),
+    "sgx_gconv3x3_bwd_weight": (_i32, [_CD, _i32, _P, _P, _P, _P, _i64, _P]),
     "sgx_bn_gate_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i32, _P, _i64, _i32, _i32, _i32, _i32, _P]),
     "sgx_bn_gate_act_bwd_gate_workspace": (_i64, [_i32] * 3),
     "sgx_bn_gate_act_bwd_gate": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _P, _i64, _P]),

@@ -1102,3 +1102,6 @@ extern "C" int32_t sgx_dwconv5x5_bwd_weight(const sgx_conv_desc* d, const float*
     SGX_CHECK_LAUNCH("dwconv5x5_bwd_weight (fold)");
     return SGX_OK;
 }
+
+// Grouped 3x3 convolution (1 < groups < C): MFMA tiles over an LDS patch; shares dw_check and the weight-gradient fold above.
+#include "gconv.h"

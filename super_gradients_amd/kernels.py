@@ -611,6 +611,58 @@ def set_dwconv5x5_form(form: str):
     check(lib().sgx_debug_set_dwconv5x5_form({"register": 0, "lds": 1}[form]), "sgx_debug_set_dwconv5x5_form")
 
 
+# --------------------------------------------------------------------------------------------- grouped 3x3 convolution (1 < groups < C)
+def _chk_gw(w: torch.Tensor, C, groups):
+    if groups <= 0 or C % groups:
+        raise _lib.SgxError(f"grouped convolution: groups={groups} does not divide C={C}")
+    _chk_w(w, C, 3, 3, C // groups)
+
+
+def gconv3x3_fwd(x, w, groups, bias=None, out=None, act=None, stride=1, stat_partials=False):
+    """y = act(gconv(x, w) + bias), 3x3 pad 1, w logical [C, C / groups, 3, 3] in OHWI memory; stat_partials: also the BatchNorm
+    statistics rows of y (then no bias / activation)."""
+    C = x.shape[3]
+    _chk_gw(w, C, groups)
+    if out is None:
+        out = torch.empty(conv_out_shape(x, C, 3, 3, stride, 1), device=x.device, dtype=torch.float32)
+    d = conv_desc(x, C, 3, 3, stride, 1, out)
+    parts = None
+    if stat_partials:
+        nblk = lib().sgx_gconv3x3_stat_blocks(d.ref, groups)
+        if nblk <= 0:
+            check(-1, "sgx_gconv3x3_stat_blocks")
+        parts = torch.empty(2, nblk, C, device=x.device, dtype=torch.float32)
+    check(lib().sgx_gconv3x3_fwd(d.ref, groups, ptr(x), ptr(w), ptr(bias), ptr(out), ACT[act], ptr(parts), stream()), "sgx_gconv3x3_fwd")
+    return (out, parts) if stat_partials else out
+
+
+def gconv3x3_bwd_data(dy, w, groups, x_shape, stride=1, out=None, accumulate=False):
+    C = x_shape[3]
+    _chk_gw(w, C, groups)
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("gconv3x3_bwd_data: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
+    d = conv_desc(out, C, 3, 3, stride, 1, dy)
+    check(lib().sgx_gconv3x3_bwd_data(d.ref, groups, ptr(dy), ptr(w), ptr(out), int(accumulate), None, 0, stream()), "sgx_gconv3x3_bwd_data")
+    return out
+
+
+def gconv3x3_bwd_weight(x, dy, dw, groups, stride=1):
+    """dw (logical [C, C / groups, 3, 3], OHWI memory) += grad."""
+    C = x.shape[3]
+    _chk_gw(dw, C, groups)
+    d = conv_desc(x, C, 3, 3, stride, 1, dy)
+    sizes = d.__dict__.setdefault("gconv_wgrad_ws", {})
+    if groups not in sizes:
+        sizes[groups] = lib().sgx_gconv3x3_bwd_weight_workspace(d.ref, groups)
+        if sizes[groups] <= 0:
+            del sizes[groups]
+            check(-1, "sgx_gconv3x3_bwd_weight_workspace")
+    ws = WORKSPACE.get(sizes[groups], x.device)
+    check(lib().sgx_gconv3x3_bwd_weight(d.ref, groups, ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel(), stream()), "sgx_gconv3x3_bwd_weight")
+
+
 _TICKETS = {}
 
 

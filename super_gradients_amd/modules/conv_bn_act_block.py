@@ -13,17 +13,22 @@ from torch import nn
 
 from .. import kernels as K
 from .engine import SgxBlock
-from .layers import BatchNorm, ConvLayer, DepthwiseConvLayer, act_name
+from .layers import GROUPED_CG, BatchNorm, ConvLayer, DepthwiseConvLayer, GroupedConvLayer, act_name
 
 
 def _conv_layer(in_channels, out_channels, kernel_size, stride, padding, groups):
-    """groups == 1: the implicit-GEMM ConvLayer; groups == in == out with a 3x3 pad-1 or 5x5 pad-2 filter: the depthwise layer; anything else raises."""
+    """groups == 1: the implicit-GEMM ConvLayer; groups == in == out with a 3x3 pad-1 or 5x5 pad-2 filter: the depthwise layer; 1 < groups < in == out
+    with a 3x3 pad-1 filter and 4, 8, 16, 32 or 64 channels per group: the grouped layer; anything else raises."""
     if groups in (None, 1):
         return ConvLayer(in_channels, out_channels, kernel_size, stride, padding, bias=False)
     if groups == in_channels == out_channels and (kernel_size, padding) in ((3, 1), (5, 2)):
         return DepthwiseConvLayer(in_channels, stride, kernel_size)
-    raise NotImplementedError(f"grouped convolution on the HIP path: groups=1, or depthwise 3x3 pad 1 / 5x5 pad 2 (groups == in_channels == out_channels); got groups={groups}, "
-                              f"{in_channels} -> {out_channels}, kernel {kernel_size}, padding {padding}")
+    if (1 < groups < in_channels and in_channels == out_channels and (kernel_size, padding) == (3, 1) and in_channels % groups == 0
+            and in_channels // groups in GROUPED_CG and stride in (1, 2)):
+        return GroupedConvLayer(in_channels, groups, stride)
+    raise NotImplementedError(f"grouped convolution on the HIP path: groups=1, depthwise 3x3 pad 1 / 5x5 pad 2 (groups == in_channels == out_channels), or 3x3 pad 1 "
+                              f"stride 1 / 2 with in_channels == out_channels and in_channels / groups in {GROUPED_CG}; got groups={groups}, "
+                              f"{in_channels} -> {out_channels}, kernel {kernel_size}, stride {stride}, padding {padding}")
 
 
 class _ConvBN(SgxBlock):
@@ -91,6 +96,8 @@ class _ConvBN(SgxBlock):
             folded = self._folded if self._folded is not None else self._folded_half
             if self.training or folded is None:
                 raise RuntimeError("half-precision inference runs the folded deployment form: call prep_model_for_conversion() in eval mode first")
+            if conv.grouped:
+                raise NotImplementedError("the grouped convolution has no half-precision kernel")
             return K.conv2d_fwd(x, folded[0], bias=folded[1], out=out, act=self.act, stride=conv.stride, pad=conv.padding,
                                 post_add=post_add, post_scale=post_scale)
         if post_scale is not None:
@@ -110,7 +117,7 @@ class _ConvBN(SgxBlock):
             self._req = None
             return y
         if gate is not None:  # eval: dwconv + bias (folded) or the plain convolution, then the gate sweep with / without the BatchNorm affine
-            if self._folded is not None and conv.depthwise:
+            if self._folded is not None and (conv.depthwise or conv.grouped):
                 t = conv.conv_with(x, self._folded[0], self._folded[1])
                 return gate.fwd_fused(t, None, None, self.act, out=out if out is not None else t)
             t = conv.conv(x)
@@ -119,6 +126,10 @@ class _ConvBN(SgxBlock):
         if self._folded is not None and post_add is None:
             if conv.depthwise and residual is None:
                 return conv.conv_with(x, self._folded[0], self._folded[1], out=out, act=self.act)
+            if conv.grouped:  # act(gconv(x, w) + bias) in one launch; ReLU6 / hard-swish and a residual take the sweep after it
+                own = self.act not in ("relu6", "hswish") and residual is None
+                t = conv.conv_with(x, self._folded[0], self._folded[1], out=out if own else None, act=self.act if own else None)
+                return t if own else K.affine_act(t, r1=residual, act=self.act, out=out if out is not None else t)
             if self.act in ("relu6", "hswish"):  # the conv epilogues do not carry ReLU6 / hard-swish: conv + bias, then the sweep in place
                 t = K.conv2d_fwd(x, self._folded[0], bias=self._folded[1], stride=conv.stride, pad=conv.padding)
                 return K.affine_act(t, act=self.act, out=out if out is not None else t)
@@ -178,7 +189,7 @@ class _Seq(nn.Module):
 
 
 class ConvBNAct(_ConvBN):
-    """Reference `ConvBNAct` (conv_bn_act_block.py:9-69), supported subset: groups=1, dilation=1, zero padding, use_normalization=True."""
+    """Reference `ConvBNAct` (conv_bn_act_block.py:9-69), supported subset: groups as `_conv_layer` routes them (1, depthwise, grouped 3x3), dilation=1, zero padding, use_normalization=True."""
 
     def __init__(self, in_channels, out_channels, kernel_size, padding=0, activation_type=None, stride=1, dilation=1, groups=1, bias=True,
                  padding_mode="zeros", use_normalization=True, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True,

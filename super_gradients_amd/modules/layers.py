@@ -4,6 +4,7 @@ reference's Conv2d / BatchNorm2d / ReLU / ConvTranspose2d / MaxPool2d / Linear m
 Every class keeps the reference's parameter names and logical shapes (state_dict compatible):
   ConvLayer        nn.Conv2d                         weight [K,C,R,S] (+ bias)      modules/conv_bn_act_block.py:88
   DepthwiseConvLayer nn.Conv2d(C, C, k, s, k // 2, groups=C) weight [C,1,k,k], k = 3 / 5  classification_models/mobilenetv2.py:73,87, mobilenetv3.py:88,104
+  GroupedConvLayer nn.Conv2d(C, C, 3, s, 1, groups=G), 1 < G < C   weight [C,C/G,3,3]    classification_models/regnet.py (XBlock), resnext.py (conv2)
   BatchNorm        nn.BatchNorm2d                    weight, bias, running_mean, running_var, num_batches_tracked
   ConvTranspose2x2 nn.ConvTranspose2d(k=2,s=2)       weight [C,K,2,2], bias          modules/sampling.py:72-73
   LinearLayer      nn.Linear                         weight [K,C], bias              classification_models/resnet.py:186
@@ -49,6 +50,7 @@ class ConvLayer(SgxBlock):
 
     _param_kinds = {"weight": "conv"}
     depthwise = False
+    grouped = False
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False):
         super().__init__()
@@ -107,6 +109,7 @@ class DepthwiseConvLayer(SgxBlock):
 
     _param_kinds = {"weight": "dwconv"}
     depthwise = True
+    grouped = False
 
     def __init__(self, channels, stride=1, kernel_size=3):
         super().__init__()
@@ -153,6 +156,63 @@ class DepthwiseConvLayer(SgxBlock):
                 out = K.axpy(addend, out=out)
             accumulate = True
         return self._dgrad(dy, self._w, x_shape, stride=self.stride, out=out, accumulate=accumulate)
+
+
+GROUPED_CG = (4, 8, 16, 32, 64)  # channels per group the grouped 3x3 kernels are built for (csrc/gconv.h)
+
+
+class GroupedConvLayer(SgxBlock):
+    """Grouped 3x3 pad-1 convolution, stride 1 or 2, 1 < groups < channels: parameters + the three grouped kernels, with ConvLayer's
+    interface.  The filter is the dense layout with C := channels / groups ([K][3][3][cg] in the arena, the parameter the reference's
+    [K,cg,3,3] as a view of it).  The data gradient reads the filter transposed in its launch (no buffer in the per-step transpose batch);
+    the weight gradient is forked to the side stream on its own - the grouped job-table queue holds dense problems only."""
+
+    _param_kinds = {"weight": "conv"}
+    depthwise = False
+    grouped = True
+
+    def __init__(self, channels, groups, stride=1):
+        super().__init__()
+        if stride not in (1, 2):
+            raise NotImplementedError(f"grouped convolution on the HIP path: stride 1 or 2, got {stride}")
+        if not (1 < groups < channels) or channels % groups or channels // groups not in GROUPED_CG:
+            raise NotImplementedError(f"grouped convolution on the HIP path: channels / groups in {GROUPED_CG}, got {channels} channels in {groups} groups")
+        self.in_channels = self.out_channels = channels
+        self.groups = groups
+        self.kernel_size, self.stride, self.padding = 3, stride, 1
+        w = torch.empty(channels, channels // groups, 3, 3)
+        nn.init.kaiming_uniform_(w, a=math.sqrt(5))  # nn.Conv2d default
+        self.weight = nn.Parameter(w)
+        self.register_parameter("bias", None)
+        self._w = self._gw = None
+
+    def on_materialize(self):
+        slots = {s.param: s for s in self._net.slots}
+        s = slots[self.weight]
+        self._w, self._gw = s.kernel_view, s.grad_kernel_view
+
+    def conv(self, x, out=None, act=None, addend=None, stats=False):
+        if addend is not None:
+            raise NotImplementedError("the grouped convolution has no pre-activation addend")
+        return K.gconv3x3_fwd(x, self._w, self.groups, out=out, act=act, stride=self.stride, stat_partials=stats)
+
+    def conv_with(self, x, w, bias, out=None, act=None):
+        """act(gconv(x, w) + bias) with a filter that is not the parameter (the folded eval form)"""
+        return K.gconv3x3_fwd(x, w, self.groups, bias=bias, out=out, act=act, stride=self.stride)
+
+    def wgrad(self, x, dy, bias_grad=True):
+        self._net.fork_side(lambda: K.gconv3x3_bwd_weight(x, dy, self._gw, self.groups, stride=self.stride), x, dy)
+
+    def dgrad(self, dy, x_shape, out=None, accumulate=False, addend=None, reqs=None):
+        if reqs:  # (the producing layer would skip its own reduce sweep and read rows nobody wrote)
+            raise NotImplementedError("the grouped data gradient carries no BatchNorm-reduce requests")
+        if addend is not None:  # no addend operand in the kernel: the addend becomes the tensor the gradient is added to
+            if accumulate:
+                K.axpy(addend, out=out, accumulate=True)
+            else:
+                out = K.axpy(addend, out=out)
+            accumulate = True
+        return K.gconv3x3_bwd_data(dy, self._w, self.groups, x_shape, stride=self.stride, out=out, accumulate=accumulate)
 
 
 class BatchNorm(SgxBlock):

@@ -5,4 +5,6 @@ from .classification_models import ResNet, ResNet18, ResNet18Cifar, ResNet34, Re
 from .classification_models import RepVGG, RepVggA0, RepVggA1, RepVggA2, RepVggB0, RepVggB1, RepVggB2, RepVggB3, RepVggCustom, RepVggD2SE  # noqa: F401
 from .classification_models import CustomMobileNetV2, MobileNetV2, MobileNetV2_135, MobileNetV2Base  # noqa: F401
 from .classification_models import MobileNetV3, mobilenetv3_custom, mobilenetv3_large, mobilenetv3_small  # noqa: F401
+from .classification_models import AnyNetX, CustomAnyNet, CustomRegNet, NASRegNet, RegNetX, RegNetY, RegNetY200, RegNetY400, RegNetY600, RegNetY800  # noqa: F401
+from .classification_models import GroupedConvBlock, ResNeXt, ResNeXt50, ResNeXt101  # noqa: F401
 from .detection_models.pp_yolo_e.pp_yolo_e import PPYoloE, PPYoloE_L, PPYoloE_M, PPYoloE_S, PPYoloE_X  # noqa: F401

@@ -3,3 +3,6 @@ from .resnet import (BasicResNetBlock, Bottleneck, CifarResNet, ResNet, ResNet18
 from .repvgg import (RepVGG, RepVggA0, RepVggA1, RepVggA2, RepVggB0, RepVggB1, RepVggB2, RepVggB3, RepVggCustom, RepVggD2SE)  # noqa: F401
 from .mobilenetv2 import CustomMobileNetV2, InvertedResidual, MobileNetV2, MobileNetV2_135, MobileNetV2Base  # noqa: F401
 from .mobilenetv3 import MobileNetV3, mobilenetv3_custom, mobilenetv3_large, mobilenetv3_small  # noqa: F401
+from .regnet import (AnyNetX, CustomAnyNet, CustomRegNet, Head, NASRegNet, RegNetX, RegNetY, RegNetY200, RegNetY400, RegNetY600, RegNetY800,  # noqa: F401
+                     Stage, Stem, XBlock, regnet_params_to_blocks, verify_correctness_of_parameters)
+from .resnext import GroupedConvBlock, ResNeXt, ResNeXt50, ResNeXt101  # noqa: F401

@@ -1,0 +1,435 @@
+"""RegNet / AnyNet classifiers on the HIP kernels.
+
+Reference: training/models/classification_models/regnet.py - Head (:21-33), Stem (:36-55), XBlock (:58-106), Stage (:109-119), AnyNetX
+(:122-190), regnet_params_to_blocks (:193-208), RegNetX / RegNetY (:211-243), verify_correctness_of_parameters (:246-256) and the seven
+registered classes (:259-335).  Same constructor arguments, parameter arithmetic, initial weight distributions and state_dict keys
+(net.stem.{conv,bn}.*, net.stage_{i}.blocks.block_{j}.{conv_block_1,conv_block_2,conv_block_3,shortcut}.{0,1}.*, ...se.{1,3}.{weight,bias},
+net.head.fc.*), so checkpoints interchange both ways.
+
+Kernel sequence of an XBlock (training; DESIGN.md 17 counts the passes):
+    1x1 conv (BatchNorm statistics from its epilogue) -> bn_finalize -> affine + ReLU sweep
+    grouped 3x3 conv, stride 1 / 2 (csrc/gconv.h, statistics in its launch) -> bn_finalize -> affine + ReLU sweep  [a, stored]
+    SE: image_colsum(a) -> 1x1 conv + bias + ReLU -> 1x1 conv + bias (both on [N,1,1,C]) -> channel_gate(a, pre, sigmoid)
+    1x1 conv -> bn_finalize;  shortcut: identity, or 1x1 conv (stride) -> bn_finalize -> affine sweep
+    out = relu(bn3(t3) + shortcut)                                                                    one sweep
+The SE hidden width is the block's INPUT width // se_ratio (the reference's rule), often no multiple of 4 (6, 38, 94 ...): it is padded to
+the next multiple of 4 inside with zero filter rows / bias in the first convolution and zero columns in the second; parameters and gradients
+keep the reference's shapes.  Eval after prep_model_for_conversion(): every conv + BatchNorm folds - the grouped layer is ONE
+act(gconv + bias) launch, the last 1x1 takes the shortcut as its addend and the ReLU in its epilogue.
+
+Not built (each raises NotImplementedError): droppath_prob > 0 (DropPath), replace_head(new_head=...), grouped layers whose channels per
+group are outside the kernels' set.
+"""
+from math import sqrt
+from typing import Dict
+
+import numpy as np
+import torch
+from torch import nn
+
+from .... import kernels as K
+from ....common.registry import register_model
+from ....modules.conv_bn_act_block import Conv, ConvBNSeq
+from ....modules.engine import SgxBlock, SgxNetwork
+from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, GroupedConvLayer, LinearLayer
+from ...utils.utils import get_param
+
+
+class _Named(nn.Module):
+    """Namespace whose children carry the reference's names (net.stem, net.stage_0, blocks.block_0 ...)."""
+
+    def children_list(self):
+        return list(self._modules.values())
+
+
+class _SEConv(SgxBlock):
+    """Parameters of one of the SE branch's nn.Conv2d(cin, cout, 1, bias=True): weight [cout, cin, 1, 1], bias [cout]."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size = cin, cout, 1
+        self.weight = nn.Parameter(torch.empty(cout, cin, 1, 1))
+        self.bias = nn.Parameter(torch.zeros(cout))
+        nn.init.kaiming_uniform_(self.weight, a=sqrt(5))
+        nn.init.uniform_(self.bias, -1.0 / sqrt(cin), 1.0 / sqrt(cin))
+
+    def on_materialize(self):
+        pass
+
+
+class SqueezeExcite(SgxBlock):
+    """XBlock.se (regnet.py:71-81): x * sigmoid(conv2(relu(conv1(mean_hw(x))))); keys 1.weight / 1.bias / 3.weight / 3.bias as in the
+    reference's nn.Sequential (0: pool, 2: ReLU, 4: Sigmoid, 5: Residual hold no state)."""
+
+    GATE = "sigmoid"
+    _folded = None  # eval-mode cache of the zero-padded filters (dropped like the conv + BatchNorm folds)
+
+    def __init__(self, channels, hidden):
+        super().__init__()
+        if hidden < 1:
+            raise ValueError(f"SE hidden width {hidden}: the block's input width is smaller than se_ratio")
+        self.channels, self.hidden, self._hp = channels, hidden, (hidden + 3) // 4 * 4
+        self.add_module("1", _SEConv(channels, hidden))
+        self.add_module("3", _SEConv(hidden, channels))
+
+    def on_materialize(self):
+        pass
+
+    def _filters(self):
+        """(w1 [hp, C, 1, 1], b1 [hp], w2 [C, hp, 1, 1]): the parameters themselves, or zero-padded copies when hidden % 4 != 0"""
+        c1, c2 = self._modules["1"], self._modules["3"]
+        if self._hp == self.hidden:
+            return c1.weight, c1.bias, c2.weight
+        if not self.training and self._folded is not None:
+            return self._folded
+        dev = c1.weight.device
+        w1 = torch.zeros(self._hp, self.channels, 1, 1, device=dev)
+        w1[: self.hidden].copy_(c1.weight.detach())
+        b1 = torch.zeros(self._hp, device=dev)
+        b1[: self.hidden].copy_(c1.bias.detach())
+        w2 = torch.zeros(self.channels, self._hp, 1, 1, device=dev)
+        w2[:, : self.hidden].copy_(c2.weight.detach())
+        if not self.training:  # eval: the padded copies are kept until the weights change (train(), SgxNetwork.weights_changed)
+            self._folded = (w1, b1, w2)
+        return w1, b1, w2
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._folded = None
+        return super().train(mode)
+
+    def fwd(self, x, out=None):
+        n, h, w, c = x.shape
+        m = K.image_colsum(x, scale=1.0 / (h * w)).view(n, 1, 1, c)
+        w1, b1, w2 = self._filters()
+        hr = K.conv2d_fwd(m, w1, bias=b1, act="relu")
+        pre = K.conv2d_fwd(hr, w2, bias=self._modules["3"].bias).view(n, c)
+        self._ctx = (x, m, hr, pre, w1, w2) if self.training else None
+        return K.channel_gate(x, pre, self.GATE, out=out)
+
+    def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
+        (x, m, hr, pre, w1, w2), self._ctx = self._ctx, None
+        if addend is not None:
+            raise NotImplementedError("SqueezeExcite.bwd: no addend")
+        n, h, w, c = x.shape
+        c1, c2 = self._modules["1"], self._modules["3"]
+        padded = self._hp != self.hidden
+        dpre = K.image_colsum(dy, v=x, pre=pre, gate=self.GATE).view(n, 1, 1, c)
+        gw2 = torch.zeros_like(w2) if padded else c2.weight.grad
+        K.conv2d_bwd_weight(hr, dpre, gw2, c2.bias.grad)
+        dh = K.conv2d_bwd_data(dpre, w2, (n, 1, 1, self._hp))
+        dh = K.relu_bwd(dh, hr, out=dh)
+        gw1 = torch.zeros_like(w1) if padded else c1.weight.grad
+        gb1 = torch.zeros(self._hp, device=x.device) if padded else c1.bias.grad
+        K.conv2d_bwd_weight(m, dh, gw1, gb1)
+        if padded:  # the padded rows / columns saw zero filters: their gradients are dropped, the rest joins the parameters' gradients
+            c2.weight.grad.add_(gw2[:, : self.hidden])
+            c1.weight.grad.add_(gw1[: self.hidden])
+            c1.bias.grad.add_(gb1[: self.hidden])
+        dmean = K.conv2d_bwd_data(dh, w1, (n, 1, 1, c)).view(n, c)
+        if dx_out is None:
+            dx_out, accumulate = dy, False  # in place over the incoming gradient (element-wise)
+        return K.channel_gate(dy, pre, self.GATE, bias=dmean, bias_scale=1.0 / (h * w), out=dx_out, accumulate=accumulate)
+
+
+class Stem(Conv):
+    """Conv2d(in, out, 3, stride 2, pad 1, bias=False) + BatchNorm + ReLU; keys conv.weight, bn.*."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__(in_channels, out_channels, 3, 2, "relu", padding=1)
+
+    def get_input_channels(self) -> int:
+        return self.conv.in_channels
+
+
+class XBlock(SgxBlock):
+    def __init__(self, in_channels, out_channels, bottleneck_ratio, group_width, stride, se_ratio=None, droppath_prob=0.0):
+        super().__init__()
+        if droppath_prob:
+            raise NotImplementedError("DropPath (droppath_prob > 0) is not on the HIP path")
+        inter_channels = int(out_channels // bottleneck_ratio)
+        groups = int(inter_channels // group_width)
+        self.conv_block_1 = ConvBNSeq(in_channels, inter_channels, 1, activation_type="relu")
+        self.conv_block_2 = ConvBNSeq(inter_channels, inter_channels, 3, stride=stride, padding=1, activation_type="relu", groups=groups)
+        self.se = SqueezeExcite(inter_channels, in_channels // se_ratio) if se_ratio is not None else None
+        self.conv_block_3 = ConvBNSeq(inter_channels, out_channels, 1)
+        self.shortcut = ConvBNSeq(in_channels, out_channels, 1, stride=stride) if (stride != 1 or in_channels != out_channels) else None
+
+    def on_materialize(self):
+        pass
+
+    def fwd(self, x, out=None):
+        a = self.conv_block_2.fwd(self.conv_block_1.fwd(x))
+        if self.se is not None:
+            a = self.se.fwd(a)
+        short = self.shortcut.fwd(x) if self.shortcut is not None else x
+        conv3, bn3 = self.conv_block_3._parts()
+        folded = self.conv_block_3._folded
+        if not self.training and folded is not None:
+            return K.conv2d_fwd(a, folded[0], bias=folded[1], addend=short, out=out, act="relu")
+        if self.training:
+            self.conv_block_3._folded = None
+            t, parts = conv3.conv(a, stats=True)
+            sc, sh, mean, invstd = bn3.scale_shift(parts, t.shape[0] * t.shape[1] * t.shape[2], True)
+        else:
+            t = conv3.conv(a)
+            sc, sh, mean, invstd = bn3.scale_shift(None, 0, False)
+        y = K.affine_act(t, sc, sh, r1=short, a1=1.0, act="relu", out=out)
+        self._ctx = (x, a, t, sc, sh, mean, invstd, y) if self.training else None
+        return y
+
+    def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
+        (x, a, t, sc, sh, mean, invstd, y), self._ctx = self._ctx, None
+        if addend is not None:
+            raise NotImplementedError("XBlock.bwd: no addend (the shortcut uses the first data gradient's)")
+        conv3, bn3 = self.conv_block_3._parts()
+        g = K.relu_bwd(dy, y)
+        dt = bn3.backward(g, t, sc, sh, mean, invstd, None, dx_out=t)
+        conv3.wgrad(a, dt)
+        d = conv3.dgrad(dt, tuple(a.shape))
+        if self.se is not None:
+            d = self.se.bwd(d)
+        d = self.conv_block_2.bwd(d)
+        if self.shortcut is None:  # identity: + g in the first data gradient's epilogue
+            return self.conv_block_1.bwd(d, dx_out=dx_out, accumulate=accumulate, addend=g, need_dx=need_dx)
+        dx = self.conv_block_1.bwd(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+        return self.shortcut.bwd(g, dx_out=dx, accumulate=True, need_dx=need_dx)
+
+
+class Stage(nn.Module):
+    def __init__(self, num_blocks, in_channels, out_channels, bottleneck_ratio, group_width, stride, se_ratio, droppath_prob):
+        super().__init__()
+        self.blocks = _Named()
+        self.blocks.add_module("block_0", XBlock(in_channels, out_channels, bottleneck_ratio, group_width, stride, se_ratio, droppath_prob))
+        for i in range(1, num_blocks):
+            self.blocks.add_module("block_{}".format(i), XBlock(out_channels, out_channels, bottleneck_ratio, group_width, 1, se_ratio, droppath_prob))
+
+
+class _Dropout(nn.Module):
+    """The reference's nn.Dropout at head.dropout: no state."""
+
+    def __init__(self, p):
+        super().__init__()
+        self.p = float(p)
+
+
+class Head(nn.Module):
+    """Global average pool -> dropout (Philox mask, regenerated in the backward) -> Linear; key fc.*."""
+
+    def __init__(self, num_channels, num_classes, dropout_prob):
+        super().__init__()
+        self.dropout = _Dropout(dropout_prob)
+        self.fc = LinearLayer(num_channels, num_classes)
+
+
+class AnyNetX(SgxNetwork):
+    def __init__(self, ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width, stride, num_classes, se_ratio, backbone_mode,
+                 dropout_prob=0.0, droppath_prob=0.0, input_channels=3):
+        super().__init__()
+        if droppath_prob:
+            raise NotImplementedError("DropPath (droppath_prob > 0) is not on the HIP path")
+        verify_correctness_of_parameters(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width)
+        self.net = _Named()
+        self.backbone_mode = backbone_mode
+        prev_block_width = 32
+        self.net.add_module("stem", Stem(in_channels=input_channels, out_channels=prev_block_width))
+        for i, (num_blocks, block_width, bottleneck_ratio, group_width) in enumerate(zip(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width)):
+            self.net.add_module("stage_{}".format(i), Stage(int(num_blocks), prev_block_width, int(block_width), bottleneck_ratio, int(group_width), stride, se_ratio,
+                                                            droppath_prob))
+            prev_block_width = int(block_width)
+        if not self.backbone_mode:  # backbone mode: no head (average pool + fc)
+            self.net.add_module("head", Head(int(ls_block_width[-1]), num_classes, dropout_prob))
+        self.ls_block_width = [int(w) for w in ls_block_width]
+        self.dropout_prob = dropout_prob
+        self.initialize_weight()
+
+    def initialize_weight(self):
+        """Reference :157-167: conv weights N(0, sqrt(2 / (k * k * out_channels))), BatchNorm 1 / 0, linear N(0, 0.01) with zero bias.
+        (The SE convolutions are nn.Conv2d too: the same normal draw; their biases keep nn.Conv2d's default.)"""
+        for m in self.modules():
+            if isinstance(m, (ConvLayer, DepthwiseConvLayer, GroupedConvLayer, _SEConv)):
+                m.weight.data.normal_(mean=0.0, std=sqrt(2.0 / (m.kernel_size * m.kernel_size * m.out_channels)))
+            elif isinstance(m, BatchNorm):
+                m.weight.data.fill_(1.0)
+                m.bias.data.zero_()
+            elif isinstance(m, LinearLayer):
+                m.weight.data.normal_(mean=0.0, std=0.01)
+                m.bias.data.zero_()
+
+    def _blocks(self):
+        return [(f"net.{sname}.", blk) for sname, st in self.net._modules.items() if isinstance(st, Stage) for blk in st.blocks.children_list()]
+
+    def _fwd(self, x):
+        cin = self.get_input_channels()
+        if x.dim() != 4 or x.shape[1] != cin:
+            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
+        a = self.net.stem.fwd(K.input_to_nhwc(x))
+        for _, blk in self._blocks():
+            a = blk.fwd(a)
+        if self.backbone_mode:
+            return (K.nhwc_to_nchw(a),)
+        self._feat_shape = tuple(a.shape)
+        pooled = K.avgpool_fwd(a)
+        head = self.net.head
+        p = float(head.dropout.p)
+        self._drop = None
+        if self.training and p > 0:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's default generator: torch.manual_seed repeats a step
+            self._drop = (seed, p)
+            pooled = K.dropout(pooled, p, seed)
+        return (head.fc.fwd(pooled).contiguous(),)
+
+    def _bwd(self, d_out):
+        ready = self._bucket_ready
+        if self.backbone_mode:
+            d = K.nchw_to_nhwc(d_out)
+        else:
+            d = self.net.head.fc.bwd(d_out.contiguous()).contiguous()
+            if self._drop is not None:
+                (seed, p), self._drop = self._drop, None
+                d = K.dropout(d, p, seed, out=d)  # the same mask, regenerated
+            d = K.avgpool_bwd(d, self._feat_shape)
+            ready("net.head.")
+        blocks = self._blocks()
+        for i in range(len(blocks) - 1, -1, -1):
+            prefix, blk = blocks[i]
+            d = blk.bwd(d)
+            if i == 0 or blocks[i - 1][0] != prefix:
+                ready(prefix)
+        self.net.stem.bwd(d, need_dx=False)
+        ready("net.stem.")
+
+    def gradient_buckets(self):
+        """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
+        return [f"net.{name}." for name in self.net._modules]
+
+    def supports_half_inference(self) -> bool:
+        return False
+
+    # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
+    def replace_head(self, new_num_classes=None, new_head=None):
+        if new_num_classes is None and new_head is None:
+            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
+        if new_head is not None:
+            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
+        if self._materialized:
+            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
+        head = Head(self.ls_block_width[-1], new_num_classes, self.dropout_prob)
+        head.fc.weight.data.normal_(mean=0.0, std=0.01)
+        head.fc.bias.data.zero_()
+        self.net.head = head
+
+    def replace_input_channels(self, in_channels: int, compute_new_weights_fn=None):
+        """Reference regnet.py:49-52, 181-183 with modules/weight_replacement_utils.py: the stem keeps the weights of the channels it already
+        has; extra channels are drawn from a normal distribution with the old weights' mean / std.  Before materialisation only."""
+        if self._materialized:
+            raise RuntimeError("replace_input_channels must be called before the model is materialized in HBM (before the first forward)")
+        old = self.net.stem.conv
+        if compute_new_weights_fn is not None:
+            self.net.stem.conv = compute_new_weights_fn(old, in_channels)
+            return
+        new = ConvLayer(in_channels, old.out_channels, old.kernel_size, old.stride, old.padding, bias=False)
+        w = old.weight.data
+        if in_channels <= old.in_channels:
+            new.weight.data = w[:, :in_channels].clone()
+        else:
+            new.weight.data[:, : old.in_channels] = w
+            torch.nn.init.normal_(new.weight.data[:, old.in_channels:], mean=float(w.mean()), std=float(w.std()))
+        self.net.stem.conv = new
+
+    def get_input_channels(self) -> int:
+        return self.net.stem.get_input_channels()
+
+    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
+        return {"net.head": lr, "default": 0}
+
+
+def regnet_params_to_blocks(initial_width, slope, quantized_param, network_depth, bottleneck_ratio, group_width):
+    """Block widths and counts from the RegNet parameters (the paper's equations 2 and 3, widths rounded to multiples of 8, then made
+    compatible with the group width) - the reference's arithmetic, operation by operation."""
+    parameterized_width = initial_width + slope * np.arange(network_depth)
+    parameterized_block = np.log(parameterized_width / initial_width) / np.log(quantized_param)
+    parameterized_block = np.round(parameterized_block)
+    quantized_width = initial_width * np.power(quantized_param, parameterized_block)
+    quantized_width = 8 * np.round(quantized_width / 8)
+    ls_block_width, ls_num_blocks = np.unique(quantized_width.astype(np.int32), return_counts=True)
+    ls_group_width = np.array([min(group_width, block_width // bottleneck_ratio) for block_width in ls_block_width])
+    ls_block_width = (np.round(ls_block_width // bottleneck_ratio / group_width) * group_width).astype(np.int32).tolist()
+    ls_bottleneck_ratio = [bottleneck_ratio for _ in range(len(ls_block_width))]
+    return ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width.tolist()
+
+
+def verify_correctness_of_parameters(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width):
+    """The parameters must fit the search space of the RegNet paper."""
+    err_message = "Parameters don't fit"
+    assert len(set(ls_bottleneck_ratio)) == 1, f"{err_message} AnyNetXb"
+    assert len(set(ls_group_width)) == 1, f"{err_message} AnyNetXc"
+    assert all(i <= j for i, j in zip(ls_block_width, ls_block_width[1:])) is True, f"{err_message} AnyNetXd"
+    if len(ls_num_blocks) > 2:
+        assert all(i <= j for i, j in zip(ls_num_blocks[:-2], ls_num_blocks[1:-1])) is True, f"{err_message} AnyNetXe"
+    for block_width, bottleneck_ratio, group_width in zip(ls_block_width, ls_bottleneck_ratio, ls_group_width):
+        assert int(block_width // bottleneck_ratio) % group_width == 0
+
+
+class RegNetX(AnyNetX):
+    def __init__(self, initial_width, slope, quantized_param, network_depth, bottleneck_ratio, group_width, stride, arch_params, se_ratio=None,
+                 input_channels=3, num_classes=None):
+        ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width = regnet_params_to_blocks(initial_width, slope, quantized_param, network_depth,
+                                                                                                    bottleneck_ratio, group_width)
+        super().__init__(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width, stride, num_classes or get_param(arch_params, "num_classes"), se_ratio,
+                         get_param(arch_params, "backbone_mode", False), get_param(arch_params, "dropout_prob", 0.0), get_param(arch_params, "droppath_prob", 0.0),
+                         input_channels)
+
+
+class RegNetY(RegNetX):
+    """RegNetY = RegNetX + SE"""
+
+    def __init__(self, initial_width, slope, quantized_param, network_depth, bottleneck_ratio, group_width, stride, arch_params, se_ratio, input_channels=3,
+                 num_classes=None):
+        super().__init__(initial_width, slope, quantized_param, network_depth, bottleneck_ratio, group_width, stride, arch_params, se_ratio, input_channels,
+                         num_classes)
+
+
+@register_model("custom_regnet")
+class CustomRegNet(RegNetX):
+    def __init__(self, arch_params, num_classes=None):
+        """All parameters must be provided in arch_params other than SE"""
+        g = lambda k: get_param(arch_params, k)  # noqa: E731
+        super().__init__(initial_width=g("initial_width"), slope=g("slope"), quantized_param=g("quantized_param"), network_depth=g("network_depth"),
+                         bottleneck_ratio=g("bottleneck_ratio"), group_width=g("group_width"), stride=g("stride"), arch_params=arch_params,
+                         se_ratio=get_param(arch_params, "se_ratio", None), input_channels=get_param(arch_params, "input_channels", 3), num_classes=num_classes)
+
+
+@register_model("custom_anynet")
+class CustomAnyNet(AnyNetX):
+    def __init__(self, arch_params, num_classes=None):
+        """All parameters must be provided in arch_params other than SE"""
+        g = lambda k: get_param(arch_params, k)  # noqa: E731
+        super().__init__(ls_num_blocks=g("ls_num_blocks"), ls_block_width=g("ls_block_width"), ls_bottleneck_ratio=g("ls_bottleneck_ratio"),
+                         ls_group_width=g("ls_group_width"), stride=g("stride"), num_classes=num_classes or get_param(arch_params, "num_classes"),
+                         se_ratio=get_param(arch_params, "se_ratio", None), backbone_mode=get_param(arch_params, "backbone_mode", False),
+                         dropout_prob=get_param(arch_params, "dropout_prob", 0), droppath_prob=get_param(arch_params, "droppath_prob", 0),
+                         input_channels=get_param(arch_params, "input_channels", 3))
+
+
+@register_model("nas_regnet")
+class NASRegNet(RegNetX):
+    def __init__(self, arch_params, num_classes=None):
+        """All parameters are provided as a single structure list: arch_params.structure"""
+        structure = get_param(arch_params, "structure")
+        super().__init__(initial_width=structure[0], slope=structure[1], quantized_param=structure[2], network_depth=structure[3], bottleneck_ratio=structure[4],
+                         group_width=structure[5], stride=structure[6], se_ratio=structure[7] if structure[7] > 0 else None, arch_params=arch_params,
+                         num_classes=num_classes)
+
+
+def _regnety(name, *params):
+    def init(self, arch_params, num_classes=None):
+        RegNetY.__init__(self, *params, 2, arch_params, 4, num_classes=num_classes)
+
+    return register_model(name)(type("RegNetY" + name[7:], (RegNetY,), {"__init__": init}))
+
+
+RegNetY200 = _regnety("regnetY200", 24, 36, 2.5, 13, 1, 8)
+RegNetY400 = _regnety("regnetY400", 48, 28, 2.1, 16, 1, 8)
+RegNetY600 = _regnety("regnetY600", 48, 33, 2.3, 15, 1, 16)
+RegNetY800 = _regnety("regnetY800", 56, 39, 2.4, 14, 1, 16)

@@ -52,7 +52,12 @@ class _ConvBN:
 
 
 class _ResBlock(SgxBlock):
-    """out = [relu]( bn_n(conv_n(... relu(bn_1(conv_1(x))) ...)) + shortcut(x) )"""
+    """out = [relu]( bn_n(conv_n(... relu(bn_1(conv_1(x))) ...)) + shortcut(x) )
+    Eval folds: a subclass may set `_folded = {branch index: (filter, bias)}` for layers whose conv has `conv_with` (resnext.py's
+    GroupedConvBlock does in prep_model_for_conversion); eval-mode fwd() then runs relu(conv_with(...)) for those layers.  Only layers
+    before the last; the attribute name is the one SgxNetwork.weights_changed() clears."""
+
+    _folded = None
 
     def _branch(self):
         raise NotImplementedError
@@ -81,9 +86,14 @@ class _ResBlock(SgxBlock):
         self._branched = bool(len(self.shortcut)) and net is not None and self.training and net.branches(16, x.shape[0] * x.shape[1] * x.shape[2], 64)
         if self._branched:
             forked = net.fork_branch(lambda: self._shortcut_fwd(x))
+        folded = None if self.training else self._folded
         for i, (conv, bn) in enumerate(branch):
-            t, sc, sh, mean, invstd = _ConvBN.fwd(conv, bn, a, self.training)
             last = i == len(branch) - 1
+            if folded is not None and i in folded and not last:
+                a = conv.conv_with(a, folded[i][0], folded[i][1], act="relu")
+                saved.append(None)
+                continue
+            t, sc, sh, mean, invstd = _ConvBN.fwd(conv, bn, a, self.training)
             if not last:
                 nxt = K.affine_act(t, sc, sh, act="relu", out=None if self.training else t)
                 saved.append((a, t, sc, sh, mean, invstd))
@@ -139,7 +149,8 @@ class _ResBlock(SgxBlock):
             # the ResNet blocks still ran a reduce sweep over (gradient, saved conv output) per layer: 32 of a ResNet-50 step's 53
             _, pt, psc, psh, pmean, _ = saved[i - 1]
             pbn = branch[i - 1][1]
-            req = K.BnReduceRequest(pt, psc, psh, pmean, "relu") if (self._net.fuse_bn_reduce and not pbn._synced()) else None
+            # (a grouped convolution's data gradient carries no requests: the layer below reduces in its own sweep)
+            req = K.BnReduceRequest(pt, psc, psh, pmean, "relu") if (self._net.fuse_bn_reduce and not pbn._synced() and not conv.grouped) else None
             d = conv.dgrad(dt, tuple(a.shape), reqs=[req] if req is not None else None)
             parts = req.parts if req is not None else None
         conv, bn = branch[0]
@@ -215,6 +226,8 @@ class _Layer(nn.Module):
 class _ResNetBase(SgxNetwork):
     """Shared driver: stem -> layer1..4 -> global average pool -> linear, and its backward."""
 
+    _head = "linear"  # the classifier's attribute name (ResNeXt: fc)
+
     def _make_layer(self, block, planes, num_blocks, stride):
         if num_blocks == 0:
             raise NotImplementedError("ResNet layers with num_blocks == 0 (conv-only layers of the customised variants) are not on the HIP path")
@@ -239,14 +252,14 @@ class _ResNetBase(SgxNetwork):
                 a = blk.fwd(a)
         self._feat_shape = tuple(a.shape)
         pooled = K.avgpool_fwd(a)
-        logits = self.linear.fwd(pooled)
+        logits = getattr(self, self._head).fwd(pooled)
         return (logits.contiguous(),)
 
     def _bwd(self, d_logits):
-        d = self.linear.bwd(d_logits.contiguous())
+        d = getattr(self, self._head).bwd(d_logits.contiguous())
         d = K.avgpool_bwd(d.contiguous(), self._feat_shape)
         ready = self._bucket_ready
-        ready("linear.")
+        ready(f"{self._head}.")
         for name in ("layer4", "layer3", "layer2", "layer1"):
             for blk in reversed(getattr(self, name).blocks()):
                 d = blk.bwd(d)
@@ -257,7 +270,7 @@ class _ResNetBase(SgxNetwork):
 
     def gradient_buckets(self):
         """Arena ranges in parameter order; `stem` covers conv1/bn1 (GradientAllReducer matches by name prefix)."""
-        return ["conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", "linear."]
+        return ["conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", f"{self._head}."]
 
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
     def get_input_channels(self) -> int:
