@@ -463,7 +463,11 @@ int32_t sgx_colsum(const float* x, int64_t ld, int64_t M, int32_t C, int64_t row
  * Pooling.  SPP max-pool k in {5,9,13} stride 1 (detection_models/csp_darknet53.py:146-150),
  * ResNet stem max-pool 3x3 s2 p1 and global average pool (classification_models/resnet.py:164,205).
  * ------------------------------------------------------------------------------------------- */
-/* argmax (optional, int32 [N,Ho,Wo,C] contiguous) = flat input pixel index h*W+w of the first maximum in
+/* Every operand address and every pixel / image stride must be a multiple of 16 bytes (4 floats): the kernels move float4 channel
+ * groups.  A max-pool whose output would be empty (a map smaller than the window, without padding) is SGX_ERR_BAD_ARG.
+ * NaN inputs are outside the contract: the max-pool kernels keep a NaN only where it is the first element of its window, whereas ATen
+ * always propagates it.
+ * argmax (optional, int32 [N,Ho,Wo,C] contiguous) = flat input pixel index h*W+w of the first maximum in
  * row-major window order (ATen's tie rule); it is what the backward consumes.                        */
 int32_t sgx_maxpool_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad,
                         const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y, int64_t y_ld_pix,
@@ -472,6 +476,10 @@ int32_t sgx_maxpool_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, i
 int32_t sgx_maxpool_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad,
                         const int32_t* argmax, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dx,
                         int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
+/* The kernel sgx_maxpool_fwd (backward == 0) or sgx_maxpool_bwd (backward != 0) launches for this problem: 0 the direct kernel, 1 the
+ * LDS-tile kernel, 2 the LDS-scatter kernel (backward only).  The launch code asks the same predicates; launches nothing itself.
+ * (tests pin every case to the kernel it is meant to reach)                                                                     */
+int32_t sgx_debug_maxpool_form(int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad, int32_t backward);
 int32_t sgx_avgpool_fwd(int32_t N, int32_t HW, int32_t C, const float* x, int64_t x_ld_pix, int64_t x_ld_img,
                         float* y, void* stream);
 int32_t sgx_avgpool_bwd(int32_t N, int32_t HW, int32_t C, const float* dy, float* dx, int64_t dx_ld_pix,

@@ -452,7 +452,7 @@ extern "C" int32_t sgx_hmaxpool_fwd(int32_t N, int32_t H, int32_t W, int32_t C, 
     SGX_CHECK_ARG(x_ld_pix % 8 == 0 && x_ld_img % 8 == 0 && y_ld_pix % 8 == 0 && y_ld_img % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0,
                   "hmaxpool_fwd: strides and addresses must be multiples of 16 bytes");
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    SGX_CHECK_ARG(Ho > 0 && Wo > 0, "hmaxpool_fwd: empty output");
+    SGX_CHECK_ARG(Ho > 0 && Wo > 0 && H + 2 * pad >= k && W + 2 * pad >= k, "hmaxpool_fwd: empty output");  // (the division truncates)
     const long n = (long)N * Ho * Wo * (C / 8), blocks = (n + 255) / 256;
     SGX_LAUNCH(hmaxpool_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, stream, N, H, W, C, k, stride, pad, Ho, Wo,
                (const unsigned short*)x, (long)x_ld_pix, (long)x_ld_img, (unsigned short*)y, (long)y_ld_pix, (long)y_ld_img);

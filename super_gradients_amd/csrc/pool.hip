@@ -5,6 +5,10 @@
 #include "sgx_common.h"
 #include <atomic>
 
+#define SGX_ALIGNED16(p) (((uintptr_t)(p) % 16) == 0)
+// output extent of a pooling window walk; 0 when the padded map is smaller than the window (a truncating division alone would say 1 at stride > 1)
+static int maxpool_out(int in, int k, int stride, int pad) { return in + 2 * pad < k ? 0 : (in + 2 * pad - k) / stride + 1; }
+
 __global__ void maxpool_fwd_kernel(int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, const float* x, long x_ld_pix,
                                    long x_ld_img, float* y, long y_ld_pix, long y_ld_img, int* argmax) {
     const int C4 = C / 4;
@@ -47,6 +51,11 @@ __global__ void maxpool_fwd_kernel(int N, int H, int W, int C, int k, int stride
 #define MP_CG 8
 #define MP_TILE_MAX_LDS 65536  // dynamic LDS a launch may ask for without raising the function's limit
 static long maxpool_fwd_tile_lds(int H, int W, int Wo) { return (long)H * W * MP_CG * 4 + (long)H * Wo * MP_CG * 6; }
+// The kernel a forward launch runs: 0 the direct kernel, 1 the LDS tile.  sgx_maxpool_fwd and sgx_debug_maxpool_form both ask here.
+static int maxpool_fwd_form(int H, int W, int C, int k, int stride, int pad) {
+    const int Ho = maxpool_out(H, k, stride, pad), Wo = maxpool_out(W, k, stride, pad);
+    return (stride == 1 && C % MP_CG == 0 && Ho > 0 && Wo > 0 && (long)H * W < 65536 && maxpool_fwd_tile_lds(H, W, Wo) <= MP_TILE_MAX_LDS && k > 2) ? 1 : 0;
+}
 __global__ __launch_bounds__(256) void maxpool_fwd_tile_kernel(int H, int W, int C, int k, int pad, int Ho, int Wo, const float* x, long x_ld_pix,
                                                                long x_ld_img, float* y, long y_ld_pix, long y_ld_img, int* argmax) {
     SGX_DYN_SMEM(float, smem);
@@ -109,8 +118,11 @@ extern "C" int32_t sgx_maxpool_fwd(int32_t N, int32_t H, int32_t W, int32_t C, i
                                    void* stream) {
     SGX_CHECK_ARG(x && y && C % 4 == 0 && k > 0 && stride > 0, "maxpool_fwd: bad args");
     SGX_CHECK_ARG(pad >= 0 && 2 * pad <= k, "maxpool_fwd: pad %d must be at most half the window %d (F.max_pool2d's own rule)", pad, k);
-    int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    if (stride == 1 && C % MP_CG == 0 && Ho > 0 && Wo > 0 && (long)H * W < 65536 && maxpool_fwd_tile_lds(H, W, Wo) <= MP_TILE_MAX_LDS && k > 2) {
+    SGX_CHECK_ARG(x_ld_pix % 4 == 0 && x_ld_img % 4 == 0 && y_ld_pix % 4 == 0 && y_ld_img % 4 == 0 && SGX_ALIGNED16(x) && SGX_ALIGNED16(y),
+                  "maxpool_fwd: strides and addresses must be multiples of 16 bytes");
+    const int Ho = maxpool_out(H, k, stride, pad), Wo = maxpool_out(W, k, stride, pad);
+    SGX_CHECK_ARG(Ho > 0 && Wo > 0, "maxpool_fwd: empty output");
+    if (maxpool_fwd_form(H, W, C, k, stride, pad) == 1) {
         SGX_LAUNCH(maxpool_fwd_tile_kernel, dim3((unsigned)(N * (C / MP_CG))), dim3(256), (unsigned)maxpool_fwd_tile_lds(H, W, Wo), stream, H, W, C, k, pad,
                    Ho, Wo, x, (long)x_ld_pix, (long)x_ld_img, y, (long)y_ld_pix, (long)y_ld_img, argmax);
         SGX_CHECK_LAUNCH("maxpool_fwd (tile)");
@@ -208,7 +220,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_tile_kernel(int H, int W, int
 // costs ONE add per OUTPUT element: a wave owns 64 channels of one image, lane = channel, keeps that (image, channels) slice of dx in LDS
 // (H x W x 64 floats: 100 KB for the 20 x 20 map) and walks the outputs in ascending order - every lane adds its gradient at its arg-max
 // pixel.  Lanes never share an address (different channels) and a lane's additions happen in output order: the sums are deterministic and in
-// the order of ATen's CPU kernel.  Eight outputs of loads in flight per lane; no atomics.
+// the order of ATen's CPU kernel.  Eight outputs of loads in flight per lane; no atomics.  The plain backward leaves the bits of the two
+// gather forms (tests/test_pool_kernels.py holds the three to it); with `accumulate` this form starts its chain from the target's value,
+// where the gather forms add the target last.
 // Round 5: 32 channels per workgroup by default (half a wave adds; 50 KB for the 20 x 20 map).  Alone on the chip the 64-channel form is
 // as fast (the add chain is latency-bound either way), but in the train step its 100 KB workgroups waited for a CU with that much LDS
 // free while weight-gradient kernels of the side stream were resident: 200 us per call in the step's trace against 35 alone (r5m).
@@ -259,13 +273,29 @@ __global__ __launch_bounds__(MP_SCATTER_THREADS) void maxpool_bwd_scatter_kernel
     for (int p = ps; p < HW; p += PP) gx[(long)p * dx_ld_pix] = tile[p * CH + ch];
 }
 
+// The kernel a backward launch runs: 0 the direct kernel, 1 the LDS tile, 2 the LDS scatter (tried first).
+static int maxpool_bwd_form(int H, int W, int C, int k, int stride, int pad) {
+    const int Ho = maxpool_out(H, k, stride, pad), Wo = maxpool_out(W, k, stride, pad);
+    if (C % MP_SCATTER_CH == 0 && Ho > 0 && Wo > 0 && (long)H * W * MP_SCATTER_CH * 4 <= MP_SCATTER_MAX_LDS) return 2;
+    if (stride == 1 && C % MP_CG == 0 && Ho > 0 && Wo > 0 && (long)H * W < 65536 && (long)Ho * Wo * MP_CG * 6 <= MP_TILE_MAX_LDS && k > 2) return 1;
+    return 0;
+}
+extern "C" int32_t sgx_debug_maxpool_form(int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad, int32_t backward) {
+    SGX_CHECK_ARG(H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0, "debug_maxpool_form: bad args");
+    return backward ? maxpool_bwd_form(H, W, C, k, stride, pad) : maxpool_fwd_form(H, W, C, k, stride, pad);
+}
+
 extern "C" int32_t sgx_maxpool_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad, const int32_t* argmax,
                                    const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dx, int64_t dx_ld_pix, int64_t dx_ld_img,
                                    int32_t accumulate, void* stream) {
     SGX_CHECK_ARG(argmax && dy && dx && C % 4 == 0, "maxpool_bwd: bad args");
     SGX_CHECK_ARG(pad >= 0 && 2 * pad <= k, "maxpool_bwd: pad %d must be at most half the window %d", pad, k);
-    int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    if (C % MP_SCATTER_CH == 0 && Ho > 0 && Wo > 0 && (long)H * W * MP_SCATTER_CH * 4 <= MP_SCATTER_MAX_LDS) {
+    SGX_CHECK_ARG(dy_ld_pix % 4 == 0 && dy_ld_img % 4 == 0 && dx_ld_pix % 4 == 0 && dx_ld_img % 4 == 0 && SGX_ALIGNED16(dy) && SGX_ALIGNED16(dx),
+                  "maxpool_bwd: strides and addresses must be multiples of 16 bytes");
+    const int Ho = maxpool_out(H, k, stride, pad), Wo = maxpool_out(W, k, stride, pad);
+    SGX_CHECK_ARG(Ho > 0 && Wo > 0, "maxpool_bwd: empty output");
+    const int form = maxpool_bwd_form(H, W, C, k, stride, pad);
+    if (form == 2) {
         const unsigned lds = (unsigned)((long)H * W * MP_SCATTER_CH * 4);
 #ifndef SGX_EMU
         // dynamic LDS beyond 64 KB is opt-in per function AND per device: one flag bit per device ordinal
@@ -284,7 +314,7 @@ extern "C" int32_t sgx_maxpool_bwd(int32_t N, int32_t H, int32_t W, int32_t C, i
         SGX_CHECK_LAUNCH("maxpool_bwd (scatter)");
         return SGX_OK;
     }
-    if (stride == 1 && C % MP_CG == 0 && Ho > 0 && Wo > 0 && (long)H * W < 65536 && (long)Ho * Wo * MP_CG * 6 <= MP_TILE_MAX_LDS && k > 2) {
+    if (form == 1) {
         SGX_LAUNCH(maxpool_bwd_tile_kernel, dim3((unsigned)(N * (C / MP_CG))), dim3(256), (unsigned)((long)Ho * Wo * MP_CG * 6), stream, H, W, C, k, pad, Ho, Wo,
                    argmax, dy, (long)dy_ld_pix, (long)dy_ld_img, dx, (long)dx_ld_pix, (long)dx_ld_img, accumulate);
         SGX_CHECK_LAUNCH("maxpool_bwd (tile)");
@@ -314,6 +344,7 @@ __global__ void avgpool_fwd_kernel(int N, int HW, int C, const float* x, long ld
 }
 extern "C" int32_t sgx_avgpool_fwd(int32_t N, int32_t HW, int32_t C, const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y, void* stream) {
     SGX_CHECK_ARG(x && y && C % 4 == 0, "avgpool_fwd: bad args");
+    SGX_CHECK_ARG(x_ld_pix % 4 == 0 && x_ld_img % 4 == 0 && SGX_ALIGNED16(x) && SGX_ALIGNED16(y), "avgpool_fwd: strides and addresses must be multiples of 16 bytes");
     long n = (long)N * (C / 4), blocks = (n + 63) / 64;
     SGX_LAUNCH(avgpool_fwd_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, N, HW, C, x, (long)x_ld_pix, (long)x_ld_img, y);
     SGX_CHECK_LAUNCH("avgpool_fwd");
@@ -334,6 +365,7 @@ __global__ void avgpool_bwd_kernel(int N, int HW, int C, const float* dy, float*
 }
 extern "C" int32_t sgx_avgpool_bwd(int32_t N, int32_t HW, int32_t C, const float* dy, float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, void* stream) {
     SGX_CHECK_ARG(dy && dx && C % 4 == 0, "avgpool_bwd: bad args");
+    SGX_CHECK_ARG(dx_ld_pix % 4 == 0 && dx_ld_img % 4 == 0 && SGX_ALIGNED16(dy) && SGX_ALIGNED16(dx), "avgpool_bwd: strides and addresses must be multiples of 16 bytes");
     long n = (long)N * HW * (C / 4), blocks = (n + 255) / 256;
     SGX_LAUNCH(avgpool_bwd_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, stream, N, HW, C, dy, dx, (long)dx_ld_pix,
                (long)dx_ld_img);
@@ -601,7 +633,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_wgrad_fold_kernel(const flo
     }
 }
 
-#define DW_ALIGNED(p) (((uintptr_t)(p) % 16) == 0)
+#define DW_ALIGNED(p) SGX_ALIGNED16(p)
 static int32_t dw_check(const sgx_conv_desc* d, const char* what, int k = 3) {
     SGX_CHECK_ARG(d, "%s: null descriptor", what);
     SGX_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "%s: bad dims N=%d H=%d W=%d C=%d", what, d->N, d->H, d->W, d->C);

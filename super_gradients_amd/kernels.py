@@ -1191,6 +1191,14 @@ def maxpool_bwd(dy, argmax, x_shape, k, stride, pad, out=None, accumulate=False)
     return out
 
 
+def maxpool_form(h, w, c, k, stride, pad, backward=False):
+    """Which kernel maxpool_fwd (or maxpool_bwd) launches for this problem: 0 direct, 1 LDS tile, 2 LDS scatter (sgx_debug_maxpool_form)."""
+    form = lib().sgx_debug_maxpool_form(h, w, c, k, stride, pad, int(backward))
+    if form < 0:
+        check(form, "sgx_debug_maxpool_form")
+    return form
+
+
 def avgpool_fwd(x):
     n, h, w, c = x.shape
     xl, xi = nhwc_strides(x)

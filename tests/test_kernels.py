@@ -320,7 +320,8 @@ def test_affine_residuals_and_sweeps(backend):
 def test_maxpool(backend, k, stride, pad):
     """Forward values and arg-max routing against ATen (ties on purpose: the first maximum in row-major window order wins), through every
     kernel form: the direct kernels (C = 8 at stride 2; large maps), the LDS-tile forms (stride 1, 8-channel groups) and the scatter-form
-    backward (64-channel groups of a map whose gradient slice fits LDS), plain and accumulating."""
+    backward (32-channel groups of a map whose gradient slice fits LDS), plain and accumulating.  These are the workload's shapes; every
+    form, contiguous and on channel-slice views, is held to exact ATen results in tests/test_pool_kernels.py."""
     shapes = [(2, 20, 20, 384), (2, 56, 56, 64), (2, 20, 20, 72)] if backend.type == "cuda" else [(1, 7, 6, 8), (1, 6, 5, 64)]
     for n, h, w, c in shapes:
         g = torch.Generator().manual_seed(0)
