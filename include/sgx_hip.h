@@ -550,6 +550,9 @@ int32_t sgx_gconv3x3_bwd_weight(const sgx_conv_desc* d, int32_t groups, const fl
 #define SGX_GATE_NONE 0        /* f(p) = p (plain per-image channel scale) */
 #define SGX_GATE_HARDSIGMOID 1 /* f(p) = min(max(p/6 + 1/2, 0), 1); f' = 1/6 on -3 < p < 3 (ATen) */
 #define SGX_GATE_SIGMOID 2
+/* Alignment (every fp32 entry point of this section and the sgx_bn_gate_act_* sweeps below): the kernels move float4, so every address -
+ * tensors, the [N][C] and [C] vectors (pre, bias, dmean, dpre, out, scale, shift, save_mean, partials) and the workspace - must be a
+ * multiple of 16 bytes and every pixel / image / row stride a multiple of 4 floats; anything else is SGX_ERR_BAD_ARG and nothing is launched. */
 /* Per-image column reduction, deterministic two-stage (fp32 chunk partials, fp64 finalize in fixed order):
  *   out[n][c] = scale * f'(pre[n][c]) * sum_p u[n][p][c] * v[n][p][c]      v NULL -> 1 ; pre NULL -> no f' factor.
  * mean over H*W: u = x, scale = 1/HW.  Gate gradient: u = dy, v = x, pre = the gate's pre-activation.                          */
@@ -577,7 +580,8 @@ int32_t sgx_upsample2x_bwd(int32_t N, int32_t H, int32_t W, int32_t C, const flo
  *              (ws: sgx_bn_gate_act_bwd_gate_workspace bytes).
  *   _bwd_data  dz = gv * s + dmean[n][c] / HW (dmean may be NULL), stored; partials != NULL: also [2][sgx_stats_blocks(N * HW)][C] rows
  *              sum dz, sum dz * (x - save_mean) - bit for bit the rows sgx_bn_bwd_reduce(dz, x, act = NONE) writes, so
- *              sgx_bn_bwd_finalize + sgx_bn_bwd_apply(act = NONE) finish the BatchNorm backward without a reduce sweep.            */
+ *              sgx_bn_bwd_finalize + sgx_bn_bwd_apply(act = NONE) finish the BatchNorm backward without a reduce sweep.
+ * Addresses (vectors and workspace included) and row strides: multiples of 16 bytes, as above (SGX_ERR_BAD_ARG otherwise).                */
 int32_t sgx_bn_gate_act_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
                             float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, int32_t act, void* stream);
 int64_t sgx_bn_gate_act_bwd_gate_workspace(int32_t N, int32_t HW, int32_t C);

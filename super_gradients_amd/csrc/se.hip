@@ -12,6 +12,9 @@
 #define SE_THREADS 256
 #define SE_MAXCG 64      // float4 channel groups per workgroup strip
 #define SE_CHUNK_ROWS 512  // pixels per chunk: 160x160 maps -> 50 chunks per image, 32 images -> 1600 workgroups per strip
+// every kernel here moves float4: addresses (NULL passes: an absent operand) and strides must be multiples of 16 bytes
+#define SE_ALIGNED(p) (((uintptr_t)(p) % 16) == 0)
+#define SE_LD4(ld) ((ld) % 4 == 0)
 
 __device__ __forceinline__ float se_gate(float p, int gate) {
     if (gate == SGX_GATE_HARDSIGMOID) return fminf(fmaxf(p * (1.f / 6.f) + 0.5f, 0.f), 1.f);
@@ -97,6 +100,9 @@ extern "C" int32_t sgx_image_colsum(int32_t N, int32_t HW, int32_t C, const floa
                                     int64_t ws_bytes, void* stream) {
     SGX_CHECK_ARG(u && out && ws && N > 0 && HW > 0 && C > 0 && C % 4 == 0, "image_colsum: bad args (C=%d)", C);
     SGX_CHECK_ARG(ws_bytes >= sgx_image_colsum_workspace(N, HW, C), "image_colsum: workspace too small");
+    SGX_CHECK_ARG(SE_LD4(u_ld_pix) && SE_LD4(u_ld_img) && (!v || (SE_LD4(v_ld_pix) && SE_LD4(v_ld_img))) && SE_ALIGNED(u) && SE_ALIGNED(v) && SE_ALIGNED(pre) &&
+                      SE_ALIGNED(out) && SE_ALIGNED(ws),
+                  "image_colsum: strides and addresses must be multiples of 16 bytes");
     SeGeom g = se_geom(N, HW, C);
     SGX_LAUNCH(image_colsum_kernel, dim3((unsigned)((long)N * g.chunks), g.ctiles), dim3(SE_THREADS), 0, stream, g, u, (long)u_ld_pix,
                (long)u_ld_img, v, (long)v_ld_pix, (long)v_ld_img, (float*)ws);
@@ -137,6 +143,8 @@ extern "C" int32_t sgx_channel_gate(int32_t N, int32_t HW, int32_t C, const floa
                                     int32_t accumulate, void* stream) {
     SGX_CHECK_ARG(x && pre && y && N > 0 && HW > 0 && C > 0 && C % 4 == 0, "channel_gate: bad args (C=%d)", C);
     SGX_CHECK_ARG(gate >= SGX_GATE_NONE && gate <= SGX_GATE_SIGMOID, "channel_gate: unknown gate %d", gate);
+    SGX_CHECK_ARG(SE_LD4(x_ld_pix) && SE_LD4(x_ld_img) && SE_LD4(y_ld_pix) && SE_LD4(y_ld_img) && SE_ALIGNED(x) && SE_ALIGNED(y) && SE_ALIGNED(pre) && SE_ALIGNED(bias),
+                  "channel_gate: strides and addresses must be multiples of 16 bytes");
     long n = (long)N * HW * (C / 4), blocks = (n + 255) / 256;
     SGX_LAUNCH(channel_gate_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, stream, N, HW, C, x, (long)x_ld_pix,
                (long)x_ld_img, pre, gate, bias, bias_scale, y, (long)y_ld_pix, (long)y_ld_img, accumulate);
@@ -190,6 +198,8 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(int N, int H, int W
 extern "C" int32_t sgx_upsample2x_fwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y,
                                       int64_t y_ld_pix, int64_t y_ld_img, void* stream) {
     SGX_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "upsample2x_fwd: bad args (C=%d)", C);
+    SGX_CHECK_ARG(SE_LD4(x_ld_pix) && SE_LD4(x_ld_img) && SE_LD4(y_ld_pix) && SE_LD4(y_ld_img) && SE_ALIGNED(x) && SE_ALIGNED(y),
+                  "upsample2x_fwd: strides and addresses must be multiples of 16 bytes");
     long n = (long)N * H * W * (C / 4), blocks = (n + 255) / 256;
     SGX_LAUNCH(upsample2x_fwd_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, stream, N, H, W, C, x, (long)x_ld_pix,
                (long)x_ld_img, y, (long)y_ld_pix, (long)y_ld_img);
@@ -199,6 +209,8 @@ extern "C" int32_t sgx_upsample2x_fwd(int32_t N, int32_t H, int32_t W, int32_t C
 extern "C" int32_t sgx_upsample2x_bwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img,
                                       float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream) {
     SGX_CHECK_ARG(dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "upsample2x_bwd: bad args (C=%d)", C);
+    SGX_CHECK_ARG(SE_LD4(dy_ld_pix) && SE_LD4(dy_ld_img) && SE_LD4(dx_ld_pix) && SE_LD4(dx_ld_img) && SE_ALIGNED(dy) && SE_ALIGNED(dx),
+                  "upsample2x_bwd: strides and addresses must be multiples of 16 bytes");
     long n = (long)N * H * W * (C / 4), blocks = (n + 255) / 256;
     SGX_LAUNCH(upsample2x_bwd_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, stream, N, H, W, C, dy, (long)dy_ld_pix,
                (long)dy_ld_img, dx, (long)dx_ld_pix, (long)dx_ld_img, accumulate);
@@ -249,6 +261,8 @@ extern "C" int32_t sgx_bn_gate_act_fwd(const float* x, int64_t x_ld, const float
                                        float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, int32_t act, void* stream) {
     SGX_CHECK_ARG(x && pre && y, "bn_gate_act_fwd: null pointer");
     SE_CHECK_GATE_SWEEP("bn_gate_act_fwd");
+    SGX_CHECK_ARG(SE_LD4(x_ld) && SE_LD4(y_ld) && SE_ALIGNED(x) && SE_ALIGNED(y) && SE_ALIGNED(scale) && SE_ALIGNED(shift) && SE_ALIGNED(pre),
+                  "bn_gate_act_fwd: strides and addresses must be multiples of 16 bytes");
     BnGateActFwdF f{x, x_ld, scale, shift, pre, gate, sgx_make_fastdiv(HW), C, y, y_ld, act};
     return run_sweep<BnGateActFwdF, 0, 4>(f, (long)N * HW, C, nullptr, stream, "bn_gate_act_fwd");
 }
@@ -293,6 +307,9 @@ extern "C" int32_t sgx_bn_gate_act_bwd_gate(const float* dy, int64_t dy_ld, cons
                                             int64_t ws_bytes, void* stream) {
     SGX_CHECK_ARG(dy && x && pre && dpre && ws, "bn_gate_act_bwd_gate: null pointer");
     SE_CHECK_GATE_SWEEP("bn_gate_act_bwd_gate");
+    SGX_CHECK_ARG(SE_LD4(dy_ld) && SE_LD4(x_ld) && SE_ALIGNED(dy) && SE_ALIGNED(x) && SE_ALIGNED(scale) && SE_ALIGNED(shift) && SE_ALIGNED(pre) && SE_ALIGNED(dpre) &&
+                      SE_ALIGNED(ws),
+                  "bn_gate_act_bwd_gate: strides and addresses must be multiples of 16 bytes");
     if (ws_bytes < sgx_bn_gate_act_bwd_gate_workspace(N, HW, C)) SGX_FAIL(SGX_ERR_WORKSPACE, "bn_gate_act_bwd_gate: workspace too small (sgx_bn_gate_act_bwd_gate_workspace)");
     SeGeom g = se_geom(N, HW, C);
     SGX_LAUNCH(bn_gate_bwd_colsum_kernel, dim3((unsigned)((long)N * g.chunks), g.ctiles), dim3(SE_THREADS), 0, stream, g, dy, (long)dy_ld, x, (long)x_ld, scale,
@@ -328,6 +345,9 @@ extern "C" int32_t sgx_bn_gate_act_bwd_data(const float* dy, int64_t dy_ld, cons
                                             const float* save_mean, float* partials, int32_t N, int32_t HW, int32_t C, void* stream) {
     SGX_CHECK_ARG(dy && x && pre && dz, "bn_gate_act_bwd_data: null pointer");
     SE_CHECK_GATE_SWEEP("bn_gate_act_bwd_data");
+    SGX_CHECK_ARG(SE_LD4(dy_ld) && SE_LD4(x_ld) && SE_LD4(dz_ld) && SE_ALIGNED(dy) && SE_ALIGNED(x) && SE_ALIGNED(dz) && SE_ALIGNED(scale) && SE_ALIGNED(shift) &&
+                      SE_ALIGNED(pre) && SE_ALIGNED(dmean) && SE_ALIGNED(save_mean) && SE_ALIGNED(partials),
+                  "bn_gate_act_bwd_data: strides and addresses must be multiples of 16 bytes");
     SGX_CHECK_ARG(!partials || save_mean, "bn_gate_act_bwd_data: the reduce rows need save_mean");
     BnGateActBwdDataF f{dy, dy_ld, x, x_ld, scale, shift, pre, gate, act, dmean, 1.f / (float)HW, sgx_make_fastdiv(HW), C, dz, dz_ld, save_mean};
     return run_sweep<BnGateActBwdDataF, 2, 2>(f, (long)N * HW, C, partials, stream, "bn_gate_act_bwd_data");

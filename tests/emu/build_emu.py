@@ -16,7 +16,7 @@ CXX = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 def build(force=False, verbose=False):
     os.makedirs(OUTDIR, exist_ok=True)
     deps = [os.path.join(HERE, "hip_emu.h"), os.path.join(HERE, "hip_emu.cpp"), os.path.join(CSRC, "sgx_common.h"), os.path.join(CSRC, "conv_mma.h"), os.path.join(CSRC, "wgrad_patch.h"),
-            os.path.join(CSRC, "..", "..", "include", "sgx_hip.h")]
+            os.path.join(CSRC, "sgx_sweep.h"), os.path.join(CSRC, "gconv.h"), os.path.join(CSRC, "..", "..", "include", "sgx_hip.h")]
     objs, procs = [], []
     for src in SOURCES + ["hip_emu.cpp"]:
         sp = os.path.join(HERE if src == "hip_emu.cpp" else CSRC, src)
