@@ -592,6 +592,35 @@ int32_t sgx_bn_gate_act_bwd_data(const float* dy, int64_t dy_ld, const float* x,
                                  const float* pre, int32_t gate, int32_t act, const float* dmean, float* dz, int64_t dz_ld,
                                  const float* save_mean, float* partials, int32_t N, int32_t HW, int32_t C, void* stream);
 
+/* BatchNorm -> activation -> squeeze-excitation gate as fused sweeps (EfficientNet's MBConvBlock: dw -> BN -> SiLU -> SE,
+ * classification_models/efficientnet.py:370-380).  z, s, rows and alignment as in sgx_bn_gate_act_*; a = act(z), y = s * a.  The SE
+ * layer's means are those of a, which are not affine in the means of x: _mean takes them in a pass that reads x and stores no map.
+ *   _mean      out[n][c] = (1 / HW) * sum over the image's pixels of act(z); two-stage, deterministic (fp32 chunk partials, fp64
+ *              finalize in fixed order; ws: sgx_bn_act_gate_mean_workspace bytes).  _mean and _bwd_gate cut an image into chunks of
+ *              16 rows per row lane (256 / min(C / 4, 64) lanes) - finer than sgx_image_colsum's, and a function of C alone.
+ *   _fwd       y = s * act(z), one pass.
+ *   _bwd_gate  dpre[n][c] = f'(pre) * sum over the image's pixels of dy * act(z); two-stage, deterministic
+ *              (ws: sgx_bn_act_gate_bwd_gate_workspace bytes).
+ *   _bwd_data  dz = (dy * s + dmean[n][c] / HW) * act'(z) (dmean may be NULL), stored - dz == dy in place is allowed; partials != NULL:
+ *              the [2][sgx_stats_blocks(N * HW)][C] rows sum dz, sum dz * (x - save_mean), bit for bit sgx_bn_bwd_reduce(dz, x, act = NONE)'s. */
+int64_t sgx_bn_act_gate_mean_workspace(int32_t N, int32_t HW, int32_t C);
+int32_t sgx_bn_act_gate_mean(const float* x, int64_t x_ld, const float* scale, const float* shift, int32_t act, float* out, int32_t N, int32_t HW,
+                             int32_t C, void* ws, int64_t ws_bytes, void* stream);
+int32_t sgx_bn_act_gate_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
+                            float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, int32_t act, void* stream);
+int64_t sgx_bn_act_gate_bwd_gate_workspace(int32_t N, int32_t HW, int32_t C);
+int32_t sgx_bn_act_gate_bwd_gate(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                 const float* pre, int32_t gate, int32_t act, float* dpre, int32_t N, int32_t HW, int32_t C, void* ws,
+                                 int64_t ws_bytes, void* stream);
+int32_t sgx_bn_act_gate_bwd_data(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                 const float* pre, int32_t gate, int32_t act, const float* dmean, float* dz, int64_t dz_ld,
+                                 const float* save_mean, float* partials, int32_t N, int32_t HW, int32_t C, void* stream);
+/* y = f(pre[n][c]) * (scale[c] * x + shift[c]) + r (scale == shift == NULL: z = x), the residual r at its own row stride; y may alias x or
+ * r.  With gate NONE and pre[n][:] = m[n] it is EfficientNet's drop-connect residual in the BatchNorm's own sweep.  Its backward is
+ * sgx_bn_gate_act_bwd_data(gate, act NONE, dmean NULL, partials): f(pre) * dy and the reduce rows in one sweep; dy is r's gradient.        */
+int32_t sgx_bn_gate_add_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
+                            const float* r, int64_t r_ld, float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Detection head decode, PPYoloELoss (assigner + VFL/GIoU/DFL with hand-written backward), NMS.
  * ------------------------------------------------------------------------------------------- */

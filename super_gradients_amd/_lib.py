@@ -199,6 +199,13 @@ PROTOTYPES = {
     "sgx_bn_gate_act_bwd_gate_workspace": (_i64, [_i32] * 3),
     "sgx_bn_gate_act_bwd_gate": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _P, _i64, _P]),
     "sgx_bn_gate_act_bwd_data": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _P, _i64, _P, _P, _i32, _i32, _i32, _P]),
+    "sgx_bn_act_gate_mean_workspace": (_i64, [_i32] * 3),
+    "sgx_bn_act_gate_mean": (_i32, [_P, _i64, _P, _P, _i32, _P, _i32, _i32, _i32, _P, _i64, _P]),
+    "sgx_bn_act_gate_fwd": (_i32, [_P, _i64, _P, _P, _P, _i32, _P, _i64, _i32, _i32, _i32, _i32, _P]),
+    "sgx_bn_act_gate_bwd_gate_workspace": (_i64, [_i32] * 3),
+    "sgx_bn_act_gate_bwd_gate": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _P, _i64, _P]),
+    "sgx_bn_act_gate_bwd_data": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _P, _i64, _P, _P, _i32, _i32, _i32, _P]),
+    "sgx_bn_gate_add_fwd": (_i32, [_P, _i64, _P, _P, _P, _i32, _P, _i64, _P, _i64, _i32, _i32, _i32, _P]),
     "sgx_dropout_fwd": (_i32, [_P, _i64, _P, _i64, _i64, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _P]),
     "sgx_tri_affine_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _f, _P, _P, _i64, _i64, _i32, _i32, _P, _i32, _P]),
     "sgx_tri_affine_act_bwd_reduce": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _i64, _i32, _i32,

@@ -2,6 +2,8 @@
 //   EffectiveSEBlock  modules/se_blocks.py:29-42           y = x * hardsigmoid(project(mean_hw x))
 //   ESEAttn           pp_yolo_e/pp_yolo_head.py:79-93      conv(feat * sigmoid(fc(avg_feat)))
 //   F.interpolate(x2, nearest)  pp_yolo_e/pan.py:170
+// and, further down, the fused BatchNorm / gate / activation sweeps of MobileNetV3 (gate, then activation) and EfficientNet (activation,
+// then gate; drop-connect).
 // Data layout: NHWC views with explicit pixel / image strides (channel slices of concat buffers are read and written in place);
 // per-image vectors ([N][C] means, gate pre-activations, their gradients) are contiguous.
 // The per-image reductions are two-stage and deterministic: a (image, pixel chunk, channel strip) grid leaves fp32 partial rows,
@@ -351,4 +353,226 @@ extern "C" int32_t sgx_bn_gate_act_bwd_data(const float* dy, int64_t dy_ld, cons
     SGX_CHECK_ARG(!partials || save_mean, "bn_gate_act_bwd_data: the reduce rows need save_mean");
     BnGateActBwdDataF f{dy, dy_ld, x, x_ld, scale, shift, pre, gate, act, dmean, 1.f / (float)HW, sgx_make_fastdiv(HW), C, dz, dz_ld, save_mean};
     return run_sweep<BnGateActBwdDataF, 2, 2>(f, (long)N * HW, C, partials, stream, "bn_gate_act_bwd_data");
+}
+
+// ---------------------------------------------------------------------------------------------
+// BatchNorm -> activation -> squeeze-excitation gate as fused sweeps (EfficientNet's MBConv block: dw -> BN -> SiLU -> SE,
+// classification_models/efficientnet.py:370-380).  z and s as above, a = act(z), y = s * a.  The per-image means the SE layer needs are
+// those of a - not affine in anything cheaper - so they take a pass of their own (_mean: one read of x, a is never stored); the gate
+// multiplies the activated value, so act'(z) does not see it.  Same row convention, same reduce rows as the family above.
+__device__ __forceinline__ float4 act4(const float4& z, int act) { return make_float4(sgx_act6(z.x, act), sgx_act6(z.y, act), sgx_act6(z.z, act), sgx_act6(z.w, act)); }
+__device__ __forceinline__ float4 act4_grad(const float4& z, int act) {
+    return make_float4(sgx_act6_grad(z.x, act), sgx_act6_grad(z.y, act), sgx_act6_grad(z.z, act), sgx_act6_grad(z.w, act));
+}
+
+// Geometry of the two reductions over the activated map.  image_colsum's 512-pixel chunks leave 128 workgroups for a 64 x 28 x 28 x 240
+// map, each lane walking ~200 rows - with an exponential and a division per element that is a serial ALU chain on a quarter-filled chip.
+// Here a chunk is 16 rows per row lane (RL * 16 pixels: 512 at 32 channels, 64 from 256 channels up), a function of C alone, so the
+// partial rows [N][chunks][C] and the fp64 sums over them do not depend on anything but the shape.
+#define ACT_LANE_ROWS 16
+struct ActGeom {
+    int N, HW, C, C4, CG, RL, rows, chunks, ctiles;
+};
+static ActGeom act_geom(int N, int HW, int C) {
+    ActGeom g;
+    g.N = N; g.HW = HW; g.C = C; g.C4 = C / 4;
+    g.CG = g.C4 < SE_MAXCG ? g.C4 : SE_MAXCG;
+    g.RL = SE_THREADS / g.CG;
+    g.rows = g.RL * ACT_LANE_ROWS;
+    g.chunks = (HW + g.rows - 1) / g.rows;
+    g.ctiles = (g.C4 + g.CG - 1) / g.CG;
+    return g;
+}
+static int64_t act_workspace(int32_t N, int32_t HW, int32_t C) {
+    if (N <= 0 || HW <= 0 || C < 4) return 256;
+    ActGeom g = act_geom(N, HW, C);
+    return (int64_t)N * g.chunks * C * (int64_t)sizeof(float) + 256;
+}
+// partials [N][chunks][C] of sum_p act(z) (DY false) or sum_p dy * act(z): image_colsum's first stage on the activated value, four rows
+// of a lane in flight
+template <bool DY>
+__global__ __launch_bounds__(SE_THREADS) void bn_act_colsum_kernel(ActGeom g, const float* dy, long dy_ld, const float* x, long x_ld, const float* scale,
+                                                                   const float* shift, int act, float* partials) {
+    __shared__ float4 red[SE_THREADS];
+    const int tid = threadIdx.x;
+    const int cg = tid % g.CG, rl = tid / g.CG;
+    const int c4 = blockIdx.y * g.CG + cg;
+    const int chunk = blockIdx.x % g.chunks, img = blockIdx.x / g.chunks;
+    const bool live = (rl < g.RL) && (c4 < g.C4);
+    const int c = c4 * 4;
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+        int p0 = chunk * g.rows, p1 = p0 + g.rows;
+        if (p1 > g.HW) p1 = g.HW;
+        const GateZ k = gate_z(scale, shift, c);
+        const float* xb = x + (long)img * g.HW * x_ld + c;
+        const float* db = DY ? dy + (long)img * g.HW * dy_ld + c : nullptr;
+        const int st = g.RL;
+        int p = p0 + rl;
+        for (; p + 3 * st < p1; p += 4 * st) {
+            float4 v[4], d[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[u] = sgx_ld4(xb + (long)(p + u * st) * x_ld);
+                if (DY) d[u] = sgx_ld4(db + (long)(p + u * st) * dy_ld);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float4 a = act4(k.z(v[u]), act);
+                if (DY) {
+                    q.x += d[u].x * a.x; q.y += d[u].y * a.y; q.z += d[u].z * a.z; q.w += d[u].w * a.w;
+                } else {
+                    q.x += a.x; q.y += a.y; q.z += a.z; q.w += a.w;
+                }
+            }
+        }
+        for (; p < p1; p += st) {
+            const float4 a = act4(k.z(sgx_ld4(xb + (long)p * x_ld)), act);
+            if (DY) {
+                const float4 d = sgx_ld4(db + (long)p * dy_ld);
+                q.x += d.x * a.x; q.y += d.y * a.y; q.z += d.z * a.z; q.w += d.w * a.w;
+            } else {
+                q.x += a.x; q.y += a.y; q.z += a.z; q.w += a.w;
+            }
+        }
+    }
+    red[tid] = q;
+    __syncthreads();
+    if (live && rl == 0) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int k = 0; k < g.RL; ++k) {
+            float4 a = red[k * g.CG + cg];
+            s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
+        }
+        sgx_st4(partials + ((long)img * g.chunks + chunk) * g.C + c, s);
+    }
+}
+#define SE_CHECK_ACT_SWEEP(what)                                                                                                         \
+    SGX_CHECK_ARG(N > 0 && HW > 0 && C > 0 && C % 4 == 0 && (long)N * HW < 0x7fffffffL, "%s: bad dims N=%d HW=%d C=%d", what, N, HW, C);   \
+    SGX_CHECK_ACT4(act, what);                                                                                                           \
+    SGX_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", what)
+extern "C" int64_t sgx_bn_act_gate_mean_workspace(int32_t N, int32_t HW, int32_t C) { return act_workspace(N, HW, C); }
+extern "C" int32_t sgx_bn_act_gate_mean(const float* x, int64_t x_ld, const float* scale, const float* shift, int32_t act, float* out, int32_t N, int32_t HW,
+                                        int32_t C, void* ws, int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(x && out && ws, "bn_act_gate_mean: null pointer");
+    SE_CHECK_ACT_SWEEP("bn_act_gate_mean");
+    SGX_CHECK_ARG(SE_LD4(x_ld) && SE_ALIGNED(x) && SE_ALIGNED(scale) && SE_ALIGNED(shift) && SE_ALIGNED(out) && SE_ALIGNED(ws),
+                  "bn_act_gate_mean: strides and addresses must be multiples of 16 bytes");
+    if (ws_bytes < sgx_bn_act_gate_mean_workspace(N, HW, C)) SGX_FAIL(SGX_ERR_WORKSPACE, "bn_act_gate_mean: workspace too small (sgx_bn_act_gate_mean_workspace)");
+    ActGeom g = act_geom(N, HW, C);
+    SGX_LAUNCH(bn_act_colsum_kernel<false>, dim3((unsigned)((long)N * g.chunks), g.ctiles), dim3(SE_THREADS), 0, stream, g, (const float*)nullptr, 0L, x, (long)x_ld,
+               scale, shift, act, (float*)ws);
+    SGX_CHECK_LAUNCH("bn_act_gate_mean");
+    SGX_LAUNCH(image_colsum_finalize_kernel, dim3(sgx_cdiv((long)N * C, 256)), dim3(256), 0, stream, N, g.chunks, C, (const float*)ws, 1.f / (float)HW,
+               (const float*)nullptr, SGX_GATE_NONE, out);
+    SGX_CHECK_LAUNCH("bn_act_gate_mean (finalize)");
+    return SGX_OK;
+}
+
+struct BnActGateFwdF {
+    const float* x; long x_ld; const float* scale; const float* shift; const float* pre; int gate; sgx_fastdiv hw; int C;
+    float* y; long y_ld; int act;
+    struct In { float4 v, p; };
+    __device__ In load(long r, int c) const { return In{sgx_ld4(x + r * x_ld + c), sgx_ld4(pre + (long)sgx_fdiv((int)r, hw) * C + c)}; }
+    typedef GateZ Cst;
+    __device__ Cst consts(int c) const { return gate_z(scale, shift, c); }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&)[1]) const {
+        const float4 a = act4(k.z(in.v), act), s = se_gate4(in.p, gate);
+        sgx_st4(y + r * y_ld + c, make_float4(s.x * a.x, s.y * a.y, s.z * a.z, s.w * a.w));
+    }
+};
+extern "C" int32_t sgx_bn_act_gate_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
+                                       float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, int32_t act, void* stream) {
+    SGX_CHECK_ARG(x && pre && y, "bn_act_gate_fwd: null pointer");
+    SE_CHECK_GATE_SWEEP("bn_act_gate_fwd");
+    SGX_CHECK_ARG(SE_LD4(x_ld) && SE_LD4(y_ld) && SE_ALIGNED(x) && SE_ALIGNED(y) && SE_ALIGNED(scale) && SE_ALIGNED(shift) && SE_ALIGNED(pre),
+                  "bn_act_gate_fwd: strides and addresses must be multiples of 16 bytes");
+    BnActGateFwdF f{x, x_ld, scale, shift, pre, gate, sgx_make_fastdiv(HW), C, y, y_ld, act};
+    return run_sweep<BnActGateFwdF, 0, 4>(f, (long)N * HW, C, nullptr, stream, "bn_act_gate_fwd");
+}
+
+// d pre[n][c] = f'(pre) * sum over the image's pixels of dy * act(z)
+extern "C" int64_t sgx_bn_act_gate_bwd_gate_workspace(int32_t N, int32_t HW, int32_t C) { return act_workspace(N, HW, C); }
+extern "C" int32_t sgx_bn_act_gate_bwd_gate(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                            const float* pre, int32_t gate, int32_t act, float* dpre, int32_t N, int32_t HW, int32_t C, void* ws,
+                                            int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(dy && x && pre && dpre && ws, "bn_act_gate_bwd_gate: null pointer");
+    SE_CHECK_GATE_SWEEP("bn_act_gate_bwd_gate");
+    SGX_CHECK_ARG(SE_LD4(dy_ld) && SE_LD4(x_ld) && SE_ALIGNED(dy) && SE_ALIGNED(x) && SE_ALIGNED(scale) && SE_ALIGNED(shift) && SE_ALIGNED(pre) && SE_ALIGNED(dpre) &&
+                      SE_ALIGNED(ws),
+                  "bn_act_gate_bwd_gate: strides and addresses must be multiples of 16 bytes");
+    if (ws_bytes < sgx_bn_act_gate_bwd_gate_workspace(N, HW, C)) SGX_FAIL(SGX_ERR_WORKSPACE, "bn_act_gate_bwd_gate: workspace too small (sgx_bn_act_gate_bwd_gate_workspace)");
+    ActGeom g = act_geom(N, HW, C);
+    SGX_LAUNCH(bn_act_colsum_kernel<true>, dim3((unsigned)((long)N * g.chunks), g.ctiles), dim3(SE_THREADS), 0, stream, g, dy, (long)dy_ld, x, (long)x_ld, scale, shift,
+               act, (float*)ws);
+    SGX_CHECK_LAUNCH("bn_act_gate_bwd_gate");
+    SGX_LAUNCH(image_colsum_finalize_kernel, dim3(sgx_cdiv((long)N * C, 256)), dim3(256), 0, stream, N, g.chunks, C, (const float*)ws, 1.f, pre, gate, dpre);
+    SGX_CHECK_LAUNCH("bn_act_gate_bwd_gate (finalize)");
+    return SGX_OK;
+}
+
+// dz = (dy * s + dmean[n][c] / HW) * act'(z), stored; with `partials` also the rows sum dz, sum dz * (x - save_mean) of the BatchNorm backward
+struct BnActGateBwdDataF {
+    const float* dy; long dy_ld; const float* x; long x_ld; const float* scale; const float* shift; const float* pre; int gate; int act;
+    const float* dmean; float inv_hw; sgx_fastdiv hw; int C; float* dz; long dz_ld; const float* mean;
+    struct In { float4 d, v, p, m; };
+    __device__ In load(long r, int c) const {
+        const long o = (long)sgx_fdiv((int)r, hw) * C + c;
+        return In{sgx_ld4(dy + r * dy_ld + c), sgx_ld4(x + r * x_ld + c), sgx_ld4(pre + o), dmean ? sgx_ld4(dmean + o) : make_float4(0.f, 0.f, 0.f, 0.f)};
+    }
+    struct Cst { GateZ k; float4 mu; };
+    __device__ Cst consts(int c) const { return Cst{gate_z(scale, shift, c), mean ? sgx_ld4(mean + c) : make_float4(0.f, 0.f, 0.f, 0.f)}; }
+    // (dz ends in a product: contracted into the row sums below it would enter them unrounded, and the rows would not be the ones
+    // sgx_bn_bwd_reduce forms from the stored dz)
+    __device__ float4 grad(const float4& d, const float4& s, const float4& m, const float4& ga) const {
+#pragma clang fp contract(off)
+        return make_float4((d.x * s.x + m.x * inv_hw) * ga.x, (d.y * s.y + m.y * inv_hw) * ga.y, (d.z * s.z + m.z * inv_hw) * ga.z, (d.w * s.w + m.w * inv_hw) * ga.w);
+    }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&q)[2]) const {
+        const float4 v = in.v, mu = k.mu, o = grad(in.d, se_gate4(in.p, gate), in.m, act4_grad(k.k.z(v), act));
+        const float gx = o.x, gy = o.y, gz = o.z, gw = o.w;
+        sgx_st4(dz + r * dz_ld + c, o);
+        q[0].x += gx; q[0].y += gy; q[0].z += gz; q[0].w += gw;
+        q[1].x += gx * (v.x - mu.x); q[1].y += gy * (v.y - mu.y); q[1].z += gz * (v.z - mu.z); q[1].w += gw * (v.w - mu.w);
+    }
+};
+extern "C" int32_t sgx_bn_act_gate_bwd_data(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                            const float* pre, int32_t gate, int32_t act, const float* dmean, float* dz, int64_t dz_ld,
+                                            const float* save_mean, float* partials, int32_t N, int32_t HW, int32_t C, void* stream) {
+    SGX_CHECK_ARG(dy && x && pre && dz, "bn_act_gate_bwd_data: null pointer");
+    SE_CHECK_GATE_SWEEP("bn_act_gate_bwd_data");
+    SGX_CHECK_ARG(SE_LD4(dy_ld) && SE_LD4(x_ld) && SE_LD4(dz_ld) && SE_ALIGNED(dy) && SE_ALIGNED(x) && SE_ALIGNED(dz) && SE_ALIGNED(scale) && SE_ALIGNED(shift) &&
+                      SE_ALIGNED(pre) && SE_ALIGNED(dmean) && SE_ALIGNED(save_mean) && SE_ALIGNED(partials),
+                  "bn_act_gate_bwd_data: strides and addresses must be multiples of 16 bytes");
+    SGX_CHECK_ARG(!partials || save_mean, "bn_act_gate_bwd_data: the reduce rows need save_mean");
+    BnActGateBwdDataF f{dy, dy_ld, x, x_ld, scale, shift, pre, gate, act, dmean, 1.f / (float)HW, sgx_make_fastdiv(HW), C, dz, dz_ld, save_mean};
+    return run_sweep<BnActGateBwdDataF, 2, 2>(f, (long)N * HW, C, partials, stream, "bn_act_gate_bwd_data");
+}
+
+// y = f(pre[n][c]) * z + r: a per-image multiplier inside the BatchNorm sweep together with the residual (drop-connect: gate NONE,
+// pre[n][:] = the image's 0 or 1 / keep).  Backward: sgx_bn_gate_act_bwd_data(gate, act NONE) writes f(pre) * dy and the reduce rows.
+struct BnGateAddFwdF {
+    const float* x; long x_ld; const float* scale; const float* shift; const float* pre; int gate; sgx_fastdiv hw; int C;
+    const float* res; long r_ld; float* y; long y_ld;
+    struct In { float4 v, p, r; };
+    __device__ In load(long r, int c) const {
+        return In{sgx_ld4(x + r * x_ld + c), sgx_ld4(pre + (long)sgx_fdiv((int)r, hw) * C + c), sgx_ld4(res + r * r_ld + c)};
+    }
+    typedef GateZ Cst;
+    __device__ Cst consts(int c) const { return gate_z(scale, shift, c); }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&)[1]) const {
+        const float4 z = k.z(in.v), s = se_gate4(in.p, gate);
+        sgx_st4(y + r * y_ld + c, make_float4(s.x * z.x + in.r.x, s.y * z.y + in.r.y, s.z * z.z + in.r.z, s.w * z.w + in.r.w));
+    }
+};
+extern "C" int32_t sgx_bn_gate_add_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* pre, int32_t gate,
+                                       const float* r, int64_t r_ld, float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, void* stream) {
+    SGX_CHECK_ARG(x && pre && r && y, "bn_gate_add_fwd: null pointer");
+    const int32_t act = SGX_ACT_NONE;
+    SE_CHECK_GATE_SWEEP("bn_gate_add_fwd");
+    SGX_CHECK_ARG(SE_LD4(x_ld) && SE_LD4(r_ld) && SE_LD4(y_ld) && SE_ALIGNED(x) && SE_ALIGNED(r) && SE_ALIGNED(y) && SE_ALIGNED(scale) && SE_ALIGNED(shift) &&
+                      SE_ALIGNED(pre),
+                  "bn_gate_add_fwd: strides and addresses must be multiples of 16 bytes");
+    BnGateAddFwdF f{x, x_ld, scale, shift, pre, gate, sgx_make_fastdiv(HW), C, r, r_ld, y, y_ld};
+    return run_sweep<BnGateAddFwdF, 0, 2>(f, (long)N * HW, C, nullptr, stream, "bn_gate_add_fwd");
 }

@@ -1107,6 +1107,56 @@ def bn_gate_act_bwd_data(dy, x, scale, shift, pre, gate, act=None, dmean=None, s
     return (out, parts) if want_parts else out
 
 
+def bn_act_gate_mean(x, scale, shift, act=None):
+    """out[n,c] = mean over the image's pixels of act(scale * x + shift)   ([N,C]; the activated map is not stored)."""
+    n, hw, c, ld = _gate_rows(x)
+    out = torch.empty(n, c, device=x.device, dtype=torch.float32)
+    ws = WORKSPACE.get(lib().sgx_bn_act_gate_mean_workspace(n, hw, c), x.device)
+    check(lib().sgx_bn_act_gate_mean(ptr(x), ld, ptr(scale), ptr(shift), ACT[act], ptr(out), n, hw, c, ptr(ws), ws.numel(), stream()), "sgx_bn_act_gate_mean")
+    return out
+
+
+def bn_act_gate_fwd(x, scale, shift, pre, gate, act=None, out=None):
+    """y = f(pre[n,c]) * act(scale * x + shift); scale = shift = None: z = x (the folded eval form)."""
+    n, hw, c, ld = _gate_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(lib().sgx_bn_act_gate_fwd(ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ptr(out), rows(out)[1], n, hw, c, ACT[act], stream()),
+          "sgx_bn_act_gate_fwd")
+    return out
+
+
+def bn_act_gate_bwd_gate(dy, x, scale, shift, pre, gate, act=None):
+    """dpre[n,c] = f'(pre) * sum_pixels dy * act(z)."""
+    n, hw, c, ld = _gate_rows(x)
+    out = torch.empty(n, c, device=x.device, dtype=torch.float32)
+    ws = WORKSPACE.get(lib().sgx_bn_act_gate_bwd_gate_workspace(n, hw, c), x.device)
+    check(lib().sgx_bn_act_gate_bwd_gate(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(out), n, hw, c, ptr(ws),
+                                         ws.numel(), stream()), "sgx_bn_act_gate_bwd_gate")
+    return out
+
+
+def bn_act_gate_bwd_data(dy, x, scale, shift, pre, gate, act=None, dmean=None, save_mean=None, out=None, want_parts=False):
+    """dz = (dy * f(pre) + dmean[n,c] / HW) * act'(z) -> dz, or (dz, parts) with the BatchNorm-backward reduce rows of (dz, x) (bn_bwd(parts=...))."""
+    n, hw, c, ld = _gate_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    parts = torch.empty(2, stats_blocks(n * hw), c, device=x.device, dtype=torch.float32) if want_parts else None
+    check(lib().sgx_bn_act_gate_bwd_data(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(dmean), ptr(out),
+                                         rows(out)[1], ptr(save_mean), ptr(parts), n, hw, c, stream()), "sgx_bn_act_gate_bwd_data")
+    return (out, parts) if want_parts else out
+
+
+def bn_gate_add(x, scale, shift, pre, gate, r, out=None):
+    """y = f(pre[n,c]) * (scale * x + shift) + r: a per-image multiplier and the residual in the BatchNorm's own sweep (drop-connect)."""
+    n, hw, c, ld = _gate_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(lib().sgx_bn_gate_add_fwd(ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ptr(r), rows(r)[1], ptr(out), rows(out)[1], n, hw, c, stream()),
+          "sgx_bn_gate_add_fwd")
+    return out
+
+
 def dropout(x, p, seed, offset=0, out=None):
     """y = x * mask / (1 - p) over a [M, C] matrix or an NHWC view; the backward is the same call on dy with the same (seed, offset)."""
     if x.dim() == 2:

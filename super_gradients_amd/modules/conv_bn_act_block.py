@@ -35,7 +35,7 @@ class _ConvBN(SgxBlock):
     """Shared implementation; subclasses only choose where `conv`/`bn` are registered (key names)."""
 
     _folded = None  # (filter with the BatchNorm scale folded in, shift as bias): eval form set by prep_model_for_conversion
-    _gate = None  # (SELayer,) between BatchNorm and activation (ConvBNView(gate=...)): the block then runs on the fused bn_gate_act sweeps
+    _gate = None  # (SE object,) fused with the BatchNorm and the activation (ConvBNView(gate=...)): the block then runs on the SE object's sweeps
     _folded_half = None  # the same for a channel-padded filter (C % 4 != 0: an RGB stem) - read by the half-precision path only, which re-lays filters out itself
 
     def _parts(self):
@@ -227,7 +227,9 @@ class ConvBNView(_ConvBN):
     several such triples: InvertedResidual.conv, mobilenetv2.py:70-93).  Owns no parameter: it adds nothing to the state_dict."""
 
     def __init__(self, conv, bn, activation_type=None, gate=None):
-        """gate: an SELayer (registered elsewhere too) that sits between the BatchNorm and the activation - y = act(se(bn(conv(x))))."""
+        """gate: an SE object (registered elsewhere too) whose fwd_fused / bwd_fused run the BatchNorm, the activation and the gate.  The
+        object chooses the order: SELayer (after_act False) sits between the BatchNorm and the activation - y = act(se(bn(conv(x)))), the
+        sgx_bn_gate_act_* sweeps; MBConvSE (after_act True) sits after the activation - y = se(act(bn(conv(x)))), the sgx_bn_act_gate_* sweeps."""
         super().__init__()
         self._pair = (conv, bn)  # (a tuple: not registered as sub-modules)
         self.act = act_name(activation_type)

@@ -7,4 +7,6 @@ from .classification_models import CustomMobileNetV2, MobileNetV2, MobileNetV2_1
 from .classification_models import MobileNetV3, mobilenetv3_custom, mobilenetv3_large, mobilenetv3_small  # noqa: F401
 from .classification_models import AnyNetX, CustomAnyNet, CustomRegNet, NASRegNet, RegNetX, RegNetY, RegNetY200, RegNetY400, RegNetY600, RegNetY800  # noqa: F401
 from .classification_models import GroupedConvBlock, ResNeXt, ResNeXt50, ResNeXt101  # noqa: F401
+from .classification_models import (CustomizedEfficientnet, EfficientNet, EfficientNetB0, EfficientNetB1, EfficientNetB2, EfficientNetB3, EfficientNetB4,  # noqa: F401
+                                    EfficientNetB5, EfficientNetB6, EfficientNetB7, EfficientNetB8, EfficientNetL2)
 from .detection_models.pp_yolo_e.pp_yolo_e import PPYoloE, PPYoloE_L, PPYoloE_M, PPYoloE_S, PPYoloE_X  # noqa: F401

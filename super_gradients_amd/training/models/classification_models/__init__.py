@@ -6,3 +6,6 @@ from .mobilenetv3 import MobileNetV3, mobilenetv3_custom, mobilenetv3_large, mob
 from .regnet import (AnyNetX, CustomAnyNet, CustomRegNet, Head, NASRegNet, RegNetX, RegNetY, RegNetY200, RegNetY400, RegNetY600, RegNetY800,  # noqa: F401
                      Stage, Stem, XBlock, regnet_params_to_blocks, verify_correctness_of_parameters)
 from .resnext import GroupedConvBlock, ResNeXt, ResNeXt50, ResNeXt101  # noqa: F401
+from .efficientnet import (BlockArgs, BlockDecoder, CustomizedEfficientnet, EfficientNet, EfficientNetB0, EfficientNetB1, EfficientNetB2,  # noqa: F401
+                           EfficientNetB3, EfficientNetB4, EfficientNetB5, EfficientNetB6, EfficientNetB7, EfficientNetB8, EfficientNetL2,
+                           MBConvBlock, round_filters, round_repeats)

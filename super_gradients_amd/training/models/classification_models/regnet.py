@@ -32,6 +32,7 @@ from ....common.registry import register_model
 from ....modules.conv_bn_act_block import Conv, ConvBNSeq
 from ....modules.engine import SgxBlock, SgxNetwork
 from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, GroupedConvLayer, LinearLayer
+from ....modules.se_blocks import ConvSqueezeExcite, _SEConv
 from ...utils.utils import get_param
 
 
@@ -42,94 +43,18 @@ class _Named(nn.Module):
         return list(self._modules.values())
 
 
-class _SEConv(SgxBlock):
-    """Parameters of one of the SE branch's nn.Conv2d(cin, cout, 1, bias=True): weight [cout, cin, 1, 1], bias [cout]."""
-
-    def __init__(self, cin, cout):
-        super().__init__()
-        self.in_channels, self.out_channels, self.kernel_size = cin, cout, 1
-        self.weight = nn.Parameter(torch.empty(cout, cin, 1, 1))
-        self.bias = nn.Parameter(torch.zeros(cout))
-        nn.init.kaiming_uniform_(self.weight, a=sqrt(5))
-        nn.init.uniform_(self.bias, -1.0 / sqrt(cin), 1.0 / sqrt(cin))
-
-    def on_materialize(self):
-        pass
-
-
-class SqueezeExcite(SgxBlock):
+class SqueezeExcite(ConvSqueezeExcite):
     """XBlock.se (regnet.py:71-81): x * sigmoid(conv2(relu(conv1(mean_hw(x))))); keys 1.weight / 1.bias / 3.weight / 3.bias as in the
-    reference's nn.Sequential (0: pool, 2: ReLU, 4: Sigmoid, 5: Residual hold no state)."""
-
-    GATE = "sigmoid"
-    _folded = None  # eval-mode cache of the zero-padded filters (dropped like the conv + BatchNorm folds)
+    reference's nn.Sequential (0: pool, 2: ReLU, 4: Sigmoid, 5: Residual hold no state).  The arithmetic - hidden widths padded to a
+    multiple of 4 inside - is modules/se_blocks.py's ConvSqueezeExcite."""
 
     def __init__(self, channels, hidden):
-        super().__init__()
-        if hidden < 1:
-            raise ValueError(f"SE hidden width {hidden}: the block's input width is smaller than se_ratio")
-        self.channels, self.hidden, self._hp = channels, hidden, (hidden + 3) // 4 * 4
+        super().__init__(channels, hidden)
         self.add_module("1", _SEConv(channels, hidden))
         self.add_module("3", _SEConv(hidden, channels))
 
-    def on_materialize(self):
-        pass
-
-    def _filters(self):
-        """(w1 [hp, C, 1, 1], b1 [hp], w2 [C, hp, 1, 1]): the parameters themselves, or zero-padded copies when hidden % 4 != 0"""
-        c1, c2 = self._modules["1"], self._modules["3"]
-        if self._hp == self.hidden:
-            return c1.weight, c1.bias, c2.weight
-        if not self.training and self._folded is not None:
-            return self._folded
-        dev = c1.weight.device
-        w1 = torch.zeros(self._hp, self.channels, 1, 1, device=dev)
-        w1[: self.hidden].copy_(c1.weight.detach())
-        b1 = torch.zeros(self._hp, device=dev)
-        b1[: self.hidden].copy_(c1.bias.detach())
-        w2 = torch.zeros(self.channels, self._hp, 1, 1, device=dev)
-        w2[:, : self.hidden].copy_(c2.weight.detach())
-        if not self.training:  # eval: the padded copies are kept until the weights change (train(), SgxNetwork.weights_changed)
-            self._folded = (w1, b1, w2)
-        return w1, b1, w2
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._folded = None
-        return super().train(mode)
-
-    def fwd(self, x, out=None):
-        n, h, w, c = x.shape
-        m = K.image_colsum(x, scale=1.0 / (h * w)).view(n, 1, 1, c)
-        w1, b1, w2 = self._filters()
-        hr = K.conv2d_fwd(m, w1, bias=b1, act="relu")
-        pre = K.conv2d_fwd(hr, w2, bias=self._modules["3"].bias).view(n, c)
-        self._ctx = (x, m, hr, pre, w1, w2) if self.training else None
-        return K.channel_gate(x, pre, self.GATE, out=out)
-
-    def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
-        (x, m, hr, pre, w1, w2), self._ctx = self._ctx, None
-        if addend is not None:
-            raise NotImplementedError("SqueezeExcite.bwd: no addend")
-        n, h, w, c = x.shape
-        c1, c2 = self._modules["1"], self._modules["3"]
-        padded = self._hp != self.hidden
-        dpre = K.image_colsum(dy, v=x, pre=pre, gate=self.GATE).view(n, 1, 1, c)
-        gw2 = torch.zeros_like(w2) if padded else c2.weight.grad
-        K.conv2d_bwd_weight(hr, dpre, gw2, c2.bias.grad)
-        dh = K.conv2d_bwd_data(dpre, w2, (n, 1, 1, self._hp))
-        dh = K.relu_bwd(dh, hr, out=dh)
-        gw1 = torch.zeros_like(w1) if padded else c1.weight.grad
-        gb1 = torch.zeros(self._hp, device=x.device) if padded else c1.bias.grad
-        K.conv2d_bwd_weight(m, dh, gw1, gb1)
-        if padded:  # the padded rows / columns saw zero filters: their gradients are dropped, the rest joins the parameters' gradients
-            c2.weight.grad.add_(gw2[:, : self.hidden])
-            c1.weight.grad.add_(gw1[: self.hidden])
-            c1.bias.grad.add_(gb1[: self.hidden])
-        dmean = K.conv2d_bwd_data(dh, w1, (n, 1, 1, c)).view(n, c)
-        if dx_out is None:
-            dx_out, accumulate = dy, False  # in place over the incoming gradient (element-wise)
-        return K.channel_gate(dy, pre, self.GATE, bias=dmean, bias_scale=1.0 / (h * w), out=dx_out, accumulate=accumulate)
+    def _convs(self):
+        return self._modules["1"], self._modules["3"]
 
 
 class Stem(Conv):
