@@ -622,6 +622,53 @@ int32_t sgx_bn_gate_add_fwd(const float* x, int64_t x_ld, const float* scale, co
                             const float* r, int64_t r_ld, float* y, int64_t y_ld, int32_t N, int32_t HW, int32_t C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Vision Transformer glue (classification_models/vit.py; csrc/vit.h): softmax attention, LayerNorm over the channel axis, exact GELU, the
+ * patch-row gather and the token assembly.  Tokens are pixels: a [B, T, D] sequence is the NHWC map [B, T, 1, D].  Every operand is a view
+ * with contiguous channels; every address a multiple of 16 bytes and every pixel / image / row stride a multiple of 4 floats
+ * (SGX_ERR_BAD_ARG otherwise, nothing is launched).  All reductions run in a fixed order: the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+/* y = x * Phi(x) (erf form, nn.GELU()'s default) / dx = dy * (Phi(x) + x * phi(x)) from the stored pre-activation; rows as in the BatchNorm
+ * sweeps (M rows of C channels at a row stride); dx may alias dy.                                                                          */
+int32_t sgx_gelu_fwd(const float* x, int64_t x_ld, float* y, int64_t y_ld, int64_t M, int32_t C, void* stream);
+int32_t sgx_gelu_bwd(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, float* dx, int64_t dx_ld, int64_t M, int32_t C, void* stream);
+/* LayerNorm over C (biased variance, 4 <= C <= 2048, C % 4 == 0): y = (x - mean) * rstd * gamma + beta, rstd = 1 / sqrt(var + eps).
+ *   _fwd  saves mean[M] / rstd[M] when the pointers are given (eval passes NULL).
+ *   _bwd  dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)) [+ addend], g = dy * gamma; dx may alias dy or addend.  dgamma / dbeta (both
+ *         or neither) are ADDED to in place: [2][ceil(M / sgx_layernorm_bwd_block_rows())][C] partial rows in ws
+ *         (sgx_layernorm_bwd_workspace bytes), then a finalize that adds them in block order in fp64.                                      */
+int32_t sgx_layernorm_fwd(const float* x, int64_t x_ld, const float* gamma, const float* beta, float eps, float* y, int64_t y_ld, float* mean,
+                          float* rstd, int64_t M, int32_t C, void* stream);
+int32_t sgx_layernorm_bwd_block_rows(void);
+int64_t sgx_layernorm_bwd_workspace(int64_t M, int32_t C);
+int32_t sgx_layernorm_bwd(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* gamma, const float* mean, const float* rstd,
+                          const float* addend, int64_t addend_ld, float* dx, int64_t dx_ld, float* dgamma, float* dbeta, int64_t M, int32_t C,
+                          void* ws, int64_t ws_bytes, void* stream);
+/* Softmax attention per (image, head): o = softmax(scale * q k^T) v with T >= 1 tokens, any head count and head width d % 4 == 0, d <= 128.
+ * q, k, v: head h at channels [h d, (h + 1) d) of three views that share their strides (the slices [0, D), [D, 2D), [2D, 3D) of the to_qkv
+ * output [B, T, 1, 3D], D = heads * d); o: the same head order in a [B, T, 1, D] map.  The row maximum is subtracted before exp; lse
+ * [B][heads][T] = log sum_j exp(scale * s_ij) is saved.  The T x T probabilities are never stored in HBM.
+ *   _bwd  recomputes p from q, k and lse; dq / dk / dv are written (not accumulated) through three views that share their strides - the
+ *         slices of one [B, T, 1, 3D] gradient.  ws (sgx_attn_bwd_workspace bytes) holds Delta = sum_c dO * O per row.
+ * sgx_attn_tile_rows(0 / 1): own rows per workgroup / streamed rows staged between two barriers (what the tests place T around).          */
+int32_t sgx_attn_tile_rows(int32_t which);
+int32_t sgx_attn_fwd(int32_t B, int32_t heads, int32_t T, int32_t d, const float* q, const float* k, const float* v, int64_t ld_pix, int64_t ld_img,
+                     float scale, float* o, int64_t o_ld_pix, int64_t o_ld_img, float* lse, void* stream);
+int64_t sgx_attn_bwd_workspace(int32_t B, int32_t heads, int32_t T);
+int32_t sgx_attn_bwd(int32_t B, int32_t heads, int32_t T, int32_t d, const float* q, const float* k, const float* v, int64_t ld_pix, int64_t ld_img,
+                     const float* o, const float* dout, int64_t o_ld_pix, int64_t o_ld_img, const float* lse, float scale, float* dq, float* dk,
+                     float* dv, int64_t g_ld_pix, int64_t g_ld_img, void* ws, int64_t ws_bytes, void* stream);
+/* [B, gh * ph, gw * pw, C] -> [B, gh * gw, 1, ph * pw * C]: patch (gy, gx) becomes one row in (py, px, c) order, the order of a
+ * [D, C, ph, pw] filter stored OHWI - the patch embedding is then a 1x1 convolution.                                                        */
+int32_t sgx_patch_rows(int32_t B, int32_t gh, int32_t gw, int32_t ph, int32_t pw, int32_t C, const float* x, int64_t x_ld_pix, int64_t x_ld_img,
+                       float* y, int64_t y_ld_pix, int64_t y_ld_img, void* stream);
+/* x[b][0] = cls + pos[0], x[b][1 + i] = patch[b][i] + pos[1 + i] (patch [B, T - 1, 1, D]; cls [D], pos [T][D] contiguous).
+ * _bwd: dpos[t] += sum_b dx[b][t] (ascending b, fp64, one rounding), dcls += the same row-0 sum.                                            */
+int32_t sgx_token_assemble_fwd(int32_t B, int32_t T, int32_t D, const float* patch, int64_t p_ld_pix, int64_t p_ld_img, const float* cls,
+                               const float* pos, float* x, int64_t x_ld_pix, int64_t x_ld_img, void* stream);
+int32_t sgx_token_assemble_bwd(int32_t B, int32_t T, int32_t D, const float* dx, int64_t x_ld_pix, int64_t x_ld_img, float* dcls, float* dpos,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Detection head decode, PPYoloELoss (assigner + VFL/GIoU/DFL with hand-written backward), NMS.
  * ------------------------------------------------------------------------------------------- */
 /* dfl_heads.py:207-235 + bbox_utils.py:9-29: boxes[B,L,4] = dist2bbox(softmax(distri)·[0..R]) * stride,

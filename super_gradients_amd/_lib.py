@@ -206,6 +206,19 @@ PROTOTYPES = {
     "sgx_bn_act_gate_bwd_gate": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _P, _i64, _P]),
     "sgx_bn_act_gate_bwd_data": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _P, _i64, _P, _P, _i32, _i32, _i32, _P]),
     "sgx_bn_gate_add_fwd": (_i32, [_P, _i64, _P, _P, _P, _i32, _P, _i64, _P, _i64, _i32, _i32, _i32, _P]),
+    "sgx_gelu_fwd": (_i32, [_P, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_gelu_bwd": (_i32, [_P, _i64, _P, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_layernorm_fwd": (_i32, [_P, _i64, _P, _P, _f, _P, _i64, _P, _P, _i64, _i32, _P]),
+    "sgx_layernorm_bwd_block_rows": (_i32, []),
+    "sgx_layernorm_bwd_workspace": (_i64, [_i64, _i32]),
+    "sgx_layernorm_bwd": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _P, _i64, _P, _P, _i64, _i32, _P, _i64, _P]),
+    "sgx_attn_tile_rows": (_i32, [_i32]),
+    "sgx_attn_fwd": (_i32, [_i32] * 4 + [_P, _P, _P, _i64, _i64, _f, _P, _i64, _i64, _P, _P]),
+    "sgx_attn_bwd_workspace": (_i64, [_i32] * 3),
+    "sgx_attn_bwd": (_i32, [_i32] * 4 + [_P, _P, _P, _i64, _i64, _P, _P, _i64, _i64, _P, _f, _P, _P, _P, _i64, _i64, _P, _i64, _P]),
+    "sgx_patch_rows": (_i32, [_i32] * 6 + [_P, _i64, _i64, _P, _i64, _i64, _P]),
+    "sgx_token_assemble_fwd": (_i32, [_i32] * 3 + [_P, _i64, _i64, _P, _P, _P, _i64, _i64, _P]),
+    "sgx_token_assemble_bwd": (_i32, [_i32] * 3 + [_P, _i64, _i64, _P, _P, _P]),
     "sgx_dropout_fwd": (_i32, [_P, _i64, _P, _i64, _i64, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _P]),
     "sgx_tri_affine_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _f, _P, _P, _i64, _i64, _i32, _i32, _P, _i32, _P]),
     "sgx_tri_affine_act_bwd_reduce": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _i64, _i32, _i32,

@@ -576,3 +576,7 @@ extern "C" int32_t sgx_bn_gate_add_fwd(const float* x, int64_t x_ld, const float
     BnGateAddFwdF f{x, x_ld, scale, shift, pre, gate, sgx_make_fastdiv(HW), C, r, r_ld, y, y_ld};
     return run_sweep<BnGateAddFwdF, 0, 2>(f, (long)N * HW, C, nullptr, stream, "bn_gate_add_fwd");
 }
+
+// The Vision Transformer's kernels (attention, LayerNorm, GELU, patch rows, token assembly) build in this translation unit: they share the
+// sweep skeleton and the float4 / alignment conventions above.
+#include "vit.h"

@@ -1209,6 +1209,124 @@ def fill(t, v=0.0):
     check(lib().sgx_fill(ptr(t), t.numel(), float(v), stream()), "sgx_fill")
 
 
+# --------------------------------------------------------------------------------------------- Vision Transformer glue (csrc/vit.h)
+def token_rows(t: torch.Tensor) -> Tuple[int, int]:
+    """(M, ld) like rows(); a map of one pixel per image (the class-token rows [B, 1, 1, D] of a [B, T, 1, D] stream) has its image stride
+    as the row stride."""
+    n, h, w, _ = t.shape
+    if h * w == 1:
+        return n, nhwc_strides(t)[1]
+    return rows(t)
+
+
+def gelu_fwd(x, out=None):
+    """y = x * Phi(x), the erf form."""
+    M, ld = token_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(lib().sgx_gelu_fwd(ptr(x), ld, ptr(out), token_rows(out)[1], M, x.shape[3], stream()), "sgx_gelu_fwd")
+    return out
+
+
+def gelu_bwd(dy, x, out=None):
+    """dx = dy * gelu'(x) from the stored pre-activation x; out may be dy."""
+    M, ld = token_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(lib().sgx_gelu_bwd(ptr(dy), token_rows(dy)[1], ptr(x), ld, ptr(out), token_rows(out)[1], M, x.shape[3], stream()), "sgx_gelu_bwd")
+    return out
+
+
+def layernorm_fwd(x, gamma, beta, eps, out=None, want_stats=True):
+    """LayerNorm over the channels of every pixel -> y, or (y, mean [M], rstd [M]) with want_stats."""
+    M, ld = token_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    mean = torch.empty(M, device=x.device, dtype=torch.float32) if want_stats else None
+    rstd = torch.empty(M, device=x.device, dtype=torch.float32) if want_stats else None
+    check(lib().sgx_layernorm_fwd(ptr(x), ld, ptr(gamma), ptr(beta), float(eps), ptr(out), token_rows(out)[1], ptr(mean), ptr(rstd), M, x.shape[3], stream()),
+          "sgx_layernorm_fwd")
+    return (out, mean, rstd) if want_stats else out
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma=None, dbeta=None, addend=None, out=None):
+    """dx [+ addend]; dgamma / dbeta (views of the gradient arena) are added to in place."""
+    M, ld = token_rows(x)
+    C = x.shape[3]
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    ws = WORKSPACE.get(lib().sgx_layernorm_bwd_workspace(M, C), x.device) if dgamma is not None else None
+    check(lib().sgx_layernorm_bwd(ptr(dy), token_rows(dy)[1], ptr(x), ld, ptr(gamma), ptr(mean), ptr(rstd), ptr(addend),
+                                  token_rows(addend)[1] if addend is not None else 0, ptr(out), token_rows(out)[1], ptr(dgamma), ptr(dbeta), M, C, ptr(ws),
+                                  ws.numel() if ws is not None else 0, stream()), "sgx_layernorm_bwd")
+    return out
+
+
+def _attn_views(q, k, v, heads):
+    b, t, one, D = q.shape
+    if one != 1 or D % heads or k.shape != q.shape or v.shape != q.shape:
+        raise _lib.SgxError(f"attention: q, k, v must be [B, T, 1, heads * d] views of one shape, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)} ({heads} heads)")
+    ld = nhwc_strides(q)
+    if nhwc_strides(k) != ld or nhwc_strides(v) != ld:
+        raise _lib.SgxError("attention: q, k, v must share their strides (slices of one to_qkv output)")
+    return b, t, D // heads, ld
+
+
+def attn_fwd(q, k, v, heads, scale, out=None):
+    """softmax(scale * q k^T) v per (image, head) -> (o [B, T, 1, D], lse [B, heads, T])."""
+    b, t, d, (lp, li) = _attn_views(q, k, v, heads)
+    if out is None:
+        out = torch.empty(b, t, 1, heads * d, device=q.device, dtype=torch.float32)
+    lse = torch.empty(b, heads, t, device=q.device, dtype=torch.float32)
+    ol, oi = nhwc_strides(out)
+    check(lib().sgx_attn_fwd(b, heads, t, d, ptr(q), ptr(k), ptr(v), lp, li, float(scale), ptr(out), ol, oi, ptr(lse), stream()), "sgx_attn_fwd")
+    return out, lse
+
+
+def attn_bwd(q, k, v, o, do, lse, heads, scale, dq, dk, dv):
+    """dq, dk, dv (three views that share their strides: the slices of one [B, T, 1, 3D] gradient) from the recomputed probabilities."""
+    b, t, d, (lp, li) = _attn_views(q, k, v, heads)
+    gl = _attn_views(dq, dk, dv, heads)[3]
+    ol = nhwc_strides(o)
+    if nhwc_strides(do) != ol or o.shape != q.shape or do.shape != q.shape or dq.shape != q.shape:
+        raise _lib.SgxError("attention backward: o and dO must share shape and strides")
+    ws = WORKSPACE.get(lib().sgx_attn_bwd_workspace(b, heads, t), q.device)
+    check(lib().sgx_attn_bwd(b, heads, t, d, ptr(q), ptr(k), ptr(v), lp, li, ptr(o), ptr(do), ol[0], ol[1], ptr(lse), float(scale), ptr(dq), ptr(dk), ptr(dv),
+                             gl[0], gl[1], ptr(ws), ws.numel(), stream()), "sgx_attn_bwd")
+
+
+def patch_rows(x, ph, pw, out=None):
+    """NHWC [B, gh * ph, gw * pw, C] -> [B, gh * gw, 1, ph * pw * C] rows in (py, px, c) order."""
+    n, h, w, c = x.shape
+    if h % ph or w % pw:
+        raise _lib.SgxError(f"patch_rows: {h} x {w} is not a whole number of {ph} x {pw} patches")
+    gh, gw = h // ph, w // pw
+    if out is None:
+        out = torch.empty(n, gh * gw, 1, ph * pw * c, device=x.device, dtype=torch.float32)
+    xl, xi = nhwc_strides(x)
+    yl, yi = nhwc_strides(out)
+    check(lib().sgx_patch_rows(n, gh, gw, ph, pw, c, ptr(x), xl, xi, ptr(out), yl, yi, stream()), "sgx_patch_rows")
+    return out
+
+
+def token_assemble_fwd(patch, cls, pos, out=None):
+    """x[b, 0] = cls + pos[0], x[b, 1 + i] = patch[b, i] + pos[1 + i]; cls [D] and pos [T, D] contiguous."""
+    n, p, _, D = patch.shape
+    if out is None:
+        out = torch.empty(n, p + 1, 1, D, device=patch.device, dtype=torch.float32)
+    pl, pi = nhwc_strides(patch)
+    xl, xi = nhwc_strides(out)
+    check(lib().sgx_token_assemble_fwd(n, p + 1, D, ptr(patch), pl, pi, ptr(cls), ptr(pos), ptr(out), xl, xi, stream()), "sgx_token_assemble_fwd")
+    return out
+
+
+def token_assemble_bwd(dx, dcls, dpos):
+    """dpos[t] += sum_b dx[b, t], dcls += sum_b dx[b, 0] (in place, fixed image order)."""
+    n, t, _, D = dx.shape
+    xl, xi = nhwc_strides(dx)
+    check(lib().sgx_token_assemble_bwd(n, t, D, ptr(dx), xl, xi, ptr(dcls), ptr(dpos), stream()), "sgx_token_assemble_bwd")
+
+
 # --------------------------------------------------------------------------------------------- pooling
 def maxpool_fwd(x, k, stride, pad, out=None, want_argmax=True):
     n, h, w, c = x.shape

@@ -9,3 +9,4 @@ from .resnext import GroupedConvBlock, ResNeXt, ResNeXt50, ResNeXt101  # noqa: F
 from .efficientnet import (BlockArgs, BlockDecoder, CustomizedEfficientnet, EfficientNet, EfficientNetB0, EfficientNetB1, EfficientNetB2,  # noqa: F401
                            EfficientNetB3, EfficientNetB4, EfficientNetB5, EfficientNetB6, EfficientNetB7, EfficientNetB8, EfficientNetL2,
                            MBConvBlock, round_filters, round_repeats)
+from .vit import ViT, ViTBase, ViTHuge, ViTLarge  # noqa: F401
