@@ -662,11 +662,50 @@ int32_t sgx_attn_bwd(int32_t B, int32_t heads, int32_t T, int32_t d, const float
 int32_t sgx_patch_rows(int32_t B, int32_t gh, int32_t gw, int32_t ph, int32_t pw, int32_t C, const float* x, int64_t x_ld_pix, int64_t x_ld_img,
                        float* y, int64_t y_ld_pix, int64_t y_ld_img, void* stream);
 /* x[b][0] = cls + pos[0], x[b][1 + i] = patch[b][i] + pos[1 + i] (patch [B, T - 1, 1, D]; cls [D], pos [T][D] contiguous).
- * _bwd: dpos[t] += sum_b dx[b][t] (ascending b, fp64, one rounding), dcls += the same row-0 sum.                                            */
+ * _bwd: dpos[t] += sum_b dx[b][t] (ascending b, fp64, one rounding), dcls += the same row-0 sum.
+ * pos / dpos may be NULL (BEiT without an absolute position embedding): the rows move unchanged; the backward sums the class-token row only. */
 int32_t sgx_token_assemble_fwd(int32_t B, int32_t T, int32_t D, const float* patch, int64_t p_ld_pix, int64_t p_ld_img, const float* cls,
                                const float* pos, float* x, int64_t x_ld_pix, int64_t x_ld_img, void* stream);
 int32_t sgx_token_assemble_bwd(int32_t B, int32_t T, int32_t D, const float* dx, int64_t x_ld_pix, int64_t x_ld_img, float* dcls, float* dpos,
                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BEiT glue (classification_models/beit.py; csrc/vit.h): attention with a relative position bias, layer scale, the patch-token mean.
+ * ------------------------------------------------------------------------------------------- */
+/* sgx_attn_fwd / _bwd with s_ij = scale * q_i k_j + table[index(i, j)][h] over a gh x gw token grid behind one class token (T == gh gw + 1).
+ * table: N = (2 gh - 1)(2 gw - 1) + 3 rows of heads floats at a row stride tab_ld >= heads (the parameter's own [N][heads] layout).
+ * index(i, j) is computed in the kernels: N - 1 for i = j = 0, N - 3 for i = 0, N - 2 for j = 0, otherwise
+ * (y_i - y_j + gh - 1)(2 gw - 1) + (x_i - x_j + gw - 1) with (y, x) = divmod(token - 1, gw).  Head h's table column is staged in LDS once per
+ * workgroup: N <= sgx_attn_rpb_max_rows() (4096: grids up to 32 x 32), SGX_ERR_BAD_ARG beyond it.  lse includes the bias; with an all-zero
+ * table every output has the bits of the plain kernels.  Neither a [heads, T, T] bias nor ds ever reaches HBM.
+ *   _bwd  also ADDS dtable[r][h] = sum_b sum_{index(i, j) = r} ds_bhij onto a view of the table's layout (row stride dtab_ld): the dq pass
+ *         bins its ds tiles in LDS (thread-owned bins, ascending rows), leaves one partial row [N] per (image, row tile, head) in ws
+ *         (sgx_attn_rpb_bwd_workspace bytes: Delta, then the partial rows), and a finalize adds them in (image, tile) order in fp64 - no
+ *         floating-point atomics, the same inputs give the same bits.                                                                       */
+int32_t sgx_attn_rpb_max_rows(void);
+int32_t sgx_attn_rpb_fwd(int32_t B, int32_t heads, int32_t T, int32_t d, int32_t gh, int32_t gw, const float* q, const float* k, const float* v,
+                         int64_t ld_pix, int64_t ld_img, float scale, const float* table, int64_t tab_ld, float* o, int64_t o_ld_pix, int64_t o_ld_img,
+                         float* lse, void* stream);
+int64_t sgx_attn_rpb_bwd_workspace(int32_t B, int32_t heads, int32_t T, int32_t gh, int32_t gw);
+int32_t sgx_attn_rpb_bwd(int32_t B, int32_t heads, int32_t T, int32_t d, int32_t gh, int32_t gw, const float* q, const float* k, const float* v,
+                         int64_t ld_pix, int64_t ld_img, const float* o, const float* dout, int64_t o_ld_pix, int64_t o_ld_img, const float* lse,
+                         float scale, const float* table, int64_t tab_ld, float* dq, float* dk, float* dv, int64_t g_ld_pix, int64_t g_ld_img,
+                         float* dtable, int64_t dtab_ld, void* ws, int64_t ws_bytes, void* stream);
+/* Layer scale with an optional per-image multiplier (stochastic depth): y = x + m_b * (gamma * t) over M rows of C channels, row r in image
+ * r / rows_per_img; gamma [C] or NULL (ones), m [M / rows_per_img] or NULL (ones); y may alias x.
+ *   _bwd  dt = m_b * gamma * dy (dt may alias dy; the skip's gradient is dy itself); dgamma (NULL: none; needs gamma and t) is ADDED to in
+ *         place: [ceil(M / sgx_layerscale_block_rows())][C] partial rows of m_b * dy * t in ws (sgx_layerscale_bwd_workspace bytes), then a
+ *         finalize that adds them in block order in fp64.                                                                                   */
+int32_t sgx_layerscale_fwd(const float* x, int64_t x_ld, const float* t, int64_t t_ld, const float* gamma, const float* m, int64_t rows_per_img,
+                           float* y, int64_t y_ld, int64_t M, int32_t C, void* stream);
+int32_t sgx_layerscale_block_rows(void);
+int64_t sgx_layerscale_bwd_workspace(int64_t M, int32_t C);
+int32_t sgx_layerscale_bwd(const float* dy, int64_t dy_ld, const float* t, int64_t t_ld, const float* gamma, const float* m, int64_t rows_per_img,
+                           float* dt, int64_t dt_ld, float* dgamma, int64_t M, int32_t C, void* ws, int64_t ws_bytes, void* stream);
+/* y[b] = the mean of rows 1 .. T - 1 of x[b] ([B, T, 1, D] -> rows of D floats at stride y_ld), added in ascending row order.
+ * _bwd writes the whole [B, T, 1, D] gradient: row 0 zero, every other row dy[b] / (T - 1).                                                 */
+int32_t sgx_token_mean_fwd(int32_t B, int32_t T, int32_t D, const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y, int64_t y_ld, void* stream);
+int32_t sgx_token_mean_bwd(int32_t B, int32_t T, int32_t D, const float* dy, int64_t dy_ld, float* dx, int64_t x_ld_pix, int64_t x_ld_img, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detection head decode, PPYoloELoss (assigner + VFL/GIoU/DFL with hand-written backward), NMS.

@@ -219,6 +219,16 @@ PROTOTYPES = {
     "sgx_patch_rows": (_i32, [_i32] * 6 + [_P, _i64, _i64, _P, _i64, _i64, _P]),
     "sgx_token_assemble_fwd": (_i32, [_i32] * 3 + [_P, _i64, _i64, _P, _P, _P, _i64, _i64, _P]),
     "sgx_token_assemble_bwd": (_i32, [_i32] * 3 + [_P, _i64, _i64, _P, _P, _P]),
+    "sgx_attn_rpb_max_rows": (_i32, []),
+    "sgx_attn_rpb_fwd": (_i32, [_i32] * 6 + [_P, _P, _P, _i64, _i64, _f, _P, _i64, _P, _i64, _i64, _P, _P]),
+    "sgx_attn_rpb_bwd_workspace": (_i64, [_i32] * 5),
+    "sgx_attn_rpb_bwd": (_i32, [_i32] * 6 + [_P, _P, _P, _i64, _i64, _P, _P, _i64, _i64, _P, _f, _P, _i64, _P, _P, _P, _i64, _i64, _P, _i64, _P, _i64, _P]),
+    "sgx_layerscale_fwd": (_i32, [_P, _i64, _P, _i64, _P, _P, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_layerscale_block_rows": (_i32, []),
+    "sgx_layerscale_bwd_workspace": (_i64, [_i64, _i32]),
+    "sgx_layerscale_bwd": (_i32, [_P, _i64, _P, _i64, _P, _P, _i64, _P, _i64, _P, _i64, _i32, _P, _i64, _P]),
+    "sgx_token_mean_fwd": (_i32, [_i32] * 3 + [_P, _i64, _i64, _P, _i64, _P]),
+    "sgx_token_mean_bwd": (_i32, [_i32] * 3 + [_P, _i64, _P, _i64, _i64, _P]),
     "sgx_dropout_fwd": (_i32, [_P, _i64, _P, _i64, _i64, _i32, _f, ctypes.c_uint64, ctypes.c_uint64, _P]),
     "sgx_tri_affine_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _P, _P, _P, _i64, _f, _P, _P, _i64, _i64, _i32, _i32, _P, _i32, _P]),
     "sgx_tri_affine_act_bwd_reduce": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _i64, _i64, _i32, _i32,

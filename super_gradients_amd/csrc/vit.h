@@ -323,19 +323,52 @@ __device__ __forceinline__ void att_store(float* dst, long ld_pix, int t0, int T
     }
 }
 
-template <int NB>
+// Relative position bias (BEiT): s_ij = scale * q_i k_j + table[index(i, j)][h] over a gh x gw token grid behind one class token
+// (T = gh gw + 1).  index(i, j) is computed, never read: N - 1 for i = j = 0, N - 3 for i = 0, N - 2 for j = 0, else
+// (y_i - y_j + gh - 1) (2 gw - 1) + (x_i - x_j + gw - 1) = lin(i) - lin(j) + c0 with lin(t) = y_t (2 gw - 1) + x_t, (y, x) = divmod(t - 1, gw),
+// N = (2 gh - 1)(2 gw - 1) + 3.  Head h's column of the table is staged in LDS once per workgroup: N <= ATT_RPB_MAXN floats.
+#define ATT_RPB_MAXN 4096
+#define ATT_RPB_BINS (ATT_RPB_MAXN / ATT_THREADS)  // bins of the table gradient a thread of the dq pass owns: 4 up to N = 1024 (16 x 16 grids), else 16
+#define ATT_T2(a, b) a, b
+struct AttRpb {
+    const float* table;  // [N][ld] (+ h: head h's column)
+    long ld;
+    int gh, gw, N, c0;  // c0 = (gh - 1) (2 gw - 1) + gw - 1
+};
+// lin(t) of a token clamped into 1 .. T - 1 (rows and columns past T are masked by their callers; their index must stay inside the table)
+__device__ __forceinline__ int rpb_lin(int t, int T, int gw) {
+    t = t < T ? t : T - 1;
+    t = t > 0 ? t - 1 : 0;
+    const int y = t / gw;
+    return y * (2 * gw - 1) + (t - y * gw);
+}
+__device__ __forceinline__ int rpb_index(int i, int j, int li, int lj, const AttRpb& rp) {
+    return i == 0 ? (j == 0 ? rp.N - 1 : rp.N - 3) : (j == 0 ? rp.N - 2 : li - lj + rp.c0);
+}
+__device__ __forceinline__ void rpb_stage(float* Ts, const AttRpb& rp, int h) {
+    for (int i = threadIdx.x; i < rp.N; i += ATT_THREADS) Ts[i] = rp.table[(long)i * rp.ld + h];
+}
+
+template <int NB, bool BIAS>
 __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(int T, int d, int heads, const float* q, const float* k, const float* v, long ld_pix,
-                                                               long ld_img, float scale, float* o, long o_ld_pix, long o_ld_img, float* lse) {
+                                                               long ld_img, float scale, float* o, long o_ld_pix, long o_ld_img, float* lse, AttRpb rp) {
     SGX_DYN_SMEM(float, sm);
     const int dp = ((d + 15) & ~15) + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* Ks = sm;
     float* Vs = Ks + ATT_TK * dp;
     float* Ps = Vs + ATT_TK * dp + wave * 256;
+    const float* Ts = Vs + ATT_TK * dp + 4 * 256;
     const int h = blockIdx.y, b = blockIdx.z, q0 = blockIdx.x * ATT_TQ + 16 * wave;
     const long base = (long)b * ld_img + (long)h * d;
     float qf[4 * NB];
     att_load_frag<NB>(qf, q + base, ld_pix, q0, T, d, lane);
+    int li[4];  // lin() of the lane's four accumulator rows
+    if constexpr (BIAS) {
+        rpb_stage(Vs + ATT_TK * dp + 4 * 256, rp, h);  // (visible after the loop's first barrier)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) li[r] = rpb_lin(q0 + (lane >> 4) * 4 + r, T, rp.gw);
+    }
     float m[4], l[4];
     sgx_f32x4 acc[NB];
 #pragma unroll
@@ -352,10 +385,15 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(int T, int d, int
             if (kk >= T) break;  // the same for every thread of the workgroup
             const sgx_f32x4 s = att_nt<NB>(qf, Ks + 16 * u * dp, dp, d, lane);
             const bool valid = kk + (lane & 15) < T;
-            float p[4], alpha[4];
+            float p[4], alpha[4], bias[4];
+            if constexpr (BIAS) {
+                const int j = kk + (lane & 15), lj = rpb_lin(j, T, rp.gw);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) bias[r] = Ts[rpb_index(q0 + (lane >> 4) * 4 + r, valid ? j : T - 1, li[r], lj, rp)];
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float sv = valid ? scale * s[r] : ATT_NEG_INF;
+                const float sv = valid ? (BIAS ? fmaf(scale, s[r], bias[r]) : scale * s[r]) : ATT_NEG_INF;
                 const float mn = fmaxf(m[r], att_max16(sv));  // finite: key kk is valid
                 p[r] = expf(sv - mn);                          // masked keys: exp(-inf) = 0
                 alpha[r] = expf(m[r] - mn);
@@ -382,17 +420,60 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(int T, int d, int
     att_store<NB>(o + (long)b * o_ld_img + (long)h * d, o_ld_pix, q0, T, d, acc, inv, lane);
 }
 
-template <int NB>
+// The table gradient inside the dq pass: dtable[r][h] = sum_b sum_{index(i, j) = r} ds_bhij.  The workgroup parks the ds of its 64 rows x the
+// staged ATT_TK columns in LDS (Dp, [64][ATT_TK + 1]); thread t owns bins t, t + 256, ... and adds, per staged tile, the elements of its
+// bins in ascending row order into registers - a regular bin (dy, dx) meets row i at column j = i - (dy gw + dx) wherever x_i - dx stays
+// inside the grid, so a bin walks only the rows whose column is staged: 64 x ATT_TK additions per tile over the whole workgroup.  One
+// partial row [N] per (image, row tile, head) goes to the workspace; attn_rpb_dtable_finalize_kernel adds them in (image, tile) order.
+template <int BINS>
+__device__ __forceinline__ void rpb_gather(float (&bin)[BINS], const float* Dp, int I0, int k0, int T, const AttRpb& rp) {
+    const int W = 2 * rp.gw - 1, gw = rp.gw;
+    const int jlo = k0 > 1 ? k0 : 1, jhi = k0 + ATT_TK < T ? k0 + ATT_TK : T;  // the staged patch-token columns
+    const int ilo = I0 > 1 ? I0 : 1, ihi = I0 + ATT_TQ < T ? I0 + ATT_TQ : T;  // the workgroup's patch-token rows
+#pragma unroll
+    for (int m = 0; m < BINS; ++m) {
+        const int r = (int)threadIdx.x + ATT_THREADS * m;
+        if (r >= rp.N) continue;
+        float a = bin[m];
+        if (r < rp.N - 3) {
+            const int by = r / W;
+            const int dx = r - by * W - (gw - 1), off = (by - (rp.gh - 1)) * gw + dx;  // i - j of the bin's pairs
+            int i = ilo > jlo + off ? ilo : jlo + off;
+            const int iend = ihi < jhi + off ? ihi : jhi + off;
+            if (i < iend) {
+                int xi = (i - 1) % gw;
+                const float* p = Dp + (i - I0) * (ATT_TK + 1) + (i - off - k0);  // (the next row's element: one row down, one column on)
+                for (; i < iend; ++i, p += ATT_TK + 2) {
+                    if ((unsigned)(xi - dx) < (unsigned)gw) a += *p;
+                    if (++xi == gw) xi = 0;
+                }
+            }
+        } else if (r == rp.N - 3) {  // the class token's row
+            if (I0 == 0)
+                for (int j = jlo; j < jhi; ++j) a += Dp[j - k0];
+        } else if (r == rp.N - 2) {  // the class token's column
+            if (k0 == 0)
+                for (int i = ilo; i < ihi; ++i) a += Dp[(i - I0) * (ATT_TK + 1)];
+        } else if (I0 == 0 && k0 == 0) {
+            a += Dp[0];
+        }
+        bin[m] = a;
+    }
+}
+
+template <int NB, bool BIAS, int BINS>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(int T, int d, int heads, const float* q, const float* k, const float* v, long ld_pix,
                                                                   long ld_img, const float* o, const float* dout, long o_ld_pix, long o_ld_img,
                                                                   const float* lse, float scale, float* dq, long g_ld_pix, long g_ld_img,
-                                                                  float* delta) {
+                                                                  float* delta, AttRpb rp, float* dt_part) {
     SGX_DYN_SMEM(float, sm);
     const int dp = ((d + 15) & ~15) + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* Ks = sm;
     float* Vs = Ks + ATT_TK * dp;
     float* Ss = Vs + ATT_TK * dp + wave * 256;
+    float* Ts = Vs + ATT_TK * dp + 4 * 256;  // BIAS: head h's table column [N], then Dp [ATT_TQ][ATT_TK + 1]
+    float* Dp = Ts + rp.N;
     const int h = blockIdx.y, b = blockIdx.z, q0 = blockIdx.x * ATT_TQ + 16 * wave;
     const long base = (long)b * ld_img + (long)h * d, obase = (long)b * o_ld_img + (long)h * d;
     const long sbase = ((long)b * heads + h) * T;
@@ -415,6 +496,15 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(int T, int d, 
         L[r] = t < T ? lse[sbase + t] : 0.f;
         if (t < T && (lane & 15) == 0) delta[sbase + t] = dl[r];
     }
+    int li[4];
+    float bin[BINS];
+    if constexpr (BIAS) {
+        rpb_stage(Ts, rp, h);  // (visible after the loop's first barrier)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) li[r] = rpb_lin(q0 + (lane >> 4) * 4 + r, T, rp.gw);
+#pragma unroll
+        for (int m = 0; m < BINS; ++m) bin[m] = 0.f;
+    }
     sgx_f32x4 acc[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) acc[nb] = sgx_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -429,23 +519,76 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(int T, int d, 
             const sgx_f32x4 s = att_nt<NB>(qf, Ks + 16 * u * dp, dp, d, lane), dpv = att_nt<NB>(df, Vs + 16 * u * dp, dp, d, lane);
             const bool valid = kk + (lane & 15) < T;
             float ds[4];
+            if constexpr (BIAS) {
+                // p = exp(scale s + b - lse) written as scale s - (lse - b): with b = 0 the expression the plain kernel evaluates, bit for bit
+                const int j = kk + (lane & 15), lj = rpb_lin(j, T, rp.gw);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ds[r] = valid ? expf(scale * s[r] - L[r]) * (dpv[r] - dl[r]) : 0.f;
+                for (int r = 0; r < 4; ++r) {
+                    const float bias = Ts[rpb_index(q0 + (lane >> 4) * 4 + r, valid ? j : T - 1, li[r], lj, rp)];
+                    ds[r] = valid ? expf(scale * s[r] - (L[r] - bias)) * (dpv[r] - dl[r]) : 0.f;
+                    Dp[(16 * wave + (lane >> 4) * 4 + r) * (ATT_TK + 1) + 16 * u + (lane & 15)] = ds[r];
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ds[r] = valid ? expf(scale * s[r] - L[r]) * (dpv[r] - dl[r]) : 0.f;
+            }
             sgx_wave_lds_sync();
             att_put_tile(Ss, ds, lane);
             sgx_wave_lds_sync();
             att_nn<NB>(acc, Ss, Ks + 16 * u * dp, dp, d, lane);
         }
+        if constexpr (BIAS) {
+            __syncthreads();  // the four waves' ds rows of this tile are parked
+            rpb_gather<BINS>(bin, Dp, blockIdx.x * ATT_TQ, k0, T, rp);
+        }
     }
     const float mul[4] = {scale, scale, scale, scale};
     att_store<NB>(dq + (long)b * g_ld_img + (long)h * d, g_ld_pix, q0, T, d, acc, mul, lane);
+    if constexpr (BIAS) {
+        float* row = dt_part + (((long)b * gridDim.x + blockIdx.x) * heads + h) * rp.N;
+#pragma unroll
+        for (int m = 0; m < BINS; ++m) {
+            const int r = (int)threadIdx.x + ATT_THREADS * m;
+            if (r < rp.N) row[r] = bin[m];
+        }
+    }
 }
 
-template <int NB>
+// dtable[r][h] += the partial rows of bin (r, h), one rounding onto the arena view.  A workgroup owns 16 bins of one head; 16 threads per bin
+// each add a contiguous sixteenth of the (image, row tile) sequence in ascending order in fp64, and the bin's first thread adds the sixteen
+// sub-sums in ascending order: a fixed order that depends on the shape alone (36 workgroups of one serial chain each took as long as a
+// fifth of the attention backward at batch 64).
+#define RPB_FIN_BINS 16
+#define RPB_FIN_CHUNKS 16
+__global__ __launch_bounds__(RPB_FIN_BINS * RPB_FIN_CHUNKS) void attn_rpb_dtable_finalize_kernel(int nparts, int heads, int N, const float* __restrict__ parts,
+                                                                                                 float* dtable, long ld) {
+    __shared__ double sub[RPB_FIN_CHUNKS][RPB_FIN_BINS];
+    const int rb = threadIdx.x % RPB_FIN_BINS, c = threadIdx.x / RPB_FIN_BINS;
+    const int r = blockIdx.x * RPB_FIN_BINS + rb, h = blockIdx.y;
+    const int per = (nparts + RPB_FIN_CHUNKS - 1) / RPB_FIN_CHUNKS;
+    const int i0 = c * per, i1 = i0 + per < nparts ? i0 + per : nparts;
+    double a = 0.0;
+    if (r < N) {
+        const float* p = parts + (long)h * N + r;
+        const long step = (long)heads * N;
+#pragma unroll 4
+        for (int i = i0; i < i1; ++i) a += (double)p[i * step];
+    }
+    sub[c][rb] = a;
+    __syncthreads();
+    if (c == 0 && r < N) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < RPB_FIN_CHUNKS; ++k) t += sub[k][rb];
+        dtable[(long)r * ld + h] += (float)t;
+    }
+}
+
+template <int NB, bool BIAS>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkv_kernel(int T, int d, int heads, const float* q, const float* k, const float* v, long ld_pix,
                                                                    long ld_img, const float* dout, long o_ld_pix, long o_ld_img, const float* lse,
                                                                    const float* delta, float scale, float* dk, float* dv, long g_ld_pix,
-                                                                   long g_ld_img) {
+                                                                   long g_ld_img, AttRpb rp) {
     SGX_DYN_SMEM(float, sm);
     const int dp = ((d + 15) & ~15) + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -453,12 +596,19 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkv_kernel(int T, int d,
     float* Ds = Qs + ATT_TK * dp;
     float* Pt = Ds + ATT_TK * dp + wave * 512;
     float* St = Pt + 256;
+    float* Ts = Ds + ATT_TK * dp + 4 * 512;
     const int h = blockIdx.y, b = blockIdx.z, j0 = blockIdx.x * ATT_TQ + 16 * wave;  // the wave's own key rows
     const long base = (long)b * ld_img + (long)h * d, obase = (long)b * o_ld_img + (long)h * d;
     const long sbase = ((long)b * heads + h) * T;
     float kf[4 * NB], vf[4 * NB];
     att_load_frag<NB>(kf, k + base, ld_pix, j0, T, d, lane);
     att_load_frag<NB>(vf, v + base, ld_pix, j0, T, d, lane);
+    int lj[4];  // lin() of the lane's four accumulator rows (keys)
+    if constexpr (BIAS) {
+        rpb_stage(Ts, rp, h);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lj[r] = rpb_lin(j0 + (lane >> 4) * 4 + r, T, rp.gw);
+    }
     sgx_f32x4 ak[NB], av[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) ak[nb] = av[nb] = sgx_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -476,10 +626,21 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkv_kernel(int T, int d,
             const bool valid = i < T;
             const float Li = valid ? lse[sbase + i] : 0.f, Di = valid ? delta[sbase + i] : 0.f;
             float p[4], ds[4];
+            if constexpr (BIAS) {
+                const int li = rpb_lin(i, T, rp.gw);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                p[r] = valid ? expf(scale * s[r] - Li) : 0.f;
-                ds[r] = p[r] * (dpv[r] - Di);
+                for (int r = 0; r < 4; ++r) {
+                    const int j = j0 + (lane >> 4) * 4 + r;
+                    const float bias = Ts[rpb_index(valid ? i : T - 1, j < T ? j : T - 1, li, lj[r], rp)];
+                    p[r] = valid ? expf(scale * s[r] - (Li - bias)) : 0.f;
+                    ds[r] = p[r] * (dpv[r] - Di);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    p[r] = valid ? expf(scale * s[r] - Li) : 0.f;
+                    ds[r] = p[r] * (dpv[r] - Di);
+                }
             }
             sgx_wave_lds_sync();
             att_put_tile(Pt, p, lane);
@@ -497,12 +658,12 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkv_kernel(int T, int d,
 #define ATT_CHECK_DIMS(what)                                                                                                                  \
     SGX_CHECK_ARG(B > 0 && B <= 65535 && heads > 0 && heads <= 65535 && T > 0 && d >= 4 && d % 4 == 0 && d <= ATT_MAXD,                        \
                   "%s: need 1 <= B, heads <= 65535, T >= 1, d %% 4 == 0 and 4 <= d <= %d (B=%d heads=%d T=%d d=%d)", what, ATT_MAXD, B, heads, T, d)
-#define ATT_DISPATCH(kernel, patches, ...)                                                                                         \
+#define ATT_DISPATCH(kernel, BIAS, patches, extra, ...)                                                                            \
     do {                                                                                                                           \
-        const size_t smem__ = ((size_t)2 * ATT_TK * (((d + 15) & ~15) + 4) + 4 * 256 * (patches)) * sizeof(float);                 \
+        const size_t smem__ = ((size_t)2 * ATT_TK * (((d + 15) & ~15) + 4) + 4 * 256 * (patches) + (extra)) * sizeof(float);       \
         const dim3 grid__(sgx_cdiv(T, ATT_TQ), heads, B), block__(ATT_THREADS);                                                    \
-        if (d <= 64) SGX_LAUNCH((kernel<4>), grid__, block__, smem__, stream, __VA_ARGS__);                                        \
-        else SGX_LAUNCH((kernel<8>), grid__, block__, smem__, stream, __VA_ARGS__);                                                \
+        if (d <= 64) SGX_LAUNCH((kernel<4, BIAS>), grid__, block__, smem__, stream, __VA_ARGS__);                                  \
+        else SGX_LAUNCH((kernel<8, BIAS>), grid__, block__, smem__, stream, __VA_ARGS__);                                          \
     } while (0)
 
 extern "C" int32_t sgx_attn_tile_rows(int32_t which) { return which == 0 ? ATT_TQ : ATT_TK; }
@@ -512,7 +673,7 @@ extern "C" int32_t sgx_attn_fwd(int32_t B, int32_t heads, int32_t T, int32_t d, 
     ATT_CHECK_DIMS("attn_fwd");
     SGX_CHECK_ARG(VIT_LD4(ld_pix) && VIT_LD4(ld_img) && VIT_LD4(o_ld_pix) && VIT_LD4(o_ld_img) && VIT_ALIGNED(q) && VIT_ALIGNED(k) && VIT_ALIGNED(v) && VIT_ALIGNED(o),
                   "attn_fwd: strides and addresses must be multiples of 16 bytes");
-    ATT_DISPATCH(attn_fwd_kernel, 1, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, scale, o, (long)o_ld_pix, (long)o_ld_img, lse);
+    ATT_DISPATCH(attn_fwd_kernel, false, 1, 0, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, scale, o, (long)o_ld_pix, (long)o_ld_img, lse, AttRpb{});
     SGX_CHECK_LAUNCH("attn_fwd");
     return SGX_OK;
 }
@@ -527,12 +688,197 @@ extern "C" int32_t sgx_attn_bwd(int32_t B, int32_t heads, int32_t T, int32_t d, 
                       VIT_ALIGNED(ws),
                   "attn_bwd: strides and addresses must be multiples of 16 bytes");
     SGX_CHECK_ARG(ws && ws_bytes >= sgx_attn_bwd_workspace(B, heads, T), "attn_bwd: workspace too small");
-    ATT_DISPATCH(attn_bwd_dq_kernel, 1, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, o, dout, (long)o_ld_pix, (long)o_ld_img, lse, scale, dq,
-                 (long)g_ld_pix, (long)g_ld_img, (float*)ws);
+    ATT_DISPATCH(attn_bwd_dq_kernel, ATT_T2(false, 1), 1, 0, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, o, dout, (long)o_ld_pix, (long)o_ld_img, lse, scale, dq,
+                 (long)g_ld_pix, (long)g_ld_img, (float*)ws, AttRpb{}, (float*)nullptr);
     SGX_CHECK_LAUNCH("attn_bwd (dq)");
-    ATT_DISPATCH(attn_bwd_dkv_kernel, 2, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, dout, (long)o_ld_pix, (long)o_ld_img, lse, (const float*)ws,
-                 scale, dk, dv, (long)g_ld_pix, (long)g_ld_img);
+    ATT_DISPATCH(attn_bwd_dkv_kernel, false, 2, 0, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, dout, (long)o_ld_pix, (long)o_ld_img, lse, (const float*)ws,
+                 scale, dk, dv, (long)g_ld_pix, (long)g_ld_img, AttRpb{});
     SGX_CHECK_LAUNCH("attn_bwd (dk, dv)");
+    return SGX_OK;
+}
+
+// With a relative position bias: the same operands plus the token grid (T == gh gw + 1) and the table [N][heads] with its row stride
+// (tab_ld >= heads floats; the parameter's own layout has tab_ld == heads).  N = (2 gh - 1)(2 gw - 1) + 3 <= ATT_RPB_MAXN (4096: grids up to
+// 32 x 32; 16 KB of LDS beside the 38 KB of the staged rows at d = 128) - anything else is SGX_ERR_BAD_ARG with nothing launched.
+// The backward adds the table's gradient onto dtable (same layout, its own row stride).  Workspace: Delta [B heads T], then one partial row
+// [N] of the table gradient per (image, row tile, head).
+#define ATT_RPB_CHECK(what)                                                                                                                          \
+    SGX_CHECK_ARG(gh > 0 && gw > 0 && (long)gh * gw + 1 == T, "%s: T = %d is not gh * gw + 1 (grid %d x %d)", what, T, gh, gw);                      \
+    SGX_CHECK_ARG((2L * gh - 1) * (2L * gw - 1) + 3 <= ATT_RPB_MAXN, "%s: the %d x %d grid has %ld table rows, the LDS cap is %d", what, gh, gw,     \
+                  (2L * gh - 1) * (2L * gw - 1) + 3, ATT_RPB_MAXN);                                                                                  \
+    SGX_CHECK_ARG(table && tab_ld >= heads, "%s: the table's row stride (%ld) must be at least heads (%d)", what, (long)tab_ld, heads)
+static AttRpb att_rpb(const float* table, int64_t tab_ld, int gh, int gw) {
+    return AttRpb{table, (long)tab_ld, gh, gw, (2 * gh - 1) * (2 * gw - 1) + 3, (gh - 1) * (2 * gw - 1) + gw - 1};
+}
+extern "C" int32_t sgx_attn_rpb_max_rows(void) { return ATT_RPB_MAXN; }
+extern "C" int32_t sgx_attn_rpb_fwd(int32_t B, int32_t heads, int32_t T, int32_t d, int32_t gh, int32_t gw, const float* q, const float* k, const float* v,
+                                    int64_t ld_pix, int64_t ld_img, float scale, const float* table, int64_t tab_ld, float* o, int64_t o_ld_pix,
+                                    int64_t o_ld_img, float* lse, void* stream) {
+    SGX_CHECK_ARG(q && k && v && o && lse, "attn_rpb_fwd: null pointer");
+    ATT_CHECK_DIMS("attn_rpb_fwd");
+    ATT_RPB_CHECK("attn_rpb_fwd");
+    SGX_CHECK_ARG(VIT_LD4(ld_pix) && VIT_LD4(ld_img) && VIT_LD4(o_ld_pix) && VIT_LD4(o_ld_img) && VIT_ALIGNED(q) && VIT_ALIGNED(k) && VIT_ALIGNED(v) && VIT_ALIGNED(o),
+                  "attn_rpb_fwd: strides and addresses must be multiples of 16 bytes");
+    const AttRpb rp = att_rpb(table, tab_ld, gh, gw);
+    ATT_DISPATCH(attn_fwd_kernel, true, 1, rp.N, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, scale, o, (long)o_ld_pix, (long)o_ld_img, lse, rp);
+    SGX_CHECK_LAUNCH("attn_rpb_fwd");
+    return SGX_OK;
+}
+extern "C" int64_t sgx_attn_rpb_bwd_workspace(int32_t B, int32_t heads, int32_t T, int32_t gh, int32_t gw) {
+    const int64_t N = (2L * gh - 1) * (2L * gw - 1) + 3, tiles = (T + ATT_TQ - 1) / ATT_TQ;
+    return ((int64_t)B * heads * T + (int64_t)B * tiles * heads * N) * (int64_t)sizeof(float) + 256;
+}
+extern "C" int32_t sgx_attn_rpb_bwd(int32_t B, int32_t heads, int32_t T, int32_t d, int32_t gh, int32_t gw, const float* q, const float* k, const float* v,
+                                    int64_t ld_pix, int64_t ld_img, const float* o, const float* dout, int64_t o_ld_pix, int64_t o_ld_img, const float* lse,
+                                    float scale, const float* table, int64_t tab_ld, float* dq, float* dk, float* dv, int64_t g_ld_pix, int64_t g_ld_img,
+                                    float* dtable, int64_t dtab_ld, void* ws, int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(q && k && v && o && dout && lse && dq && dk && dv && dtable, "attn_rpb_bwd: null pointer");
+    ATT_CHECK_DIMS("attn_rpb_bwd");
+    ATT_RPB_CHECK("attn_rpb_bwd");
+    SGX_CHECK_ARG(dtab_ld >= heads, "attn_rpb_bwd: the table gradient's row stride (%ld) must be at least heads (%d)", (long)dtab_ld, heads);
+    SGX_CHECK_ARG(VIT_LD4(ld_pix) && VIT_LD4(ld_img) && VIT_LD4(o_ld_pix) && VIT_LD4(o_ld_img) && VIT_LD4(g_ld_pix) && VIT_LD4(g_ld_img) && VIT_ALIGNED(q) &&
+                      VIT_ALIGNED(k) && VIT_ALIGNED(v) && VIT_ALIGNED(o) && VIT_ALIGNED(dout) && VIT_ALIGNED(dq) && VIT_ALIGNED(dk) && VIT_ALIGNED(dv) &&
+                      VIT_ALIGNED(ws),
+                  "attn_rpb_bwd: strides and addresses must be multiples of 16 bytes");
+    SGX_CHECK_ARG(ws && ws_bytes >= sgx_attn_rpb_bwd_workspace(B, heads, T, gh, gw), "attn_rpb_bwd: workspace too small");
+    const AttRpb rp = att_rpb(table, tab_ld, gh, gw);
+    float* delta = (float*)ws;
+    float* parts = delta + (((long)B * heads * T + 3) & ~3L);
+    const int tiles = sgx_cdiv(T, ATT_TQ);
+    if (rp.N <= 4 * ATT_THREADS)
+        ATT_DISPATCH(attn_bwd_dq_kernel, ATT_T2(true, 4), 1, rp.N + ATT_TQ * (ATT_TK + 1), T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, o, dout,
+                     (long)o_ld_pix, (long)o_ld_img, lse, scale, dq, (long)g_ld_pix, (long)g_ld_img, delta, rp, parts);
+    else
+        ATT_DISPATCH(attn_bwd_dq_kernel, ATT_T2(true, ATT_RPB_BINS), 1, rp.N + ATT_TQ * (ATT_TK + 1), T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, o, dout,
+                     (long)o_ld_pix, (long)o_ld_img, lse, scale, dq, (long)g_ld_pix, (long)g_ld_img, delta, rp, parts);
+    SGX_CHECK_LAUNCH("attn_rpb_bwd (dq)");
+    ATT_DISPATCH(attn_bwd_dkv_kernel, true, 2, rp.N, T, d, heads, q, k, v, (long)ld_pix, (long)ld_img, dout, (long)o_ld_pix, (long)o_ld_img, lse,
+                 (const float*)delta, scale, dk, dv, (long)g_ld_pix, (long)g_ld_img, rp);
+    SGX_CHECK_LAUNCH("attn_rpb_bwd (dk, dv)");
+    SGX_LAUNCH(attn_rpb_dtable_finalize_kernel, dim3(sgx_cdiv(rp.N, RPB_FIN_BINS), heads), dim3(RPB_FIN_BINS * RPB_FIN_CHUNKS), 0, stream, B * tiles, heads, rp.N, (const float*)parts, dtable,
+               (long)dtab_ld);
+    SGX_CHECK_LAUNCH("attn_rpb_bwd (table gradient)");
+    return SGX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Layer scale with an optional per-image multiplier (BEiT's gamma_1 / gamma_2 and stochastic depth): y = x + m_b (gamma * t) over the rows of a
+// [B, T, 1, C] stream (row r belongs to image r / rows_per_img); gamma [C] or NULL (ones), m [B] or NULL (ones); y may alias x.  Backward:
+// dt = m_b gamma * dy (dt may alias dy; the skip's gradient is dy itself), dgamma += sum_rows m_b dy * t - partial rows of LS_BLOCK_ROWS rows
+// on the sweep skeleton, added in block order in fp64 onto the arena view.
+#define LS_BLOCK_ROWS 64
+struct LayerScaleFwdF {
+    const float* x; long x_ld; const float* t; long t_ld; const float* gamma; const float* m; long rows_per_img; float* y; long y_ld;
+    struct In { float4 a, b; float mul; };
+    __device__ In load(long r, int c) const { return In{sgx_ld4(x + r * x_ld + c), sgx_ld4(t + r * t_ld + c), m ? m[r / rows_per_img] : 1.f}; }
+    struct Cst { float4 g; };
+    __device__ Cst consts(int c) const { return Cst{gamma ? sgx_ld4(gamma + c) : make_float4(1.f, 1.f, 1.f, 1.f)}; }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&)[1]) const {
+        sgx_st4(y + r * y_ld + c, make_float4(in.a.x + in.mul * (k.g.x * in.b.x), in.a.y + in.mul * (k.g.y * in.b.y), in.a.z + in.mul * (k.g.z * in.b.z),
+                                              in.a.w + in.mul * (k.g.w * in.b.w)));
+    }
+};
+template <bool WITH_T>
+struct LayerScaleBwdF {
+    const float* dy; long dy_ld; const float* t; long t_ld; const float* gamma; const float* m; long rows_per_img; float* dt; long dt_ld;
+    struct In { float4 d, b; float mul; };
+    __device__ In load(long r, int c) const {
+        return In{sgx_ld4(dy + r * dy_ld + c), WITH_T ? sgx_ld4(t + r * t_ld + c) : make_float4(0.f, 0.f, 0.f, 0.f), m ? m[r / rows_per_img] : 1.f};
+    }
+    struct Cst { float4 g; };
+    __device__ Cst consts(int c) const { return Cst{gamma ? sgx_ld4(gamma + c) : make_float4(1.f, 1.f, 1.f, 1.f)}; }
+    __device__ void apply(long r, int c, const In& in, const Cst& k, float4 (&q)[1]) const {
+        const float4 md = make_float4(in.mul * in.d.x, in.mul * in.d.y, in.mul * in.d.z, in.mul * in.d.w);
+        if (WITH_T) { q[0].x += md.x * in.b.x; q[0].y += md.y * in.b.y; q[0].z += md.z * in.b.z; q[0].w += md.w * in.b.w; }
+        sgx_st4(dt + r * dt_ld + c, make_float4(md.x * k.g.x, md.y * k.g.y, md.z * k.g.z, md.w * k.g.w));
+    }
+};
+__global__ void layerscale_dgamma_finalize_kernel(int nblk, int C, const float* partials, float* dgamma) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0;
+    for (int k = 0; k < nblk; ++k) a += (double)partials[(long)k * C + c];
+    dgamma[c] += (float)a;
+}
+extern "C" int32_t sgx_layerscale_fwd(const float* x, int64_t x_ld, const float* t, int64_t t_ld, const float* gamma, const float* m, int64_t rows_per_img,
+                                      float* y, int64_t y_ld, int64_t M, int32_t C, void* stream) {
+    SGX_CHECK_ARG(x && t && y && rows_per_img > 0 && M % rows_per_img == 0, "layerscale_fwd: null pointer, or M is not a whole number of images");
+    SGX_CHECK_ARG(VIT_LD4(x_ld) && VIT_LD4(t_ld) && VIT_LD4(y_ld) && VIT_ALIGNED(x) && VIT_ALIGNED(t) && VIT_ALIGNED(y) && VIT_ALIGNED(gamma),
+                  "layerscale_fwd: strides and addresses must be multiples of 16 bytes");
+    LayerScaleFwdF f{x, (long)x_ld, t, (long)t_ld, gamma, m, (long)rows_per_img, y, (long)y_ld};
+    return run_sweep<LayerScaleFwdF, 0, 2>(f, M, C, nullptr, stream, "layerscale_fwd");
+}
+extern "C" int32_t sgx_layerscale_block_rows(void) { return LS_BLOCK_ROWS; }
+extern "C" int64_t sgx_layerscale_bwd_workspace(int64_t M, int32_t C) {
+    return ((M + LS_BLOCK_ROWS - 1) / LS_BLOCK_ROWS) * (int64_t)C * (int64_t)sizeof(float) + 256;
+}
+extern "C" int32_t sgx_layerscale_bwd(const float* dy, int64_t dy_ld, const float* t, int64_t t_ld, const float* gamma, const float* m, int64_t rows_per_img,
+                                      float* dt, int64_t dt_ld, float* dgamma, int64_t M, int32_t C, void* ws, int64_t ws_bytes, void* stream) {
+    SGX_CHECK_ARG(dy && dt && rows_per_img > 0 && M % rows_per_img == 0, "layerscale_bwd: null pointer, or M is not a whole number of images");
+    SGX_CHECK_ARG((dgamma == nullptr) || (gamma && t), "layerscale_bwd: dgamma needs gamma and the branch output t");
+    SGX_CHECK_ARG(VIT_LD4(dy_ld) && VIT_LD4(t_ld) && VIT_LD4(dt_ld) && VIT_ALIGNED(dy) && VIT_ALIGNED(t) && VIT_ALIGNED(dt) && VIT_ALIGNED(gamma) &&
+                      VIT_ALIGNED(dgamma) && VIT_ALIGNED(ws),
+                  "layerscale_bwd: strides and addresses must be multiples of 16 bytes");
+    if (!dgamma) {
+        LayerScaleBwdF<false> f{dy, (long)dy_ld, nullptr, 0, gamma, m, (long)rows_per_img, dt, (long)dt_ld};
+        return run_sweep<LayerScaleBwdF<false>, 0, 2>(f, M, C, nullptr, stream, "layerscale_bwd");
+    }
+    SGX_CHECK_ARG(ws && ws_bytes >= sgx_layerscale_bwd_workspace(M, C), "layerscale_bwd: workspace too small");
+    const int nblk = (int)((M + LS_BLOCK_ROWS - 1) / LS_BLOCK_ROWS);
+    LayerScaleBwdF<true> f{dy, (long)dy_ld, t, (long)t_ld, gamma, m, (long)rows_per_img, dt, (long)dt_ld};
+    const int32_t rc = run_sweep<LayerScaleBwdF<true>, 1, 2>(f, M, C, (float*)ws, stream, "layerscale_bwd", nblk);
+    if (rc != SGX_OK) return rc;
+    SGX_LAUNCH(layerscale_dgamma_finalize_kernel, dim3(sgx_cdiv(C, 256)), dim3(256), 0, stream, nblk, C, (const float*)ws, dgamma);
+    SGX_CHECK_LAUNCH("layerscale_bwd (finalize)");
+    return SGX_OK;
+}
+
+// Mean over the patch tokens (BEiT's global_pool = "avg"): y[b] = mean of rows 1 .. T - 1 of x[b] in ascending row order.  Backward: the whole
+// [B, T, 1, D] gradient - row 0 zero, every other row dy[b] / (T - 1).
+__global__ __launch_bounds__(256) void token_mean_fwd_kernel(int B, int T, int D4, const float* x, long x_ld_pix, long x_ld_img, float* y, long y_ld) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * D4) return;
+    const int c = (i % D4) * 4, b = i / D4;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int t = 1; t < T; ++t) {
+        const float4 a = sgx_ld4(x + (long)b * x_ld_img + (long)t * x_ld_pix + c);
+        s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
+    }
+    const float inv = 1.f / (float)(T - 1);
+    sgx_st4(y + (long)b * y_ld + c, make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv));
+}
+__global__ __launch_bounds__(256) void token_mean_bwd_kernel(int B, int T, int D4, const float* dy, long dy_ld, float* dx, long x_ld_pix, long x_ld_img) {
+    const long n = (long)B * T * D4;
+    const float inv = 1.f / (float)(T - 1);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % D4) * 4;
+        const long r = i / D4;
+        const int t = (int)(r % T);
+        const long b = r / T;
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t > 0) {
+            const float4 a = sgx_ld4(dy + b * dy_ld + c);
+            g = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+        }
+        sgx_st4(dx + b * x_ld_img + (long)t * x_ld_pix + c, g);
+    }
+}
+extern "C" int32_t sgx_token_mean_fwd(int32_t B, int32_t T, int32_t D, const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y, int64_t y_ld, void* stream) {
+    SGX_CHECK_ARG(x && y && B > 0 && T > 1 && D > 0 && D % 4 == 0 && (long)B * (D / 4) < 0x7fffffffL, "token_mean_fwd: bad args (T=%d D=%d)", T, D);
+    SGX_CHECK_ARG(VIT_LD4(x_ld_pix) && VIT_LD4(x_ld_img) && VIT_LD4(y_ld) && VIT_ALIGNED(x) && VIT_ALIGNED(y),
+                  "token_mean_fwd: strides and addresses must be multiples of 16 bytes");
+    SGX_LAUNCH(token_mean_fwd_kernel, dim3(sgx_cdiv((long)B * (D / 4), 256)), dim3(256), 0, stream, B, T, D / 4, x, (long)x_ld_pix, (long)x_ld_img, y, (long)y_ld);
+    SGX_CHECK_LAUNCH("token_mean_fwd");
+    return SGX_OK;
+}
+extern "C" int32_t sgx_token_mean_bwd(int32_t B, int32_t T, int32_t D, const float* dy, int64_t dy_ld, float* dx, int64_t x_ld_pix, int64_t x_ld_img, void* stream) {
+    SGX_CHECK_ARG(dy && dx && B > 0 && T > 1 && D > 0 && D % 4 == 0, "token_mean_bwd: bad args (T=%d D=%d)", T, D);
+    SGX_CHECK_ARG(VIT_LD4(x_ld_pix) && VIT_LD4(x_ld_img) && VIT_LD4(dy_ld) && VIT_ALIGNED(dx) && VIT_ALIGNED(dy),
+                  "token_mean_bwd: strides and addresses must be multiples of 16 bytes");
+    const long n = (long)B * T * (D / 4), blocks = (n + 255) / 256;
+    SGX_LAUNCH(token_mean_bwd_kernel, dim3((unsigned)SGX_STRIDE_GRID(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, stream, B, T, D / 4, dy, (long)dy_ld, dx,
+               (long)x_ld_pix, (long)x_ld_img);
+    SGX_CHECK_LAUNCH("token_mean_bwd");
     return SGX_OK;
 }
 
@@ -567,7 +913,8 @@ extern "C" int32_t sgx_patch_rows(int32_t B, int32_t gh, int32_t gw, int32_t ph,
     return SGX_OK;
 }
 
-// Token assembly: x[b][0] = cls + pos[0], x[b][1 + i] = patch[b][i] + pos[1 + i] (T = 1 + patches per image), one launch.  Backward:
+// Token assembly: x[b][0] = cls + pos[0], x[b][1 + i] = patch[b][i] + pos[1 + i] (T = 1 + patches per image), one launch; pos / dpos may be
+// NULL (no position embedding: the rows move unchanged, the backward sums the class-token row only).  Backward:
 // dpos[t] += sum_b dx[b][t] in ascending image order (fp64 accumulator, one rounding), dcls += the row-0 sum; the patch rows' gradient is the
 // view dx[:, 1:] and needs no kernel.
 __global__ __launch_bounds__(256) void token_assemble_kernel(int B, int T, int D4, const float* patch, long p_ld_pix, long p_ld_img, const float* cls,
@@ -579,13 +926,17 @@ __global__ __launch_bounds__(256) void token_assemble_kernel(int B, int T, int D
         const int t = (int)(r % T);
         const long b = r / T;
         const float4 a = t == 0 ? sgx_ld4(cls + c) : sgx_ld4(patch + b * p_ld_img + (long)(t - 1) * p_ld_pix + c);
+        if (!pos) {  // (BEiT without an absolute position embedding: the rows move as they are)
+            sgx_st4(x + b * x_ld_img + (long)t * x_ld_pix + c, a);
+            continue;
+        }
         const float4 p = sgx_ld4(pos + (long)t * D4 * 4 + c);
         sgx_st4(x + b * x_ld_img + (long)t * x_ld_pix + c, make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w));
     }
 }
 __global__ __launch_bounds__(256) void token_assemble_bwd_kernel(int B, int T, int D4, const float* dx, long x_ld_pix, long x_ld_img, float* dcls,
                                                                  float* dpos) {
-    const long n = (long)T * D4;
+    const long n = (long)(dpos ? T : 1) * D4;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i % D4) * 4;
         const int t = (int)(i / D4);
@@ -595,8 +946,11 @@ __global__ __launch_bounds__(256) void token_assemble_bwd_kernel(int B, int T, i
             s[0] += a.x; s[1] += a.y; s[2] += a.z; s[3] += a.w;
         }
         const float4 r = make_float4((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
-        float4 o = sgx_ld4(dpos + (long)t * D4 * 4 + c);
-        sgx_st4(dpos + (long)t * D4 * 4 + c, make_float4(o.x + r.x, o.y + r.y, o.z + r.z, o.w + r.w));
+        float4 o;
+        if (dpos) {
+            o = sgx_ld4(dpos + (long)t * D4 * 4 + c);
+            sgx_st4(dpos + (long)t * D4 * 4 + c, make_float4(o.x + r.x, o.y + r.y, o.z + r.z, o.w + r.w));
+        }
         if (t == 0) {
             o = sgx_ld4(dcls + c);
             sgx_st4(dcls + c, make_float4(o.x + r.x, o.y + r.y, o.z + r.z, o.w + r.w));
@@ -605,7 +959,7 @@ __global__ __launch_bounds__(256) void token_assemble_bwd_kernel(int B, int T, i
 }
 extern "C" int32_t sgx_token_assemble_fwd(int32_t B, int32_t T, int32_t D, const float* patch, int64_t p_ld_pix, int64_t p_ld_img, const float* cls,
                                           const float* pos, float* x, int64_t x_ld_pix, int64_t x_ld_img, void* stream) {
-    SGX_CHECK_ARG(cls && pos && x && (patch || T == 1) && B > 0 && T > 0 && D > 0 && D % 4 == 0, "token_assemble_fwd: bad args (D=%d)", D);
+    SGX_CHECK_ARG(cls && x && (patch || T == 1) && B > 0 && T > 0 && D > 0 && D % 4 == 0, "token_assemble_fwd: bad args (D=%d)", D);
     SGX_CHECK_ARG(VIT_LD4(p_ld_pix) && VIT_LD4(p_ld_img) && VIT_LD4(x_ld_pix) && VIT_LD4(x_ld_img) && VIT_ALIGNED(patch) && VIT_ALIGNED(cls) && VIT_ALIGNED(pos) &&
                       VIT_ALIGNED(x),
                   "token_assemble_fwd: strides and addresses must be multiples of 16 bytes");
@@ -617,10 +971,10 @@ extern "C" int32_t sgx_token_assemble_fwd(int32_t B, int32_t T, int32_t D, const
 }
 extern "C" int32_t sgx_token_assemble_bwd(int32_t B, int32_t T, int32_t D, const float* dx, int64_t x_ld_pix, int64_t x_ld_img, float* dcls, float* dpos,
                                           void* stream) {
-    SGX_CHECK_ARG(dx && dcls && dpos && B > 0 && T > 0 && D > 0 && D % 4 == 0, "token_assemble_bwd: bad args (D=%d)", D);
+    SGX_CHECK_ARG(dx && dcls && B > 0 && T > 0 && D > 0 && D % 4 == 0, "token_assemble_bwd: bad args (D=%d)", D);
     SGX_CHECK_ARG(VIT_LD4(x_ld_pix) && VIT_LD4(x_ld_img) && VIT_ALIGNED(dx) && VIT_ALIGNED(dcls) && VIT_ALIGNED(dpos),
                   "token_assemble_bwd: strides and addresses must be multiples of 16 bytes");
-    const long n = (long)T * (D / 4), blocks = (n + 255) / 256;
+    const long n = (long)(dpos ? T : 1) * (D / 4), blocks = (n + 255) / 256;  // (no position embedding: the class-token row alone)
     SGX_LAUNCH(token_assemble_bwd_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, stream, B, T, D / 4, dx, (long)x_ld_pix,
                (long)x_ld_img, dcls, dpos);
     SGX_CHECK_LAUNCH("token_assemble_bwd");

@@ -1321,10 +1321,91 @@ def token_assemble_fwd(patch, cls, pos, out=None):
 
 
 def token_assemble_bwd(dx, dcls, dpos):
-    """dpos[t] += sum_b dx[b, t], dcls += sum_b dx[b, 0] (in place, fixed image order)."""
+    """dpos[t] += sum_b dx[b, t], dcls += sum_b dx[b, 0] (in place, fixed image order); dpos None: the class-token row only."""
     n, t, _, D = dx.shape
     xl, xi = nhwc_strides(dx)
     check(lib().sgx_token_assemble_bwd(n, t, D, ptr(dx), xl, xi, ptr(dcls), ptr(dpos), stream()), "sgx_token_assemble_bwd")
+
+
+# --------------------------------------------------------------------------------------------- BEiT glue (csrc/vit.h)
+def rpb_rows(grid):
+    """Rows of a relative-position-bias table over a gh x gw token grid behind one class token."""
+    return (2 * grid[0] - 1) * (2 * grid[1] - 1) + 3
+
+
+def _rpb_table(table, heads, grid, what):
+    if table.dim() != 2 or table.shape[0] != rpb_rows(grid) or table.shape[1] != heads or table.stride(1) != 1:
+        raise _lib.SgxError(f"{what}: the table must be [{rpb_rows(grid)}, {heads}] with contiguous heads, got {tuple(table.shape)} strides {tuple(table.stride())}")
+    return table.stride(0)
+
+
+def attn_rpb_fwd(q, k, v, heads, scale, table, grid, out=None):
+    """softmax(scale * q k^T + table[index]) v per (image, head) over a grid = (gh, gw) of patch tokens behind one class token
+    -> (o [B, T, 1, D], lse [B, heads, T]); table [N, heads] (any row stride), the index is computed in the kernel."""
+    b, t, d, (lp, li) = _attn_views(q, k, v, heads)
+    tl = _rpb_table(table, heads, grid, "attn_rpb_fwd")
+    if out is None:
+        out = torch.empty(b, t, 1, heads * d, device=q.device, dtype=torch.float32)
+    lse = torch.empty(b, heads, t, device=q.device, dtype=torch.float32)
+    ol, oi = nhwc_strides(out)
+    check(lib().sgx_attn_rpb_fwd(b, heads, t, d, grid[0], grid[1], ptr(q), ptr(k), ptr(v), lp, li, float(scale), ptr(table), tl, ptr(out), ol, oi, ptr(lse),
+                                 stream()), "sgx_attn_rpb_fwd")
+    return out, lse
+
+
+def attn_rpb_bwd(q, k, v, o, do, lse, heads, scale, table, grid, dq, dk, dv, dtable):
+    """attn_bwd with the bias; the table's gradient is added onto dtable (a view of the table's shape) in a fixed order."""
+    b, t, d, (lp, li) = _attn_views(q, k, v, heads)
+    gl = _attn_views(dq, dk, dv, heads)[3]
+    ol = nhwc_strides(o)
+    if nhwc_strides(do) != ol or o.shape != q.shape or do.shape != q.shape or dq.shape != q.shape:
+        raise _lib.SgxError("attention backward: o and dO must share shape and strides")
+    tl, dtl = _rpb_table(table, heads, grid, "attn_rpb_bwd"), _rpb_table(dtable, heads, grid, "attn_rpb_bwd (dtable)")
+    ws = WORKSPACE.get(lib().sgx_attn_rpb_bwd_workspace(b, heads, t, grid[0], grid[1]), q.device)
+    check(lib().sgx_attn_rpb_bwd(b, heads, t, d, grid[0], grid[1], ptr(q), ptr(k), ptr(v), lp, li, ptr(o), ptr(do), ol[0], ol[1], ptr(lse), float(scale),
+                                 ptr(table), tl, ptr(dq), ptr(dk), ptr(dv), gl[0], gl[1], ptr(dtable), dtl, ptr(ws), ws.numel(), stream()), "sgx_attn_rpb_bwd")
+
+
+def layerscale_fwd(x, t, gamma=None, m=None, out=None):
+    """x + m_b * (gamma * t) over a [B, T, 1, C] stream; gamma [C] or None, m [B] or None; out may be x."""
+    M, ld = token_rows(x)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(lib().sgx_layerscale_fwd(ptr(x), ld, ptr(t), token_rows(t)[1], ptr(gamma), ptr(m), M // x.shape[0], ptr(out), token_rows(out)[1], M, x.shape[3],
+                                   stream()), "sgx_layerscale_fwd")
+    return out
+
+
+def layerscale_bwd(dy, t=None, gamma=None, m=None, dgamma=None, out=None):
+    """dt = m_b * gamma * dy (out may be dy); dgamma (a view of the gradient arena) += sum_rows m_b * dy * t."""
+    M, ld = token_rows(dy)
+    C = dy.shape[3]
+    if out is None:
+        out = torch.empty(dy.shape, device=dy.device, dtype=torch.float32)
+    ws = WORKSPACE.get(lib().sgx_layerscale_bwd_workspace(M, C), dy.device) if dgamma is not None else None
+    check(lib().sgx_layerscale_bwd(ptr(dy), ld, ptr(t), token_rows(t)[1] if t is not None else 0, ptr(gamma), ptr(m), M // dy.shape[0], ptr(out),
+                                   token_rows(out)[1], ptr(dgamma), M, C, ptr(ws), ws.numel() if ws is not None else 0, stream()), "sgx_layerscale_bwd")
+    return out
+
+
+def token_mean_fwd(x, out=None):
+    """[B, T, 1, D] -> [B, 1, 1, D]: the mean of the patch-token rows 1 .. T - 1."""
+    n, t, _, D = x.shape
+    if out is None:
+        out = torch.empty(n, 1, 1, D, device=x.device, dtype=torch.float32)
+    xl, xi = nhwc_strides(x)
+    check(lib().sgx_token_mean_fwd(n, t, D, ptr(x), xl, xi, ptr(out), nhwc_strides(out)[1], stream()), "sgx_token_mean_fwd")
+    return out
+
+
+def token_mean_bwd(dy, tokens, out=None):
+    """The whole [B, T, 1, D] gradient of token_mean_fwd: row 0 zero, the others dy / (T - 1)."""
+    n, _, _, D = dy.shape
+    if out is None:
+        out = torch.empty(n, tokens, 1, D, device=dy.device, dtype=torch.float32)
+    xl, xi = nhwc_strides(out)
+    check(lib().sgx_token_mean_bwd(n, tokens, D, ptr(dy), nhwc_strides(dy)[1], ptr(out), xl, xi, stream()), "sgx_token_mean_bwd")
+    return out
 
 
 # --------------------------------------------------------------------------------------------- pooling

@@ -141,6 +141,9 @@ class SgxNetwork(nn.Module):
             for bname, b in list(m._buffers.items()):
                 if b is None:
                     continue
+                if b.dtype != torch.float32 and b.numel() != 1:  # an index table (BEiT's relative_position_index): no arena, it only moves
+                    m._buffers[bname] = b.to(device)
+                    continue
                 (fbufs if b.dtype == torch.float32 else ibufs).append((m, bname, b))
         for m, bname, b in fbufs:
             self.b_arena.reserve(bname, b.numel())
@@ -315,6 +318,8 @@ class SgxNetwork(nn.Module):
                         _, start, n = new.b_arena.segments[fb]
                         fb += 1
                         m._buffers[bname] = new.b_arena.buf[start: start + n].view(b.shape)
+                    elif b.numel() != 1:  # (an index table: deepcopy's clone is the copy's own)
+                        continue
                     else:
                         m._buffers[bname] = new.i_arena[ib]
                         ib += 1

@@ -10,3 +10,4 @@ from .efficientnet import (BlockArgs, BlockDecoder, CustomizedEfficientnet, Effi
                            EfficientNetB3, EfficientNetB4, EfficientNetB5, EfficientNetB6, EfficientNetB7, EfficientNetB8, EfficientNetL2,
                            MBConvBlock, round_filters, round_repeats)
 from .vit import ViT, ViTBase, ViTHuge, ViTLarge  # noqa: F401
+from .beit import Beit, BeitBasePatch16_224, BeitLargePatch16_224  # noqa: F401

@@ -51,7 +51,7 @@ class TokenLinear(ConvLayer):
 
     _param_kinds = {}
 
-    def __init__(self, in_features, out_features):
+    def __init__(self, in_features, out_features, bias=True):
         SgxBlock.__init__(self)
         if in_features % 4 or out_features % 4:
             _not_built(f"token-wise linear layers need widths that are multiples of 4 (16-byte channel groups), got {in_features} -> {out_features}")
@@ -62,7 +62,10 @@ class TokenLinear(ConvLayer):
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))  # nn.Linear default
         self.weight = nn.Parameter(w)
         bound = 1.0 / math.sqrt(in_features)
-        self.bias = nn.Parameter(torch.empty(out_features).uniform_(-bound, bound))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_features).uniform_(-bound, bound))
+        else:  # (BEiT's qkv: its owner passes a packed bias to the launch, or none)
+            self.register_parameter("bias", None)
         self._w = self._gw = None
 
     def _filter_views(self, slot):
