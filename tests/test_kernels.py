@@ -1622,7 +1622,8 @@ def test_bn_backward_input_gradient_sums_to_zero(backend):
     mean(g) (2^-24 |mean g| in EVERY element) is amplified by M * mean(activation) against a sum that only grows like sqrt(M).  Found by
     the flip-free gradient check at 32 x 640^2 (r3b: 60x further from fp64 than ATen's CPU kernel, which forms g - mean g in double).
     The apply sweeps therefore take mean(g) as hi + lo floats: |sum dx| must stay at the random-rounding level, far below the
-    single-float offset bound M * 2^-24 * |mean g| * c1 (both the plain BatchNorm backward and the QARepVGG pair's)."""
+    single-float offset bound M * 2^-24 * |mean g| * c1.  This test runs the plain BatchNorm backward; the QARepVGG pair's two input
+    gradients are held to the same bound, on these inputs, by tests/test_qarep_kernels.py::test_qarep_input_gradient_sums_to_zero."""
     n, h, w, c = _sizes(backend, (8, 80, 80, 16), (1, 150, 150, 4))
     M = n * h * w
     g = torch.Generator().manual_seed(3)
