@@ -42,6 +42,7 @@ struct StatsF {
 };
 extern "C" int32_t sgx_channel_stats_partial(const float* x, int64_t M, int32_t C, int64_t ld, float* partials, void* stream) {
     SGX_CHECK_ARG(x && partials, "channel_stats: null pointer");
+    SW_CHECK_VEC(C, SW_LD4(ld) && SW_ALIGNED(x) && SW_ALIGNED(partials), "channel_stats");
     StatsF f{x, ld};
     return run_sweep<StatsF, 2, 4>(f, M, C, partials, stream, "channel_stats");
 }
@@ -362,6 +363,9 @@ extern "C" int32_t sgx_affine_act_fwd(const float* x, int64_t x_ld, const float*
     SGX_CHECK_ARG(x && y, "affine_act: null pointer");
     SGX_CHECK_ACT4(act, "affine_act");
     SGX_CHECK_ARG((scale == nullptr) == (shift == nullptr), "affine_act: scale and shift go together");
+    SW_CHECK_VEC(C, SW_LD4(x_ld) && SW_LD4(y_ld) && (!r1 || SW_LD4(r1_ld)) && (!r2 || SW_LD4(r2_ld)) && SW_ALIGNED(x) && SW_ALIGNED(y) && SW_ALIGNED(r1) && SW_ALIGNED(r2) &&
+                     SW_ALIGNED(scale) && SW_ALIGNED(shift) && SW_ALIGNED(partials),
+                 "affine_act");
     AffineActF f{x, x_ld, scale, shift, r1, r1_ld, a1, a1_dev, r2, r2_ld, a2, y, y_ld, act};
     return run_sweep<AffineActF, 2, 4>(f, M, C, partials, stream, "affine_act");
 }
@@ -402,6 +406,7 @@ extern "C" int32_t sgx_dropout_fwd(const float* x, int64_t x_ld, float* y, int64
                                    void* stream) {
     SGX_CHECK_ARG(x && y, "dropout: null pointer");
     SGX_CHECK_ARG(p >= 0.f && p < 1.f, "dropout: p = %g outside [0, 1)", (double)p);
+    SW_CHECK_VEC(C, SW_LD4(x_ld) && SW_LD4(y_ld) && SW_ALIGNED(x) && SW_ALIGNED(y), "dropout");
     DropoutF f{x, x_ld, y, y_ld, C / 4, (unsigned)((double)p * 4294967296.0), (float)(1.0 - (double)p), seed, offset};
     return run_sweep<DropoutF, 0, 4>(f, M, C, nullptr, stream, "dropout");
 }
@@ -430,6 +435,8 @@ extern "C" int32_t sgx_bn_bwd_reduce(const float* dy, int64_t dy_ld, const float
                                      const float* save_mean, int64_t M, int32_t C, int32_t act, float* partials, void* stream) {
     SGX_CHECK_ARG(dy && x && scale && shift && save_mean && partials, "bn_bwd_reduce: null pointer");
     SGX_CHECK_ACT4(act, "bn_bwd_reduce");
+    SW_CHECK_VEC(C, SW_LD4(dy_ld) && SW_LD4(x_ld) && SW_ALIGNED(dy) && SW_ALIGNED(x) && SW_ALIGNED(scale) && SW_ALIGNED(shift) && SW_ALIGNED(save_mean) && SW_ALIGNED(partials),
+                 "bn_bwd_reduce");
     BnBwdReduceF f{dy, dy_ld, x, x_ld, scale, shift, save_mean, act};
     return run_sweep<BnBwdReduceF, 2, 4>(f, M, C, partials, stream, "bn_bwd_reduce");
 }
@@ -512,6 +519,9 @@ extern "C" int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float*
                                     int32_t act, void* stream) {
     SGX_CHECK_ARG(dy && x && scale && shift && coef && dx, "bn_bwd_apply: null pointer");
     SGX_CHECK_ACT4(act, "bn_bwd_apply");
+    SW_CHECK_VEC(C, SW_LD4(dy_ld) && SW_LD4(x_ld) && SW_LD4(dx_ld) && (!g_out || SW_LD4(g_ld)) && SW_ALIGNED(dy) && SW_ALIGNED(x) && SW_ALIGNED(scale) && SW_ALIGNED(shift) &&
+                     SW_ALIGNED(coef) && SW_ALIGNED(dx) && SW_ALIGNED(g_out),
+                 "bn_bwd_apply");
     BnBwdApplyF f{dy, dy_ld, x, x_ld, scale, shift, coef, C, dx, dx_ld, g_out, g_ld, act};
     return run_sweep<BnBwdApplyF, 0, 4>(f, M, C, nullptr, stream, "bn_bwd_apply");
 }
@@ -581,6 +591,7 @@ extern "C" int32_t sgx_dot(const float* a, int64_t a_ld, const float* b, int64_t
     SGX_CHECK_ARG(a && b && out && ws, "dot: null pointer");
     SGX_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "dot: need M>0 and C%%4==0 (C=%d)", C);
     if (ws_bytes < sgx_dot_workspace(M, C)) SGX_FAIL(SGX_ERR_WORKSPACE, "dot: workspace too small (sgx_dot_workspace)");
+    SW_CHECK_VEC(C, SW_LD4(a_ld) && SW_LD4(b_ld) && SW_ALIGNED(a) && SW_ALIGNED(b), "dot");
     SweepGeom g = sweep_geom(M, C);
     SGX_LAUNCH(dot_kernel, dim3(g.nblk, g.ctiles), dim3(SW_THREADS), 0, stream, a, (long)a_ld, b, (long)b_ld, g, (double*)ws);
     SGX_CHECK_LAUNCH("dot");
@@ -611,6 +622,7 @@ struct AxpyF {
 extern "C" int32_t sgx_axpy(const float* x, int64_t x_ld, float a, const float* a_dev, float* y, int64_t y_ld, int64_t M, int32_t C,
                             int32_t accumulate, void* stream) {
     SGX_CHECK_ARG(x && y, "axpy: null pointer");
+    SW_CHECK_VEC(C, SW_LD4(x_ld) && SW_LD4(y_ld) && SW_ALIGNED(x) && SW_ALIGNED(y), "axpy");
     AxpyF f{x, x_ld, a, a_dev, y, y_ld, accumulate};
     return run_sweep<AxpyF, 0, 4>(f, M, C, nullptr, stream, "axpy");
 }
@@ -631,6 +643,7 @@ struct ReluBwdF {
 extern "C" int32_t sgx_relu_bwd(const float* dy, int64_t dy_ld, const float* y, int64_t y_ld, float* g, int64_t g_ld, int64_t M, int32_t C,
                                 void* stream) {
     SGX_CHECK_ARG(dy && y && g, "relu_bwd: null pointer");
+    SW_CHECK_VEC(C, SW_LD4(dy_ld) && SW_LD4(y_ld) && SW_LD4(g_ld) && SW_ALIGNED(dy) && SW_ALIGNED(y) && SW_ALIGNED(g), "relu_bwd");
     ReluBwdF f{dy, dy_ld, y, y_ld, g, g_ld};
     return run_sweep<ReluBwdF, 0, 4>(f, M, C, nullptr, stream, "relu_bwd");
 }
@@ -655,6 +668,9 @@ struct ReluBwdBnReduceF {
 extern "C" int32_t sgx_relu_bwd_bn_reduce(const float* dy, int64_t dy_ld, const float* y, int64_t y_ld, const float* x, int64_t x_ld,
                                           const float* save_mean, float* g, int64_t g_ld, int64_t M, int32_t C, float* partials, void* stream) {
     SGX_CHECK_ARG(dy && y && x && save_mean && g && partials, "relu_bwd_bn_reduce: null pointer");
+    SW_CHECK_VEC(C, SW_LD4(dy_ld) && SW_LD4(y_ld) && SW_LD4(x_ld) && SW_LD4(g_ld) && SW_ALIGNED(dy) && SW_ALIGNED(y) && SW_ALIGNED(x) && SW_ALIGNED(save_mean) && SW_ALIGNED(g) &&
+                     SW_ALIGNED(partials),
+                 "relu_bwd_bn_reduce");
     ReluBwdBnReduceF f{dy, dy_ld, y, y_ld, x, x_ld, save_mean, g, g_ld};
     return run_sweep<ReluBwdBnReduceF, 2, 4>(f, M, C, partials, stream, "relu_bwd_bn_reduce");
 }
@@ -769,6 +785,8 @@ extern "C" int32_t sgx_qarep_bwd_reduce(const float* dout, int64_t d_ld, const f
                                         const float* sv, int64_t M, int32_t C, int32_t act, float* partials4, void* stream) {
     SGX_CHECK_ARG(dout && y && u && cf && sv && partials4, "qarep_bwd_reduce: null pointer");
     SGX_CHECK_ACT3(act, "qarep_bwd_reduce");
+    SW_CHECK_VEC(C, SW_LD4(d_ld) && SW_LD4(y_ld) && SW_LD4(u_ld) && SW_ALIGNED(dout) && SW_ALIGNED(y) && SW_ALIGNED(u) && SW_ALIGNED(cf) && SW_ALIGNED(sv) && SW_ALIGNED(partials4),
+                 "qarep_bwd_reduce");
     QarepBwdReduceF f{QarepBwdBase{dout, d_ld, y, y_ld, u, u_ld, cf, sv, C, act}};
     return run_sweep<QarepBwdReduceF, 4, 2>(f, M, C, partials4, stream, "qarep_bwd_reduce");  // (three tensors per row: two rows in flight)
 }
@@ -837,6 +855,9 @@ extern "C" int32_t sgx_qarep_bwd_apply(const float* dout, int64_t d_ld, const fl
                                        int32_t act, void* stream) {
     SGX_CHECK_ARG(dout && y && u && cf && sv && cb && ds && dy, "qarep_bwd_apply: null pointer");
     SGX_CHECK_ACT3(act, "qarep_bwd_apply");
+    SW_CHECK_VEC(C, SW_LD4(d_ld) && SW_LD4(y_ld) && SW_LD4(u_ld) && SW_LD4(ds_ld) && SW_LD4(dy_ld) && SW_ALIGNED(dout) && SW_ALIGNED(y) && SW_ALIGNED(u) && SW_ALIGNED(cf) &&
+                     SW_ALIGNED(sv) && SW_ALIGNED(cb) && SW_ALIGNED(ds) && SW_ALIGNED(dy),
+                 "qarep_bwd_apply");
     QarepBwdApplyF f{QarepBwdBase{dout, d_ld, y, y_ld, u, u_ld, cf, sv, C, act}, cb, ds, ds_ld, dy, dy_ld};
     return run_sweep<QarepBwdApplyF, 0, 2>(f, M, C, nullptr, stream, "qarep_bwd_apply");
 }
@@ -936,6 +957,10 @@ extern "C" int32_t sgx_tri_affine_act_fwd(const float* x1, int64_t x1_ld, const 
     SGX_CHECK_ACT3(act, "tri_affine_act_fwd");
     SGX_CHECK_ARG(!x2 || (s2 && t2), "tri_affine_act_fwd: second branch needs scale and shift");
     SGX_CHECK_ARG(!x3 || (s3 && t3), "tri_affine_act_fwd: third branch needs scale and shift");
+    SW_CHECK_VEC(C, SW_LD4(x1_ld) && (!x2 || SW_LD4(x2_ld)) && (!x3 || SW_LD4(x3_ld)) && (!r || SW_LD4(r_ld)) && SW_LD4(y_ld) && SW_ALIGNED(x1) && SW_ALIGNED(s1) && SW_ALIGNED(t1) &&
+                     (!x2 || (SW_ALIGNED(x2) && SW_ALIGNED(s2) && SW_ALIGNED(t2))) && (!x3 || (SW_ALIGNED(x3) && SW_ALIGNED(s3) && SW_ALIGNED(t3))) && SW_ALIGNED(r) &&
+                     SW_ALIGNED(y) && SW_ALIGNED(partials),
+                 "tri_affine_act_fwd");
     Branch br[3] = {{x1, x1_ld, s1, t1, nullptr}, {x2, x2_ld, s2, t2, nullptr}, {x3, x3_ld, s3, t3, nullptr}};
     const int nb = present(br);
     const BranchSumOut o{r, r_ld, r_scale, r_scale_dev, y, y_ld};
@@ -998,6 +1023,10 @@ extern "C" int32_t sgx_tri_affine_act_bwd_reduce(const float* dy, int64_t dy_ld,
     SGX_CHECK_ACT3(act, "tri_affine_act_bwd_reduce");
     SGX_CHECK_ARG(!x2 || (s2 && t2 && mean2), "tri_affine_act_bwd_reduce: second branch needs scale, shift and mean");
     SGX_CHECK_ARG(!x3 || (s3 && t3 && mean3), "tri_affine_act_bwd_reduce: third branch needs scale, shift and mean");
+    SW_CHECK_VEC(C, SW_LD4(dy_ld) && SW_LD4(x1_ld) && (!x2 || SW_LD4(x2_ld)) && (!x3 || SW_LD4(x3_ld)) && SW_LD4(g_ld) && SW_ALIGNED(dy) && SW_ALIGNED(x1) && SW_ALIGNED(s1) &&
+                     SW_ALIGNED(t1) && SW_ALIGNED(mean1) && (!x2 || (SW_ALIGNED(x2) && SW_ALIGNED(s2) && SW_ALIGNED(t2) && SW_ALIGNED(mean2))) &&
+                     (!x3 || (SW_ALIGNED(x3) && SW_ALIGNED(s3) && SW_ALIGNED(t3) && SW_ALIGNED(mean3))) && SW_ALIGNED(g) && SW_ALIGNED(partials),
+                 "tri_affine_act_bwd_reduce");
     Branch br[3] = {{x1, x1_ld, s1, t1, mean1}, {x2, x2_ld, s2, t2, mean2}, {x3, x3_ld, s3, t3, mean3}};
     const int nb = present(br);
     return nb == 1 ? branch_sum_bwd_reduce<1>(br, act, dy, dy_ld, g, g_ld, M, C, partials, nblk, stream)
@@ -1035,6 +1064,7 @@ extern "C" int64_t sgx_colsum_workspace(int64_t M, int32_t C) {
 extern "C" int32_t sgx_colsum(const float* x, int64_t ld, int64_t M, int32_t C, int64_t rows_per_img, int64_t ld_img, float* out,
                               int32_t accumulate, float* ws, void* stream) {
     SGX_CHECK_ARG(x && out && ws && rows_per_img > 0, "colsum: bad args");
+    SW_CHECK_VEC(C, SW_LD4(ld) && SW_LD4(ld_img) && SW_ALIGNED(x) && SW_ALIGNED(ws), "colsum");
     ColsumF f{x, ld, rows_per_img, ld_img};
     int32_t rc = run_sweep<ColsumF, 1, 4>(f, M, C, ws, stream, "colsum");
     if (rc) return rc;

@@ -5,6 +5,16 @@
 
 #define SW_THREADS 256
 #define SW_MAXCG 64  // float4 channel groups per workgroup strip (256 channels)
+// every sweep moves float4 (sgx_ld4 / sgx_st4): the addresses of its tensors, per-channel rows and partial rows (NULL passes: an absent
+// operand) and its row strides must be multiples of 16 bytes (include/sgx_hip.h, conventions) - checked by the entry points, before any launch
+#define SW_ALIGNED(p) (((uintptr_t)(p) % 16) == 0)
+#define SW_LD4(ld) ((ld) % 4 == 0)
+// (the channel count first: the per-channel rows of one operand sit C floats apart)
+#define SW_CHECK_VEC(C, cond, what)                                                                   \
+    do {                                                                                              \
+        SGX_CHECK_ARG((C) > 0 && (C) % 4 == 0, "%s: need M>0 and C%%4==0 (C=%d)", what, (int)(C));    \
+        SGX_CHECK_ARG(cond, "%s: strides and addresses must be multiples of 16 bytes", what);         \
+    } while (0)
 
 struct SweepGeom {
     long M;
