@@ -1076,35 +1076,47 @@ def _gate_rows(x):
     return n, h * w, c, rows(x)[1]
 
 
-def bn_gate_act_fwd(x, scale, shift, pre, gate, act=None, out=None):
-    """y = act(f(pre[n,c]) * (scale * x + shift)); scale = shift = None: z = x (the folded eval form)."""
+# sgx_bn_gate_act_* (gate, then activation) and sgx_bn_act_gate_* (activation, then gate) take the same arguments: one body per kind, `name` picks the entry point
+def _gate_fwd(name, x, scale, shift, pre, gate, act, out):
     n, hw, c, ld = _gate_rows(x)
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-    check(lib().sgx_bn_gate_act_fwd(ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ptr(out), rows(out)[1], n, hw, c, ACT[act], stream()),
-          "sgx_bn_gate_act_fwd")
+    check(getattr(lib(), name)(ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ptr(out), rows(out)[1], n, hw, c, ACT[act], stream()), name)
     return out
 
 
-def bn_gate_act_bwd_gate(dy, x, scale, shift, pre, gate, act=None):
-    """dpre[n,c] = f'(pre) * sum_pixels gv * z, gv = dy * act'(f(pre) * z)."""
+def _gate_bwd_gate(name, dy, x, scale, shift, pre, gate, act):
     n, hw, c, ld = _gate_rows(x)
     out = torch.empty(n, c, device=x.device, dtype=torch.float32)
-    ws = WORKSPACE.get(lib().sgx_bn_gate_act_bwd_gate_workspace(n, hw, c), x.device)
-    check(lib().sgx_bn_gate_act_bwd_gate(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(out), n, hw, c, ptr(ws),
-                                         ws.numel(), stream()), "sgx_bn_gate_act_bwd_gate")
+    ws = WORKSPACE.get(getattr(lib(), name + "_workspace")(n, hw, c), x.device)
+    check(getattr(lib(), name)(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(out), n, hw, c, ptr(ws), ws.numel(),
+                               stream()), name)
     return out
 
 
-def bn_gate_act_bwd_data(dy, x, scale, shift, pre, gate, act=None, dmean=None, save_mean=None, out=None, want_parts=False):
-    """dz = gv * f(pre) + dmean[n,c] / HW -> dz, or (dz, parts) with the BatchNorm-backward reduce rows of (dz, x) (bn_bwd(parts=...))."""
+def _gate_bwd_data(name, dy, x, scale, shift, pre, gate, act, dmean, save_mean, out, want_parts):
     n, hw, c, ld = _gate_rows(x)
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     parts = torch.empty(2, stats_blocks(n * hw), c, device=x.device, dtype=torch.float32) if want_parts else None
-    check(lib().sgx_bn_gate_act_bwd_data(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(dmean), ptr(out),
-                                         rows(out)[1], ptr(save_mean), ptr(parts), n, hw, c, stream()), "sgx_bn_gate_act_bwd_data")
+    check(getattr(lib(), name)(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(dmean), ptr(out), rows(out)[1],
+                               ptr(save_mean), ptr(parts), n, hw, c, stream()), name)
     return (out, parts) if want_parts else out
+
+
+def bn_gate_act_fwd(x, scale, shift, pre, gate, act=None, out=None):
+    """y = act(f(pre[n,c]) * (scale * x + shift)); scale = shift = None: z = x (the folded eval form)."""
+    return _gate_fwd("sgx_bn_gate_act_fwd", x, scale, shift, pre, gate, act, out)
+
+
+def bn_gate_act_bwd_gate(dy, x, scale, shift, pre, gate, act=None):
+    """dpre[n,c] = f'(pre) * sum_pixels gv * z, gv = dy * act'(f(pre) * z)."""
+    return _gate_bwd_gate("sgx_bn_gate_act_bwd_gate", dy, x, scale, shift, pre, gate, act)
+
+
+def bn_gate_act_bwd_data(dy, x, scale, shift, pre, gate, act=None, dmean=None, save_mean=None, out=None, want_parts=False):
+    """dz = gv * f(pre) + dmean[n,c] / HW -> dz, or (dz, parts) with the BatchNorm-backward reduce rows of (dz, x) (bn_bwd(parts=...))."""
+    return _gate_bwd_data("sgx_bn_gate_act_bwd_data", dy, x, scale, shift, pre, gate, act, dmean, save_mean, out, want_parts)
 
 
 def bn_act_gate_mean(x, scale, shift, act=None):
@@ -1118,33 +1130,17 @@ def bn_act_gate_mean(x, scale, shift, act=None):
 
 def bn_act_gate_fwd(x, scale, shift, pre, gate, act=None, out=None):
     """y = f(pre[n,c]) * act(scale * x + shift); scale = shift = None: z = x (the folded eval form)."""
-    n, hw, c, ld = _gate_rows(x)
-    if out is None:
-        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-    check(lib().sgx_bn_act_gate_fwd(ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ptr(out), rows(out)[1], n, hw, c, ACT[act], stream()),
-          "sgx_bn_act_gate_fwd")
-    return out
+    return _gate_fwd("sgx_bn_act_gate_fwd", x, scale, shift, pre, gate, act, out)
 
 
 def bn_act_gate_bwd_gate(dy, x, scale, shift, pre, gate, act=None):
     """dpre[n,c] = f'(pre) * sum_pixels dy * act(z)."""
-    n, hw, c, ld = _gate_rows(x)
-    out = torch.empty(n, c, device=x.device, dtype=torch.float32)
-    ws = WORKSPACE.get(lib().sgx_bn_act_gate_bwd_gate_workspace(n, hw, c), x.device)
-    check(lib().sgx_bn_act_gate_bwd_gate(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(out), n, hw, c, ptr(ws),
-                                         ws.numel(), stream()), "sgx_bn_act_gate_bwd_gate")
-    return out
+    return _gate_bwd_gate("sgx_bn_act_gate_bwd_gate", dy, x, scale, shift, pre, gate, act)
 
 
 def bn_act_gate_bwd_data(dy, x, scale, shift, pre, gate, act=None, dmean=None, save_mean=None, out=None, want_parts=False):
     """dz = (dy * f(pre) + dmean[n,c] / HW) * act'(z) -> dz, or (dz, parts) with the BatchNorm-backward reduce rows of (dz, x) (bn_bwd(parts=...))."""
-    n, hw, c, ld = _gate_rows(x)
-    if out is None:
-        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-    parts = torch.empty(2, stats_blocks(n * hw), c, device=x.device, dtype=torch.float32) if want_parts else None
-    check(lib().sgx_bn_act_gate_bwd_data(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(pre), GATE[gate], ACT[act], ptr(dmean), ptr(out),
-                                         rows(out)[1], ptr(save_mean), ptr(parts), n, hw, c, stream()), "sgx_bn_act_gate_bwd_data")
-    return (out, parts) if want_parts else out
+    return _gate_bwd_data("sgx_bn_act_gate_bwd_data", dy, x, scale, shift, pre, gate, act, dmean, save_mean, out, want_parts)
 
 
 def bn_gate_add(x, scale, shift, pre, gate, r, out=None):
