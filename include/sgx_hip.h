@@ -228,8 +228,10 @@ int32_t sgx_conv2d_bwd_weight(const sgx_conv_desc* d, const float* x, const floa
  * nn.Conv2d, sg_trainer.py:611-647 -> qarepvgg_block.py:105-128): a GROUP of them runs as one launch per tile shape, the pixel split of
  * every job sized so that the group - not each layer alone - fills the chip, and the split partials are folded inside the launch by
  * arrival tickets in a fixed order (deterministic; no separate reduce launch).  jobs: HOST array (read during the call only); ws:
- * sgx_conv2d_bwd_weight_group_sizes bytes of scratch; tickets: that many int32, ZERO on entry, owned by this stream between calls (the
- * kernels leave them zero, so a caller clears the buffer once).  dw += gradient, as above.                                            */
+ * sgx_conv2d_bwd_weight_group_sizes bytes of scratch; tickets: that many int32, owned by this stream between calls, cleared ONCE when
+ * they are allocated and never again: a ticket counts only if it holds the launch epoch of the current call (a process-wide counter of
+ * the library), so whatever earlier calls - of this or of another job list - or an aborted launch left there is fine.  (A call recorded
+ * into a graph clears its tickets itself: every replay carries the epoch of the capture.)  dw += gradient, as above.                     */
 typedef struct sgx_wgrad_job {
     sgx_conv_desc d;
     const float* x;
@@ -242,6 +244,13 @@ int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_t njobs, vo
 /* Measurement aid for the grouped weight gradient: rounds of work items a large group is cut into (0 = default 6), work of an item below
  * which a small group is not cut further (MFLOP, 0 = default 8; an item is never larger than twice that), XCD-aware workgroup order (default 1).  Never set by the product.     */
 int32_t sgx_debug_set_wgrad_group(int32_t rounds, int32_t item_mflop, int32_t xcd_order);
+/* Measurement aid for the fold tree of the grouped weight gradient.  0 (default): a workgroup looks at its pair's ticket before it publishes
+ * its node and publishes nothing where the sibling is already there; tickets carry the launch epoch and are never cleared.  1: every node is
+ * published and the used tickets are cleared on every call (the earlier form; bit-identical results).  Never set by the product.
+ * sgx_debug_wgrad_fold_counts: nodes published / skipped so far (reset != 0: and zero them) - counted by the host emulation build only
+ * (tests); the product kernels carry no counter and report -1.                                                                          */
+int32_t sgx_debug_set_wgrad_fold(int32_t mode);
+int32_t sgx_debug_wgrad_fold_counts(int64_t* published, int64_t* skipped, int32_t reset);
 /* Measurement aid: deep_slab bit 0 = 32-pixel slabs in the weight-gradient loop for the tiles whose two slabs fit 32 KB of LDS, bit 1 = ONE
  * slab of global loads in flight instead of two (one register set), bit 2 = the 64x64 tile on two waves instead of four, bit 3 = the
  * bf16x3 loop (three bf16 planes per slab, operands through the LDS transpose read, six bf16 MFMAs per product; the main tile shapes).

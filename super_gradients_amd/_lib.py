@@ -134,6 +134,8 @@ PROTOTYPES = {
     "sgx_conv2d_bwd_weight_group_sizes": (_i32, [POINTER(WgradJob), _i32, POINTER(c_int64), POINTER(c_int64)]),
     "sgx_conv2d_bwd_weight_group": (_i32, [POINTER(WgradJob), _i32, _P, _i64, _P, _i64, _P]),
     "sgx_debug_set_wgrad_group": (_i32, [_i32] * 3),
+    "sgx_debug_set_wgrad_fold": (_i32, [_i32]),
+    "sgx_debug_wgrad_fold_counts": (_i32, [POINTER(c_int64), POINTER(c_int64), _i32]),
     "sgx_debug_set_wgrad_loop": (_i32, [_i32]),
     "sgx_conv_set_wgrad_math": (_i32, [_i32]),
     "sgx_conv_get_wgrad_math": (_i32, []),
@@ -310,6 +312,11 @@ def lib():
         wgg = os.environ.get("SGX_WGRAD_GROUP")  # measurement switch of the grouped weight gradient: "rounds,item_mflop,xcd_order" (0 = default)
         if wgg:
             _LIB.sgx_debug_set_wgrad_group(*[int(v) for v in wgg.split(",")])
+        wgf = os.environ.get("SGX_WGRAD_FOLD")  # measurement switch of the fold tree: "publish" = every node published, tickets cleared per call
+        if wgf:
+            if wgf not in WGRAD_FOLD:
+                raise RuntimeError(f"SGX_WGRAD_FOLD={wgf!r}: expected one of {sorted(WGRAD_FOLD)}")
+            _LIB.sgx_debug_set_wgrad_fold(WGRAD_FOLD[wgf])
         # measurement switches of the weight-gradient loop: 32-pixel slabs (small tiles), one slab of loads in flight; one tile shape for
         # every layer "bnk,bj"
         if os.environ.get("SGX_WGRAD_SLAB") == "32" or os.environ.get("SGX_WGRAD_PF"):
@@ -340,6 +347,7 @@ def lib():
 
 
 WGRAD_MATH = {"fp32": 0, "bf16x3": 1, "patch": 2}
+WGRAD_FOLD = {"look": 0, "publish": 1}
 DEFAULT_TUNING = os.path.join(_HERE, "csrc", "conv_tuning_gfx950.json")
 TUNE_FIELDS = ("kind", "N", "H", "W", "C", "K", "R", "stride", "pad", "bm", "bn", "variant")
 

@@ -2517,12 +2517,13 @@ extern "C" int32_t sgx_conv2d_bwd_data_dual(const sgx_conv_desc* d, const float*
 // The split partials are folded INSIDE the launch, deterministically, by a fixed binary tree over the split index that the workgroups walk
 // in arrival order (see the kernel's tail): fixed association whatever the arrival order, pairwise summation, no float atomics, no
 // separate reduce launch, no workgroup folding more than one partner tile per level.  The hand-over moves with device-scope stores /
-// loads (sc1), not with L2 write-back fences.  Tickets are zero on entry and are left zero (the second arriver of a pair resets it).
+// loads (sc1), not with L2 write-back fences.  A ticket is "taken" when it holds the call's launch epoch (WgFold, wgrad_patch.h): no
+// ticket is ever cleared or reset.
 // ------------------------------------------------------------------------------------------------
 #define WG_BKP 16      // pixels per slab (template parameter BKP of the kernel: 16, or WG_BKP_DEEP for the tiles whose two slabs stay <= 32 KB)
 #define WG_BKP_DEEP 32
 #define WG_MAX_SPLIT 4096
-#define WG_MAX_JOBS 24  // the job table travels as kernel arguments: 24 x (152 + 4) B + 8 B < 4 KB
+#define WG_MAX_JOBS 24  // the job table travels as kernel arguments: 24 x (152 + 4) B + 16 B < 4 KB
 
 struct WgJob {
     const float* X;
@@ -2538,6 +2539,7 @@ struct WgJob {
 };
 struct WgGroupParams {
     int njobs, xcd_order;
+    WgFold fold;
     int blk0[WG_MAX_JOBS];  // first workgroup of every job, together: the job lookup is a handful of scalar loads, not one per job
     WgJob jobs[WG_MAX_JOBS];
 };
@@ -2833,7 +2835,11 @@ __global__ __launch_bounds__(WK * WC * 64, MATH ? 1 : wg_min_waves((BNK / (WK * 
     // two children (fp32 addition commutes), so the result is bit-reproducible - and it is a pairwise summation: ~log2(ksplit) roundings
     // on top of the chains.  No workgroup ever folds more than one partner tile per level (the serial "last arriver folds them all" form
     // measured r3b: 55 TFLOP/s against 88 for the two-launch kernel it replaced).  Tickets: one per pair, at the right child's
-    // leftmost-leaf index (odd x 2^L: unique over the tree), reset by the second arriver.
+    // leftmost-leaf index (odd x 2^L: unique over the tree); "taken" = holds this call's epoch (exchanged in by whoever publishes).
+    // LOOK before publishing: only the first arriver's node is ever loaded, so a workgroup first reads the ticket (one lane, one sc1
+    // load - no loop, nobody waits for anybody).  Taken: the sibling published and its stores were acknowledged BEFORE its exchange, so
+    // this workgroup writes nothing, waits for no store and loads the sibling's node behind the barrier that broadcasts the look.  Not
+    // taken: publish, wait, exchange as ever; if the exchange returns the epoch, both published (the only wasted node left).
     const int ksplit = p.ksplit;
     if (ksplit > 1) {
         constexpr int TE = BNK * BJ;
@@ -2844,27 +2850,37 @@ __global__ __launch_bounds__(WK * WC * 64, MATH ? 1 : wg_min_waves((BNK / (WK * 
             const int i = split >> L, sib = i ^ 1;
             if (((long)sib << L) >= ksplit) continue;  // no sibling on this level: the value passes up as it is
             float* const mine = base + ((long)i << L) * TE;
-#pragma unroll
-            for (int a = 0; a < TK; ++a)
-#pragma unroll
-                for (int b = 0; b < TC; ++b) {
-                    float* const q = mine + foff + (a * 32) * BJ + b * 32;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sgx_st_dev(&q[((r & 3) + 8 * (r >> 2)) * BJ], acc[a][b][r]);
-                    sgx_sched_fence();
-                }
-            sgx_wait_stores();
-            __syncthreads();
-            if (tid == 0) {
-                int* const t = &tk[((long)(i | 1)) << L];
-                const int old = atomicAdd(t, 1);
-                s_last = old;
-                if (old) *t = 0;
+            int* const t = &tk[((long)(i | 1)) << L];
+            int second = 0;  // the sibling's node is in memory (published, acknowledged, its ticket taken)
+            if (g.fold.look) {
+                if (tid == 0) s_last = sgx_ld_dev_i32(t) == g.fold.epoch;
+                __syncthreads();
+                second = s_last;
             }
-            __syncthreads();
-            const int second = s_last;
-            __syncthreads();  // (s_last is rewritten on the next level)
-            if (!second) return;
+            if (second) {
+                if (tid == 0) SGX_FOLD_COUNT(g_sgx_fold_skipped);
+                __syncthreads();  // (s_last is rewritten on the next level)
+            } else {
+#pragma unroll
+                for (int a = 0; a < TK; ++a)
+#pragma unroll
+                    for (int b = 0; b < TC; ++b) {
+                        float* const q = mine + foff + (a * 32) * BJ + b * 32;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) sgx_st_dev(&q[((r & 3) + 8 * (r >> 2)) * BJ], acc[a][b][r]);
+                        sgx_sched_fence();
+                    }
+                sgx_wait_stores();
+                __syncthreads();  // (every wave has read the look, too)
+                if (tid == 0) {
+                    SGX_FOLD_COUNT(g_sgx_fold_published);
+                    s_last = sgx_ticket_xchg(t, g.fold.epoch) == g.fold.epoch;
+                }
+                __syncthreads();
+                second = s_last;
+                __syncthreads();  // (s_last is rewritten on the next level)
+                if (!second) return;
+            }
             const float* const other = base + ((long)sib << L) * TE;
 #pragma unroll
             for (int a = 0; a < TK; ++a)
@@ -2950,6 +2966,30 @@ extern "C" int32_t sgx_debug_set_wgrad_patch(int32_t item_mflop, int32_t kb, int
     g_wp_item_mflop = item_mflop ? item_mflop : 48;
     g_wp_kb = kb;
     g_wp_fill = min_fill_pct ? min_fill_pct : 60;
+    return SGX_OK;
+}
+// The fold tree's tickets (WgFold, wgrad_patch.h).  g_wg_epoch: process-wide, advanced once per grouped call, never 0; once it has wrapped
+// the calls clear their tickets again (an old value could now match).  g_wg_fold (measurement: sgx_debug_set_wgrad_fold) 1 = every node
+// is published and the used ticket range is cleared on every call - the fold before the look and the epoch.
+static std::atomic<uint32_t> g_wg_epoch{0};
+static std::atomic<int> g_wg_epoch_wrapped{0}, g_wg_fold{0};
+#ifdef SGX_EMU
+std::atomic<long> g_sgx_fold_published{0}, g_sgx_fold_skipped{0};
+#endif
+extern "C" int32_t sgx_debug_set_wgrad_fold(int32_t mode) {
+    SGX_CHECK_ARG(mode == 0 || mode == 1, "debug_set_wgrad_fold: mode must be 0 (look, epoch tickets) or 1 (always publish, clear per call)");
+    g_wg_fold = mode;
+    return SGX_OK;
+}
+extern "C" int32_t sgx_debug_wgrad_fold_counts(int64_t* published, int64_t* skipped, int32_t reset) {
+    SGX_CHECK_ARG(published && skipped, "debug_wgrad_fold_counts: null pointer");
+#ifdef SGX_EMU
+    *published = reset ? g_sgx_fold_published.exchange(0) : g_sgx_fold_published.load();
+    *skipped = reset ? g_sgx_fold_skipped.exchange(0) : g_sgx_fold_skipped.load();
+#else
+    (void)reset;
+    *published = *skipped = -1;  // the product kernels carry no counter
+#endif
     return SGX_OK;
 }
 struct WgPlan {
@@ -3120,9 +3160,26 @@ extern "C" int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_
     if (rc) return rc;
     if (!ws || ws_bytes < pf * 4 + 256 || ((uintptr_t)ws % 16) != 0) SGX_FAIL(SGX_ERR_WORKSPACE, "conv bwd_weight_group: workspace too small / unaligned");
     if (!tickets || ticket_ints < ti + 1) SGX_FAIL(SGX_ERR_WORKSPACE, "conv bwd_weight_group: ticket buffer too small");
-    // The fold trees leave their tickets zero (the second arriver of a pair resets it), but that invariant would not survive an aborted
-    // launch or a plan that changed between two calls on one buffer: the used range is cleared on every call (a few KB, stream-ordered).
-    if (ti > 0) SGX_MEMSET_ASYNC(tickets, 0, ti * 4, stream);
+    // This call's epoch: what earlier calls, an aborted launch or another plan left in the buffer is an older epoch (or the zero of
+    // allocation) and cannot match, so nothing is cleared.  Exceptions, which clear the used range as every call once did: the
+    // measurement switch, a counter that has wrapped (old values could match again), and a call recorded into a graph - every replay
+    // would carry the epoch of the capture, so the clear is recorded with it.
+    WgFold fold;
+    {
+        uint32_t e = ++g_wg_epoch;
+        if (e == 0) {
+            g_wg_epoch_wrapped = 1;
+            e = ++g_wg_epoch;
+        }
+        fold.epoch = (int)e;
+        fold.look = g_wg_fold.load(std::memory_order_relaxed) == 0;
+        bool clear = !fold.look || g_wg_epoch_wrapped.load(std::memory_order_relaxed);
+#ifndef SGX_EMU
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (!clear && (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) clear = true;
+#endif
+        if (clear && ti > 0) SGX_MEMSET_ASYNC(tickets, 0, ti * 4, stream);
+    }
     std::vector<char> done(njobs, 0);
     // ---- the patch kernel's jobs: one launch per kernel form (stride, tile columns, filter blocks) and WP_MAX_JOBS jobs of it
     for (int first = 0; first < njobs; ++first) {
@@ -3130,6 +3187,7 @@ extern "C" int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_
         WpGroupParams g;
         memset(&g, 0, sizeof(g));
         g.xcd_order = g_wg_xcd.load(std::memory_order_relaxed);
+        g.fold = fold;
         const WpPlan& form = plans[first].wp;
         const int stride = jobs[first].d.stride;
         int nblk = 0;
@@ -3170,6 +3228,7 @@ extern "C" int32_t sgx_conv2d_bwd_weight_group(const sgx_wgrad_job* jobs, int32_
         WgGroupParams g;
         memset(&g, 0, sizeof(g));
         g.xcd_order = g_wg_xcd.load(std::memory_order_relaxed);
+        g.fold = fold;
         int nblk = 0;
         double flops = 0.0, bytes = 0.0;
         for (int i = first; i < njobs && g.njobs < WG_MAX_JOBS; ++i) {

@@ -183,13 +183,16 @@ __device__ __forceinline__ uint4 sgx_buf_ld4u(sgx_buf b, unsigned off) {
 // workgroup's stores visible by writing back the WHOLE L2 (buffer_wbl2 sc1) and an acquire fence invalidates it (buffer_inv sc1):
 // measured (r3a) at ~3x the weight-gradient kernel's run time when every workgroup publishes a partial tile that way.  Instead the
 // hand-over data itself moves with device-scope accesses (sc1: written through to / read from the memory side, no cache walk):
-//   producer: sgx_st_dev* ... sgx_wait_stores() (stores acknowledged) ... __syncthreads() ... one atomicAdd on the ticket
-//   consumer: (sees the last ticket) ... sgx_ld4_dev
+//   producer: sgx_st_dev* ... sgx_wait_stores() (stores acknowledged) ... __syncthreads() ... one sgx_ticket_xchg on the pair's ticket
+//   consumer: (its exchange returned the sibling's mark, or its sgx_ld_dev_i32 LOOK at the ticket saw it) ... __syncthreads() ... sgx_ld4_dev
+// sgx_ld_dev_i32: one device-scope relaxed load of a ticket (an sc1 load: never served by this CU's L1) - a LOOK, never a poll loop.
 #ifdef SGX_EMU
 static inline void sgx_st_dev(float* p, float v) { *p = v; }
 static inline float sgx_ld_dev(const float* p) { return *p; }
 static inline void sgx_st4_dev(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 static inline float4 sgx_ld4_dev(const float* p) { return *reinterpret_cast<const float4*>(p); }
+static inline int sgx_ld_dev_i32(const int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+static inline int sgx_ticket_xchg(int* p, int v) { return __atomic_exchange_n(p, v, __ATOMIC_SEQ_CST); }
 #define sgx_wait_stores() __atomic_thread_fence(__ATOMIC_SEQ_CST)
 #define sgx_sched_fence() ((void)0)
 #define SGX_SCHED_GROUP(mask, n) ((void)0)
@@ -232,6 +235,8 @@ __device__ __forceinline__ float4 sgx_ld4_dev(const float* p) {
     memcpy(hi, &b, 8);
     return make_float4(lo[0], lo[1], hi[0], hi[1]);
 }
+__device__ __forceinline__ int sgx_ld_dev_i32(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int sgx_ticket_xchg(int* p, int v) { return __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #define sgx_wait_stores() __builtin_amdgcn_s_waitcnt(0)  // vmcnt(0) expcnt(0) lgkmcnt(0): every store of this wave has been acknowledged
 #endif
 

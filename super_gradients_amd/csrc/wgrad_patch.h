@@ -20,8 +20,24 @@ struct WpJob {
     int blk0;                      // first workgroup of the job in its launch (a multiple of 8: XCD phase 0)
     int xcd_ranges;                // 1: workgroup b works on pixel range b % 8 + ... (enough ranges to keep the eight XCDs level)
 };
+// The fold tree's tickets (both kernels): a pair's ticket counts as "the sibling has arrived" only if it equals the launch EPOCH of this
+// call (never 0; sgx_conv2d_bwd_weight_group advances it) - whatever earlier calls, an aborted launch or another plan left in the buffer
+// is an older epoch or the zero of allocation and cannot match, so nobody clears or resets a ticket.  look != 0: a workgroup reads the
+// pair's ticket BEFORE it publishes its node and, where the sibling is already there, publishes nothing (nobody would read it).
+struct WgFold {
+    int epoch, look;
+};
+#ifdef SGX_EMU
+#include <atomic>
+extern std::atomic<long> g_sgx_fold_published, g_sgx_fold_skipped;  // nodes written / not written (emulation only: tests)
+#define SGX_FOLD_COUNT(c) ((c).fetch_add(1, std::memory_order_relaxed))
+#else
+#define SGX_FOLD_COUNT(c) ((void)0)
+#endif
+
 struct WpGroupParams {
     int njobs, xcd_order;
+    WgFold fold;
     int blk0[WP_MAX_JOBS];
     WpJob jobs[WP_MAX_JOBS];
 };

@@ -22,7 +22,7 @@
 // Arithmetic: the six-product bf16x3 scheme of conv_mma.h, ONE accumulator per 32x32 block (six roundings per 16 pixels where the fp32
 // pipe has sixteen; the pixel splits are summed pairwise by the fold tree below).
 // The pixel splits of a (job, tile) are folded inside the launch by the arrival-walked binary tree of wgrad_kernel (fixed association,
-// no float atomics, tickets left zero); a node travels as 16-byte device-scope stores in accumulator order (fully coalesced).
+// no float atomics, look before publishing, epoch tickets that nobody clears); a node travels as 16-byte device-scope stores in accumulator order (fully coalesced).
 #include "conv_mma.h"
 #include "wgrad_patch.h"
 
@@ -270,25 +270,35 @@ __global__ __launch_bounds__(192 * KB, (S == 2 && PC == 4) ? 2 : 3) void wpatch_
             const int i = split >> L, sib = i ^ 1;
             if (((long)sib << L) >= ksplit) continue;  // no sibling on this level: the value passes up as it is
             float* const mine = base + ((long)i << L) * TE + foff;
-#pragma unroll
-            for (int t = 0; t < TAPW; ++t) {
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4)
-                    sgx_st4_dev(mine + (t * 4 + r4) * 256, make_float4(acc[t][4 * r4], acc[t][4 * r4 + 1], acc[t][4 * r4 + 2], acc[t][4 * r4 + 3]));
-                sgx_sched_fence();
+            int* const tp = &tk[((long)(i | 1)) << L];
+            int second = 0;  // the sibling's node is in memory (published, acknowledged, its ticket taken)
+            if (g.fold.look) {  // look before publishing (wgrad_kernel): nobody loads a second arriver's node
+                if (tid == 0) s_last = sgx_ld_dev_i32(tp) == g.fold.epoch;
+                __syncthreads();
+                second = s_last;
             }
-            sgx_wait_stores();
-            __syncthreads();
-            if (tid == 0) {
-                int* const tp = &tk[((long)(i | 1)) << L];
-                const int old = atomicAdd(tp, 1);
-                s_last = old;
-                if (old) *tp = 0;
+            if (second) {
+                if (tid == 0) SGX_FOLD_COUNT(g_sgx_fold_skipped);
+                __syncthreads();  // (s_last is rewritten on the next level)
+            } else {
+#pragma unroll
+                for (int t = 0; t < TAPW; ++t) {
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4)
+                        sgx_st4_dev(mine + (t * 4 + r4) * 256, make_float4(acc[t][4 * r4], acc[t][4 * r4 + 1], acc[t][4 * r4 + 2], acc[t][4 * r4 + 3]));
+                    sgx_sched_fence();
+                }
+                sgx_wait_stores();
+                __syncthreads();  // (every wave has read the look, too)
+                if (tid == 0) {
+                    SGX_FOLD_COUNT(g_sgx_fold_published);
+                    s_last = sgx_ticket_xchg(tp, g.fold.epoch) == g.fold.epoch;
+                }
+                __syncthreads();
+                second = s_last;
+                __syncthreads();  // (s_last is rewritten on the next level)
+                if (!second) return;
             }
-            __syncthreads();
-            const int second = s_last;
-            __syncthreads();  // (s_last is rewritten on the next level)
-            if (!second) return;
             const float* const other = base + ((long)sib << L) * TE + foff;
 #pragma unroll
             for (int t = 0; t < TAPW; ++t) {

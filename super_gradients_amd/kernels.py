@@ -667,8 +667,9 @@ _TICKETS = {}
 
 
 def _ticket_buffer(n_ints: int, device) -> torch.Tensor:
-    """The arrival-ticket buffer of the grouped weight gradient on the current stream: int32, zero when handed to a launch and left zero by
-    it (include/sgx_hip.h: sgx_conv2d_bwd_weight_group), so it is cleared exactly once - when it is allocated."""
+    """The arrival-ticket buffer of the grouped weight gradient on the current stream: int32, cleared exactly once - when it is allocated.
+    A ticket counts only if it holds the launch epoch of the call that reads it (include/sgx_hip.h: sgx_conv2d_bwd_weight_group), so any
+    values earlier calls left in the buffer are fine and no call clears it."""
     key = (device, stream() or 0)
     b = _TICKETS.get(key)
     if b is None or b.numel() < n_ints:

@@ -6,7 +6,8 @@ the loop / the grouping - interleaved in ONE process (rounds x configs, median).
 A config is a '+'-joined list of:  base (the product default: bf16x3 arithmetic, patch kernel on the 3x3 problems) | nopatch (bf16x3 slab loop
 everywhere) | fp32 (the fp32 slab loop everywhere) | slab32 | pf1 (one slab of loads in flight instead of two) | w2 (64x64 tile on two
 waves) | bf16 (force the bf16x3 slab loop) | gR.I.X (sgx_debug_set_wgrad_group rounds.item_mflop.xcd) | tBxJ (tile override of the slab
-loop) | pI.K.F (sgx_debug_set_wgrad_patch: largest item MFLOP . filter blocks . least fill percent).
+loop) | pI.K.F (sgx_debug_set_wgrad_patch: largest item MFLOP . filter blocks . least fill percent) | pub (sgx_debug_set_wgrad_fold 1: every
+fold node published, tickets cleared per call - the fold before the look and the launch epoch).
 Per group (= one K.conv2d_bwd_weight_group call of the step): jobs, GFLOP, then microseconds per config; last line: ms per step and
 algorithmic TFLOP/s.  Measurement tool: product library only.
 """
@@ -56,10 +57,13 @@ def apply_config(cfg, lib):
     lib.sgx_debug_set_wgrad_group(0, 0, 1)
     lib.sgx_debug_set_tiles(0, 0, 0, 0, 0)
     lib.sgx_debug_set_wgrad_patch(0, 0, 0)
+    lib.sgx_debug_set_wgrad_fold(0)
     deep = 0
     for part in cfg.split("+"):
         if part == "base":
             pass
+        elif part == "pub":
+            lib.sgx_debug_set_wgrad_fold(1)
         elif part == "nopatch":
             deep |= 16
         elif part == "fp32":
