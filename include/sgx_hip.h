@@ -393,6 +393,39 @@ int32_t sgx_bn_bwd_apply(const float* dy, int64_t dy_ld, const float* x, int64_t
  * (seed, offset).  The decision does not depend on strides or launch geometry; p == 0 copies x bit for bit.                        */
 int32_t sgx_dropout_fwd(const float* x, int64_t x_ld, float* y, int64_t y_ld, int64_t M, int32_t C, float p, uint64_t seed, uint64_t offset,
                         void* stream);
+/* DenseNet (classification_models/densenet.py; kernels in csrc/dense.h).  A dense block keeps one concat buffer [N, H, W, C_total]; every
+ * layer reads a channel prefix and writes growth_rate channels behind it.  The batch sums of a channel do not depend on which BatchNorm
+ * reads it: they are folded once, where the slice is produced, into the block's statistics RECORD - fp64 [2][rec_ld], plane 0 the sums,
+ * plane 1 the sums of squares - and every BatchNorm over a prefix (each layer's norm1, the transition's norm, norm5) finalises from it.
+ *   sgx_dense_stats_reduce   partial rows [2][nblk][C_slice] (sgx_conv2d_fwd's epilogue, sgx_channel_stats_partial, ...) ->
+ *                            record[p][c_off + c]; the order of sgx_bn_reduce_sums, bit for bit; nothing outside the slice is touched.
+ *                            ws: sgx_reduce_workspace(nblk, C_slice) bytes.
+ *   sgx_dense_bn_finalize    record[:, 0 .. C_in) -> scale, shift, save_mean, save_invstd of ONE BatchNorm from its gamma / beta / eps /
+ *                            momentum, its running statistics updated in place (sgx_bn_finalize_sums' rule: unbiased running variance).
+ *   sgx_dense_bn_bwd_apply   sgx_bn_bwd_apply's arithmetic with dx += ...: C is the prefix, channels behind it (dx_ld > C) stay untouched.
+ *                            coef from sgx_bn_bwd_finalize, its partial rows from sgx_bn_bwd_reduce.
+ * C_slice / C_in / C, c_off and rec_ld are multiples of 4, addresses and row strides multiples of 16 bytes (SGX_ERR_BAD_ARG otherwise,
+ * nothing is launched).  No atomics, fixed summation order: the same inputs give the same bits.                                         */
+int32_t sgx_dense_stats_reduce(const float* partials, int32_t nblk, int32_t C_slice, double* record, int64_t rec_ld, int32_t c_off, void* ws,
+                               int64_t ws_bytes, void* stream);
+int32_t sgx_dense_bn_finalize(const double* record, int64_t rec_ld, int64_t M, int32_t C_in, const float* gamma, const float* beta, float eps,
+                              float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
+                              float* shift, void* stream);
+int32_t sgx_dense_bn_bwd_apply(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                               const float* coef, float* dx, int64_t dx_ld, int64_t M, int32_t C, int32_t act, void* stream);
+/* BatchNorm -> activation -> AvgPool2d(2, 2) as one sweep (densenet.py's _Transition, with the pool ahead of the 1x1 convolution: both are
+ * linear).  x: [N, H, W, C] rows x_ld apart (a channel prefix of a wider buffer), H, W >= 2, N*H*W < 2^31; pooled maps are
+ * [N, H/2, W/2, C]; with odd H or W the last row / column lies outside every window (nn.AvgPool2d's floor rule).
+ *   _fwd         z = mean over the window of act(scale*x + shift)   (training: scale / shift of the batch; eval: of the running statistics)
+ *   _bwd_reduce  g = dz(h/2, w/2) / 4 * act'(scale*x + shift) at every full-resolution pixel (0 outside every window; ReLU at exactly 0: 0);
+ *                partials [2][sgx_stats_blocks(N*H*W)][C] = sum g, sum g*(x - save_mean): sgx_bn_bwd_reduce's rows, for sgx_bn_bwd_finalize
+ *   _bwd_apply   dx = c1 * ((g - mg - mg_lo) - (x - mean) * k) at EVERY pixel of the map (overwrites: the first touch of a gradient buffer) */
+int32_t sgx_bn_act_avgpool2_fwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                                int32_t act, float* z, int64_t z_ld, void* stream);
+int32_t sgx_bn_act_avgpool2_bwd_reduce(int32_t N, int32_t H, int32_t W, int32_t C, const float* dz, int64_t dz_ld, const float* x, int64_t x_ld,
+                                       const float* scale, const float* shift, const float* save_mean, int32_t act, float* partials, void* stream);
+int32_t sgx_bn_act_avgpool2_bwd_apply(int32_t N, int32_t H, int32_t W, int32_t C, const float* dz, int64_t dz_ld, const float* x, int64_t x_ld,
+                                      const float* scale, const float* shift, const float* coef, int32_t act, float* dx, int64_t dx_ld, void* stream);
 /* QARepVGG block, training form, on sgx_conv2d_fwd_dual's outputs (y = conv3x3(x), u = conv1x1(x; alpha*W1 + I) + b1, five moment planes):
  * replaces, per block, F.batch_norm x2 + the two branch adds + the activation (modules/qarepvgg_block.py:184-204) and their backward.
  *   sgx_qarep_fwd_finalize  both BatchNorms' statistics from the moments (s = bn3(y) + u is affine in (y, u) per channel; fp64): running

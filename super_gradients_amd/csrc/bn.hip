@@ -231,14 +231,10 @@ static int32_t col_prereduce(const float* partials, int nblk, int C, void* ws, i
     return SGX_OK;
 }
 
-__global__ void bn_finalize_kernel(ColSrc src, long M, int C, const float* gamma, const float* beta, float eps,
-                                   float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd,
-                                   float* scale, float* shift) {
-    SGX_FIN_THREAD(src, C);
-    double tot[2];
-    col_totals<2>(src, C, c, cok, tot);
-    if (!writer) return;
-    const double s = tot[0], q = tot[1];
+// channel c of one BatchNorm from its sum s and sum of squares q over M elements (shared with the dense block's finalize, dense.h)
+__device__ __forceinline__ void bn_finalize_channel(double s, double q, long M, int c, const float* gamma, const float* beta, float eps, float momentum,
+                                                    float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
+                                                    float* shift) {
     double mean = s / (double)M;
     double var = q / (double)M - mean * mean;
     if (var < 0.0) var = 0.0;
@@ -254,6 +250,15 @@ __global__ void bn_finalize_kernel(ColSrc src, long M, int C, const float* gamma
     float sc = g * (float)invstd;
     scale[c] = sc;
     shift[c] = b - (float)mean * sc;
+}
+__global__ void bn_finalize_kernel(ColSrc src, long M, int C, const float* gamma, const float* beta, float eps,
+                                   float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd,
+                                   float* scale, float* shift) {
+    SGX_FIN_THREAD(src, C);
+    double tot[2];
+    col_totals<2>(src, C, c, cok, tot);
+    if (!writer) return;
+    bn_finalize_channel(tot[0], tot[1], M, c, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, scale, shift);
 }
 extern "C" int32_t sgx_bn_finalize(const float* partials, int32_t nblk, int64_t M, int32_t C, const float* gamma, const float* beta,
                                    float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
@@ -502,14 +507,18 @@ struct BnBwdApplyF {
         return Cst{sgx_ld4(scale + c), sgx_ld4(shift + c), sgx_ld4(coef + c), sgx_ld4(coef + C + c), sgx_ld4(coef + 2 * C + c), sgx_ld4(coef + 3 * C + c),
                    sgx_ld4(coef + 4 * C + c)};
     }
-    __device__ void apply(long r, int c, const In& in, const Cst& kc, float4 (&)[1]) const {
-        const float4 d = in.d, v = in.v;
+    // -> dx of one row's four channels; g: the masked upstream gradient (the accumulating form of the dense blocks, dense.h, shares it)
+    __device__ __forceinline__ float4 dx_of(const float4& d, const float4& v, const Cst& kc, float4& g) const {
         const float4 s = kc.s, t = kc.t;
         const float4 c1 = kc.c1, mg = kc.mg, k = kc.k, mu = kc.mu, ml = kc.ml;
-        float4 g = make_float4(bn_masked(d.x, v.x, s.x, t.x, act), bn_masked(d.y, v.y, s.y, t.y, act),
-                               bn_masked(d.z, v.z, s.z, t.z, act), bn_masked(d.w, v.w, s.w, t.w, act));
-        float4 o = make_float4(c1.x * (((g.x - mg.x) - ml.x) - (v.x - mu.x) * k.x), c1.y * (((g.y - mg.y) - ml.y) - (v.y - mu.y) * k.y),
-                               c1.z * (((g.z - mg.z) - ml.z) - (v.z - mu.z) * k.z), c1.w * (((g.w - mg.w) - ml.w) - (v.w - mu.w) * k.w));
+        g = make_float4(bn_masked(d.x, v.x, s.x, t.x, act), bn_masked(d.y, v.y, s.y, t.y, act),
+                        bn_masked(d.z, v.z, s.z, t.z, act), bn_masked(d.w, v.w, s.w, t.w, act));
+        return make_float4(c1.x * (((g.x - mg.x) - ml.x) - (v.x - mu.x) * k.x), c1.y * (((g.y - mg.y) - ml.y) - (v.y - mu.y) * k.y),
+                           c1.z * (((g.z - mg.z) - ml.z) - (v.z - mu.z) * k.z), c1.w * (((g.w - mg.w) - ml.w) - (v.w - mu.w) * k.w));
+    }
+    __device__ void apply(long r, int c, const In& in, const Cst& kc, float4 (&)[1]) const {
+        float4 g;
+        const float4 o = dx_of(in.d, in.v, kc, g);
         sgx_st4(dx + r * dx_ld + c, o);
         if (g_out) sgx_st4(g_out + r * g_ld + c, g);
     }
@@ -1217,3 +1226,7 @@ extern "C" int32_t sgx_pad_standardize_u8_hwc(int32_t h, int32_t w, int32_t C, c
     SGX_CHECK_LAUNCH("pad_standardize_u8");
     return SGX_OK;
 }
+
+// The DenseNet kernels (the block's shared statistics record, the accumulating BatchNorm backward, BatchNorm -> activation -> 2x2 average
+// pool as one sweep) build in this translation unit: they are sweeps and finalize kernels on the pieces above.
+#include "dense.h"

@@ -950,6 +950,116 @@ def bn_bwd(dy, x, scale, shift, gamma, save_mean, save_invstd, dgamma, dbeta, ac
     return (dx, g) if want_g else dx
 
 
+# --------------------------------------------------------------------------------------------- DenseNet (csrc/dense.h)
+def dense_record(C_total, device):
+    """A dense block's statistics record: fp64 [2][C_total] - per-channel sum and sum of squares of the concat buffer."""
+    return torch.empty(2, C_total, device=device, dtype=torch.float64)
+
+
+def dense_stats_reduce(parts, record, c_off, sync=False):
+    """Fold a producer's partial rows [2][nblk][C_slice] into record[:, c_off : c_off + C_slice].  sync: the slice's sums are added over all
+    data-parallel ranks (ONE all-reduce per produced slice, whichever BatchNorms read it later); -> the number of ranks summed."""
+    nblk, C = parts.shape[1], parts.shape[2]
+    ws = WORKSPACE.get(_reduce_workspace(nblk, C), parts.device)
+    if not sync:
+        check(lib().sgx_dense_stats_reduce(ptr(parts), nblk, C, ptr(record), record.stride(0), c_off, ptr(ws), ws.numel(), stream()), "sgx_dense_stats_reduce")
+        return 1
+    sums = torch.empty(2, C, device=parts.device, dtype=torch.float64)  # (a collective wants a contiguous tensor)
+    check(lib().sgx_dense_stats_reduce(ptr(parts), nblk, C, ptr(sums), C, 0, ptr(ws), ws.numel(), stream()), "sgx_dense_stats_reduce")
+    world = _allreduce_sums(sums)
+    record[:, c_off: c_off + C].copy_(sums)
+    return world
+
+
+def dense_bn_finalize(record, M, C_in, gamma, beta, eps, momentum, running_mean, running_var):
+    """One BatchNorm over the first C_in channels of the record -> scale, shift, save_mean, save_invstd; running statistics in place.
+    M: elements per channel behind the record's sums (all ranks' when the record was reduced with sync)."""
+    st = torch.empty(4, C_in, device=record.device, dtype=torch.float32)
+    check(lib().sgx_dense_bn_finalize(ptr(record), record.stride(0), M, C_in, ptr(gamma), ptr(beta), eps, momentum, ptr(running_mean), ptr(running_var),
+                                      ptr(st[2]), ptr(st[3]), ptr(st[0]), ptr(st[1]), stream()), "sgx_dense_bn_finalize")
+    return st.unbind(0)
+
+
+def _bn_bwd_coef(parts, M, gamma, save_mean, save_invstd, dgamma, dbeta, sync):
+    """Stage 2 of the BatchNorm backward as bn_bwd runs it (which keeps its own inline copy: it is called ~100 times per YOLO-NAS step and a
+    call level costs host time there): dgamma / dbeta accumulated in place, -> the apply sweep's coefficient rows [5][C]."""
+    C, dev = parts.shape[2], parts.device
+    coef = torch.empty(5, C, device=dev, dtype=torch.float32)
+    ws = WORKSPACE.get(_reduce_workspace(parts.shape[1], C), dev)
+    if sync:
+        local = torch.empty(2, C, device=dev, dtype=torch.float64)
+        check(lib().sgx_bn_reduce_sums(ptr(parts), parts.shape[1], C, ptr(local), ptr(ws), ws.numel(), stream()), "sgx_bn_reduce_sums")
+        glob = local.clone()
+        world = _allreduce_sums(glob)
+        check(lib().sgx_bn_bwd_finalize_sums(ptr(local), ptr(glob), M * world, C, ptr(gamma), ptr(save_mean), ptr(save_invstd), ptr(dgamma), ptr(dbeta),
+                                             ptr(coef), stream()), "sgx_bn_bwd_finalize_sums")
+    else:
+        check(lib().sgx_bn_bwd_finalize(ptr(parts), parts.shape[1], M, C, ptr(gamma), ptr(save_mean), ptr(save_invstd), ptr(dgamma), ptr(dbeta),
+                                        ptr(coef), ptr(ws), ws.numel(), stream()), "sgx_bn_bwd_finalize")
+    return coef
+
+
+def dense_bn_bwd(dy, x, scale, shift, gamma, save_mean, save_invstd, dgamma, dbeta, dx, act=None, sync=False, parts=None):
+    """BatchNorm(+activation) backward whose input gradient is ADDED to dx (a channel prefix of the block's gradient buffer, already
+    written by the layers behind this one).  parts: reduce rows an earlier kernel left (skips the reduce sweep)."""
+    M, ld = rows(x)
+    C = x.shape[3]
+    dl = rows(dy)[1]
+    a = ACT[act]
+    if parts is None:
+        parts = torch.empty(2, stats_blocks(M), C, device=x.device, dtype=torch.float32)
+        check(lib().sgx_bn_bwd_reduce(ptr(dy), dl, ptr(x), ld, ptr(scale), ptr(shift), ptr(save_mean), M, C, a, ptr(parts), stream()), "sgx_bn_bwd_reduce")
+    coef = _bn_bwd_coef(parts, M, gamma, save_mean, save_invstd, dgamma, dbeta, sync)
+    dense_bn_bwd_apply(dy, x, scale, shift, coef, dx, act=act)
+    return dx
+
+
+def dense_bn_bwd_apply(dy, x, scale, shift, coef, dx, act=None):
+    M, ld = rows(x)
+    if tuple(dx.shape) != tuple(x.shape):
+        raise _lib.SgxError(f"dense_bn_bwd_apply: dx {tuple(dx.shape)} != x {tuple(x.shape)}")
+    check(lib().sgx_dense_bn_bwd_apply(ptr(dy), rows(dy)[1], ptr(x), ld, ptr(scale), ptr(shift), ptr(coef), ptr(dx), rows(dx)[1], M, x.shape[3], ACT[act],
+                                       stream()), "sgx_dense_bn_bwd_apply")
+    return dx
+
+
+def bn_act_avgpool2_fwd(x, scale, shift, act=None, out=None):
+    """avg_pool2d(act(scale * x + shift), 2) as one sweep -> [N, H // 2, W // 2, C]."""
+    n, h, w, c = x.shape
+    _, ld = rows(x)
+    if out is None:
+        out = torch.empty(n, h // 2, w // 2, c, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, h // 2, w // 2, c):
+        raise _lib.SgxError(f"bn_act_avgpool2_fwd: out {tuple(out.shape)} != {(n, h // 2, w // 2, c)}")
+    check(lib().sgx_bn_act_avgpool2_fwd(n, h, w, c, ptr(x), ld, ptr(scale), ptr(shift), ACT[act], ptr(out), rows(out)[1], stream()), "sgx_bn_act_avgpool2_fwd")
+    return out
+
+
+def bn_act_avgpool2_bwd_reduce(dz, x, scale, shift, save_mean, act=None):
+    n, h, w, c = x.shape
+    parts = torch.empty(2, stats_blocks(n * h * w), c, device=x.device, dtype=torch.float32)
+    check(lib().sgx_bn_act_avgpool2_bwd_reduce(n, h, w, c, ptr(dz), rows(dz)[1], ptr(x), rows(x)[1], ptr(scale), ptr(shift), ptr(save_mean), ACT[act],
+                                               ptr(parts), stream()), "sgx_bn_act_avgpool2_bwd_reduce")
+    return parts
+
+
+def bn_act_avgpool2_bwd_apply(dz, x, scale, shift, coef, dx, act=None):
+    n, h, w, c = x.shape
+    if tuple(dx.shape) != tuple(x.shape) or tuple(dz.shape) != (n, h // 2, w // 2, c):
+        raise _lib.SgxError(f"bn_act_avgpool2_bwd_apply: x {tuple(x.shape)}, dz {tuple(dz.shape)}, dx {tuple(dx.shape)}")
+    check(lib().sgx_bn_act_avgpool2_bwd_apply(n, h, w, c, ptr(dz), rows(dz)[1], ptr(x), rows(x)[1], ptr(scale), ptr(shift), ptr(coef), ACT[act], ptr(dx),
+                                              rows(dx)[1], stream()), "sgx_bn_act_avgpool2_bwd_apply")
+    return dx
+
+
+def bn_act_avgpool2_bwd(dz, x, scale, shift, gamma, save_mean, save_invstd, dgamma, dbeta, dx, act=None, sync=False):
+    """Backward of bn_act_avgpool2_fwd through the BatchNorm: dgamma / dbeta accumulated, every pixel of dx written (not accumulated)."""
+    n, h, w, _ = x.shape
+    parts = bn_act_avgpool2_bwd_reduce(dz, x, scale, shift, save_mean, act=act)
+    coef = _bn_bwd_coef(parts, n * h * w, gamma, save_mean, save_invstd, dgamma, dbeta, sync)
+    return bn_act_avgpool2_bwd_apply(dz, x, scale, shift, coef, dx, act=act)
+
+
 def dot_sum(a, b, out, accumulate=True, scale=1.0):
     """out[0] (+)= scale * sum(a*b) over NHWC views a, b."""
     M, la = rows(a)

@@ -248,6 +248,15 @@ class BatchNorm(SgxBlock):
         sc, sh = K.bn_eval_scale_shift(self.weight, self.bias, self.running_mean, self.running_var, self.eps)
         return sc, sh, None, None
 
+    def scale_shift_record(self, rec, channels, training):
+        """scale_shift from a dense block's statistics record (rec.sums: fp64 [2][C_total], rec.count elements per channel behind them)
+        instead of partial rows: this BatchNorm normalises the record's first `channels` channels."""
+        if not training:
+            return self.scale_shift(None, 0, False)
+        if rec.count <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got {rec.count} value(s) per channel ({self.num_features} channels)")
+        return K.dense_bn_finalize(rec.sums, rec.count, channels, self.weight, self.bias, self.eps, self.momentum, self.running_mean, self.running_var)
+
     def backward(self, dy, t, scale, shift, mean, invstd, act, dx_out=None, want_g=False, parts=None):
         return K.bn_bwd(dy, t, scale, shift, self.weight, mean, invstd, self.weight.grad, self.bias.grad, act=act, dx_out=dx_out, want_g=want_g,
                         sync=self._synced(), parts=parts)

@@ -11,3 +11,4 @@ from .efficientnet import (BlockArgs, BlockDecoder, CustomizedEfficientnet, Effi
                            MBConvBlock, round_filters, round_repeats)
 from .vit import ViT, ViTBase, ViTHuge, ViTLarge  # noqa: F401
 from .beit import Beit, BeitBasePatch16_224, BeitLargePatch16_224  # noqa: F401
+from .densenet import (CustomizedDensnet, DenseBlock, DenseLayer, DenseNet, DenseNet121, DenseNet161, DenseNet169, DenseNet201, Transition)  # noqa: F401
