@@ -426,6 +426,31 @@ int32_t sgx_bn_act_avgpool2_bwd_reduce(int32_t N, int32_t H, int32_t W, int32_t 
                                        const float* scale, const float* shift, const float* save_mean, int32_t act, float* partials, void* stream);
 int32_t sgx_bn_act_avgpool2_bwd_apply(int32_t N, int32_t H, int32_t W, int32_t C, const float* dz, int64_t dz_ld, const float* x, int64_t x_ld,
                                       const float* scale, const float* shift, const float* coef, int32_t act, float* dx, int64_t dx_ld, void* stream);
+/* ShuffleNetV2 (classification_models/shufflenetv2.py; kernels in csrc/shuffle.h): the block's cat -> channel_shuffle(2) inside the sweep that
+ * applies a branch's last BatchNorm -> activation.  h is the HALF width (the sweep's channel count, h % 4 == 0); left, right: [M][h] rows with
+ * their own strides; y, dy: [M][2h] with  y[:, 2i] = L[:, i],  y[:, 2i + 1] = R[:, i].  Each side is a COPY (its scale / shift / x / coef
+ * pointers NULL: the stride-1 block's pass-through half, both sides after the eval fold) - its bits are moved, -0.0, NaN payloads and denormals
+ * included - or AFFINE: act(scale * x + shift), act one of the five codes of sgx_affine_act_fwd.
+ *   _fwd         L = left or lact(lscale*left + lshift), R likewise; one 16-byte load per side, two 16-byte stores at y + r*y_ld + 2c, + 4.
+ *   _bwd_reduce  sgx_bn_bwd_reduce of every affine side (x != NULL, then scale, shift, save_mean too) on its elements of dy.  One affine
+ *                side: partials [2][sgx_stats_blocks(M)][h].  Two: ONE sweep, partials [4][sgx_stats_blocks(M)][h] - planes 0-1 the left
+ *                side's, planes 2-3 (at partials + 2 * sgx_stats_blocks(M) * h) the right side's.  Each pair of planes is what
+ *                sgx_bn_bwd_finalize and sgx_bn_reduce_sums (-> all-reduce -> sgx_bn_bwd_finalize_sums) read, unchanged.
+ *   _bwd_apply   an affine side (coef != NULL: its [5][h] rows from sgx_bn_bwd_finalize; x, scale, shift too) stores sgx_bn_bwd_apply's dx
+ *                into its target - which may be its x (in place over the saved convolution output); a copy side stores its elements of dy,
+ *                bit for bit, into its target (a channel slice of the block's input gradient).  At least one side is affine.
+ * Addresses and row strides are multiples of 16 bytes, M > 0 (SGX_ERR_BAD_ARG otherwise, nothing is launched or written).  No atomics,
+ * fixed summation order: the same inputs give the same bits.                                                                          */
+int32_t sgx_shuffle_merge_fwd(const float* left, int64_t left_ld, const float* lscale, const float* lshift, int32_t lact, const float* right,
+                              int64_t right_ld, const float* rscale, const float* rshift, int32_t ract, float* y, int64_t y_ld, int64_t M, int32_t h,
+                              void* stream);
+int32_t sgx_shuffle_merge_bwd_reduce(const float* dy, int64_t dy_ld, const float* xl, int64_t xl_ld, const float* lscale, const float* lshift,
+                                     const float* lmean, int32_t lact, const float* xr, int64_t xr_ld, const float* rscale, const float* rshift,
+                                     const float* rmean, int32_t ract, int64_t M, int32_t h, float* partials, void* stream);
+int32_t sgx_shuffle_merge_bwd_apply(const float* dy, int64_t dy_ld, const float* xl, int64_t xl_ld, const float* lscale, const float* lshift,
+                                    const float* lcoef, int32_t lact, float* d_left, int64_t dl_ld, const float* xr, int64_t xr_ld,
+                                    const float* rscale, const float* rshift, const float* rcoef, int32_t ract, float* d_right, int64_t dr_ld,
+                                    int64_t M, int32_t h, void* stream);
 /* QARepVGG block, training form, on sgx_conv2d_fwd_dual's outputs (y = conv3x3(x), u = conv1x1(x; alpha*W1 + I) + b1, five moment planes):
  * replaces, per block, F.batch_norm x2 + the two branch adds + the activation (modules/qarepvgg_block.py:184-204) and their backward.
  *   sgx_qarep_fwd_finalize  both BatchNorms' statistics from the moments (s = bn3(y) + u is affine in (y, u) per channel; fp64): running

@@ -170,6 +170,9 @@ PROTOTYPES = {
     "sgx_dense_stats_reduce": (_i32, [_P, _i32, _i32, _P, _i64, _i32, _P, _i64, _P]),
     "sgx_dense_bn_finalize": (_i32, [_P, _i64, _i64, _i32, _P, _P, _f, _f, _P, _P, _P, _P, _P, _P, _P]),
     "sgx_dense_bn_bwd_apply": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _P, _i64, _i64, _i32, _i32, _P]),
+    "sgx_shuffle_merge_fwd": (_i32, [_P, _i64, _P, _P, _i32] * 2 + [_P, _i64, _i64, _i32, _P]),
+    "sgx_shuffle_merge_bwd_reduce": (_i32, [_P, _i64] + [_P, _i64, _P, _P, _P, _i32] * 2 + [_i64, _i32, _P, _P]),
+    "sgx_shuffle_merge_bwd_apply": (_i32, [_P, _i64] + [_P, _i64, _P, _P, _P, _i32, _P, _i64] * 2 + [_i64, _i32, _P]),
     "sgx_bn_act_avgpool2_fwd": (_i32, [_i32] * 4 + [_P, _i64, _P, _P, _i32, _P, _i64, _P]),
     "sgx_bn_act_avgpool2_bwd_reduce": (_i32, [_i32] * 4 + [_P, _i64, _P, _i64, _P, _P, _P, _i32, _P, _P]),
     "sgx_bn_act_avgpool2_bwd_apply": (_i32, [_i32] * 4 + [_P, _i64, _P, _i64, _P, _P, _P, _i32, _P, _i64, _P]),

@@ -1230,3 +1230,7 @@ extern "C" int32_t sgx_pad_standardize_u8_hwc(int32_t h, int32_t w, int32_t C, c
 // The DenseNet kernels (the block's shared statistics record, the accumulating BatchNorm backward, BatchNorm -> activation -> 2x2 average
 // pool as one sweep) build in this translation unit: they are sweeps and finalize kernels on the pieces above.
 #include "dense.h"
+
+// The ShuffleNetV2 kernels (a branch's last BatchNorm -> activation sweep that also interleaves the two halves of the block's output, and its
+// backward) build here as well: they are sweeps over BnBwdReduceF / BnBwdApplyF.
+#include "shuffle.h"

@@ -37,7 +37,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    hdrs = [os.path.join(HERE, h) for h in ("sgx_common.h", "sgx_sweep.h", "conv_mma.h", "wgrad_patch.h", "gconv.h", "vit.h", "dense.h")] + [os.path.join(HERE, "..", "..", "include", "sgx_hip.h")]
+    hdrs = [os.path.join(HERE, h) for h in ("sgx_common.h", "sgx_sweep.h", "conv_mma.h", "wgrad_patch.h", "gconv.h", "vit.h", "dense.h", "shuffle.h")] + [os.path.join(HERE, "..", "..", "include", "sgx_hip.h")]
     objdir = os.path.join(HERE, "_obj")
     os.makedirs(objdir, exist_ok=True)
     objs = []

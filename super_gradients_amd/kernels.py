@@ -1060,6 +1060,88 @@ def bn_act_avgpool2_bwd(dz, x, scale, shift, gamma, save_mean, save_invstd, dgam
     return bn_act_avgpool2_bwd_apply(dz, x, scale, shift, coef, dx, act=act)
 
 
+# --------------------------------------------------------------------------------------------- ShuffleNetV2 (csrc/shuffle.h)
+def shuffle_merge(left, right, lscale=None, lshift=None, lact=None, rscale=None, rshift=None, ract=None, out=None):
+    """channel_shuffle(cat((L, R), channels), 2) as one sweep: out[..., 2i] = L[..., i], out[..., 2i + 1] = R[..., i], where a side with
+    scale / shift is act(scale * x + shift) (a branch's last BatchNorm -> activation) and a side without is copied bit for bit."""
+    M, ll = rows(left)
+    n, hh, w, h = left.shape
+    if tuple(right.shape) != tuple(left.shape):
+        raise _lib.SgxError(f"shuffle_merge: left {tuple(left.shape)} != right {tuple(right.shape)}")
+    if out is None:
+        out = torch.empty(n, hh, w, 2 * h, device=left.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, hh, w, 2 * h):
+        raise _lib.SgxError(f"shuffle_merge: out {tuple(out.shape)} != {(n, hh, w, 2 * h)}")
+    check(lib().sgx_shuffle_merge_fwd(ptr(left), ll, ptr(lscale), ptr(lshift), ACT[lact], ptr(right), rows(right)[1], ptr(rscale), ptr(rshift), ACT[ract],
+                                      ptr(out), rows(out)[1], M, h, stream()), "sgx_shuffle_merge_fwd")
+    return out
+
+
+def _shuffle_half(dy, x):
+    if tuple(dy.shape[:3]) != tuple(x.shape[:3]) or dy.shape[3] != 2 * x.shape[3]:
+        raise _lib.SgxError(f"shuffle_merge backward: dy {tuple(dy.shape)} is not twice as wide as x {tuple(x.shape)}")
+    return x.shape[3]
+
+
+def shuffle_merge_bwd_reduce(dy, left=None, right=None):
+    """Stage 1 of the BatchNorm backward of shuffle_merge's affine side(s); a side is (x, scale, shift, save_mean, act) or None (a copy).
+    -> partial rows [2][stats_blocks(M)][h] (one affine side) or [4][stats_blocks(M)][h] (two: [:2] the left side's, [2:] the right's)."""
+    sides = [s for s in (left, right) if s is not None]
+    if not sides:
+        raise _lib.SgxError("shuffle_merge_bwd_reduce: no affine side")
+    M, dl = rows(dy)
+    h = _shuffle_half(dy, sides[0][0])
+    args = []
+    for s in (left, right):
+        if s is None:
+            args += [None, 0, None, None, None, 0]
+        else:
+            _shuffle_half(dy, s[0])
+            args += [ptr(s[0]), rows(s[0])[1], ptr(s[1]), ptr(s[2]), ptr(s[3]), ACT[s[4]]]
+    parts = torch.empty(2 * len(sides), stats_blocks(M), h, device=dy.device, dtype=torch.float32)
+    check(lib().sgx_shuffle_merge_bwd_reduce(ptr(dy), dl, *args, M, h, ptr(parts), stream()), "sgx_shuffle_merge_bwd_reduce")
+    return parts
+
+
+def shuffle_merge_bwd_apply(dy, left, right):
+    """Stage 3.  An affine side is (x, scale, shift, coef, act, target) - target may be x itself; a copy side is its target tensor alone,
+    which receives the side's elements of dy bit for bit."""
+    M, dl = rows(dy)
+    h = dy.shape[3] // 2
+    args = []
+    for s in (left, right):
+        if isinstance(s, torch.Tensor):
+            _shuffle_half(dy, s)
+            args += [None, 0, None, None, None, 0, ptr(s), rows(s)[1]]
+        else:
+            x, scale, shift, coef, act, target = s
+            _shuffle_half(dy, x)
+            _shuffle_half(dy, target)
+            args += [ptr(x), rows(x)[1], ptr(scale), ptr(shift), ptr(coef), ACT[act], ptr(target), rows(target)[1]]
+    check(lib().sgx_shuffle_merge_bwd_apply(ptr(dy), dl, *args, M, h, stream()), "sgx_shuffle_merge_bwd_apply")
+
+
+def shuffle_merge_bwd(dy, left, right):
+    """Backward of shuffle_merge through the BatchNorm(s): reduce sweep -> each BatchNorm's finalize (dgamma / dbeta accumulated in place) ->
+    apply sweep.  An affine side is (t, scale, shift, save_mean, save_invstd, act, bn) with bn a layers.BatchNorm - its input gradient is
+    written in place over t; a copy side is the tensor that receives its half of dy."""
+    def red(s):
+        return None if isinstance(s, torch.Tensor) else (s[0], s[1], s[2], s[3], s[5])
+
+    parts = shuffle_merge_bwd_reduce(dy, red(left), red(right))
+    M = rows(dy)[0]
+    sides, k = [], 0
+    for s in (left, right):
+        if isinstance(s, torch.Tensor):
+            sides.append(s)
+            continue
+        t, scale, shift, mean, invstd, act, bn = s
+        coef = _bn_bwd_coef(parts[k:k + 2], M, bn.weight, mean, invstd, bn.weight.grad, bn.bias.grad, bn._synced())
+        k += 2
+        sides.append((t, scale, shift, coef, act, t))
+    shuffle_merge_bwd_apply(dy, sides[0], sides[1])
+
+
 def dot_sum(a, b, out, accumulate=True, scale=1.0):
     """out[0] (+)= scale * sum(a*b) over NHWC views a, b."""
     M, la = rows(a)

@@ -141,6 +141,37 @@ class _ConvBN(SgxBlock):
             return K.tri_affine_act(t, scale, shift, post_add=post_add, act=self.act, out=out if out is not None else t)
         return K.affine_act(t, scale, shift, r1=residual, act=self.act, out=out if out is not None else t)
 
+    def fwd_raw(self, x):
+        """The layer WITHOUT its affine + activation sweep, for a caller whose own sweep applies them (ShuffleNetV2's merge,
+        shufflenetv2.py): -> (t, scale, shift, save_mean, save_invstd) with y = act(scale * t + shift).  Eval mode: the running statistics'
+        scale / shift and no mean / invstd; after prep_model_for_conversion() t is the finished output (bias and activation in the
+        convolution's epilogue) and scale / shift are None.  Training keeps what bwd_from_dt() needs."""
+        conv, bn = self._parts()
+        if self._gate is not None or x.dtype == K.HALF or conv.depthwise or conv.grouped or self.act in ("relu6", "hswish"):
+            raise NotImplementedError("fwd_raw: a plain fp32 convolution -> BatchNorm [-> ReLU / SiLU] layer")
+        if self.training:
+            self._folded = self._folded_half = None
+            t, parts = conv.conv(x, stats=True)
+            scale, shift, mean, invstd = bn.scale_shift(parts, t.shape[0] * t.shape[1] * t.shape[2], True)
+            self._ctx = (x, t, scale, shift, mean, invstd)
+            self._req = None
+            return t, scale, shift, mean, invstd
+        if self._folded is not None:
+            y = K.conv2d_fwd(x, self._folded[0], bias=self._folded[1], act=self.act, stride=conv.stride, pad=conv.padding)
+            return y, None, None, None, None
+        scale, shift, _, _ = bn.scale_shift(None, 0, False)
+        return conv.conv(x), scale, shift, None, None
+
+    def bwd_from_dt(self, dt, dx_out=None, accumulate=False, need_dx=True):
+        """The rest of the backward of a fwd_raw() step once the caller's sweeps have run the BatchNorm backward (dgamma / dbeta included):
+        dt is the gradient of the convolution's output."""
+        conv, _ = self._parts()
+        (x, _, _, _, _, _), self._ctx = self._ctx, None
+        conv.wgrad(x, dt, bias_grad=False)
+        if not need_dx:
+            return None
+        return conv.dgrad(dt, tuple(x.shape), out=dx_out, accumulate=accumulate)
+
     def bn_reduce_request(self):
         """This layer's BatchNorm-backward reduce as a request for the data-gradient launch that finalises its output gradient (the caller
         hands it to that launch; bwd() then finds the partial sums ready and skips its own reduce sweep).  None when it cannot be handed over

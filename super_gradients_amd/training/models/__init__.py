@@ -10,6 +10,8 @@ from .classification_models import GroupedConvBlock, ResNeXt, ResNeXt50, ResNeXt
 from .classification_models import (CustomizedEfficientnet, EfficientNet, EfficientNetB0, EfficientNetB1, EfficientNetB2, EfficientNetB3, EfficientNetB4,  # noqa: F401
                                     EfficientNetB5, EfficientNetB6, EfficientNetB7, EfficientNetB8, EfficientNetL2)
 from .classification_models import CustomizedDensnet, DenseNet, DenseNet121, DenseNet161, DenseNet169, DenseNet201  # noqa: F401
+from .classification_models import (CustomizedShuffleNetV2, ShuffleNetV2Base, ShufflenetV2_x0_5, ShufflenetV2_x1_0, ShufflenetV2_x1_5,  # noqa: F401
+                                    ShufflenetV2_x2_0)
 from .classification_models import ViT, ViTBase, ViTHuge, ViTLarge  # noqa: F401
 from .classification_models import Beit, BeitBasePatch16_224, BeitLargePatch16_224  # noqa: F401
 from .detection_models.pp_yolo_e.pp_yolo_e import PPYoloE, PPYoloE_L, PPYoloE_M, PPYoloE_S, PPYoloE_X  # noqa: F401

@@ -12,3 +12,5 @@ from .efficientnet import (BlockArgs, BlockDecoder, CustomizedEfficientnet, Effi
 from .vit import ViT, ViTBase, ViTHuge, ViTLarge  # noqa: F401
 from .beit import Beit, BeitBasePatch16_224, BeitLargePatch16_224  # noqa: F401
 from .densenet import (CustomizedDensnet, DenseBlock, DenseLayer, DenseNet, DenseNet121, DenseNet161, DenseNet169, DenseNet201, Transition)  # noqa: F401
+from .shufflenetv2 import (ChannelShuffleInvertedResidual, CustomizedShuffleNetV2, ShuffleNetV2Base, ShufflenetV2_x0_5, ShufflenetV2_x1_0,  # noqa: F401
+                           ShufflenetV2_x1_5, ShufflenetV2_x2_0)
