@@ -45,6 +45,40 @@ def act_name(activation_type) -> str:
     raise ValueError(f"activation {activation_type!r} is not available on the HIP path (relu, relu6, silu, none)")
 
 
+def need_mult4(family, what, n, why="16-byte channel groups"):
+    if n % 4:
+        raise NotImplementedError(f"{family} on the HIP path: {what} must be a multiple of 4 ({why}), got {n}")
+
+
+class Numbered(nn.Module):
+    """Namespace with the child names of a reference nn.Sequential: "0", "1", ... from a list of blocks, or the names given (a
+    sequential with stateless gaps, or named children such as net.stem / blocks.block_0).  len() - and with it truthiness: an empty
+    namespace is falsy - is used only for the ResNet blocks' shortcut, where empty means the identity."""
+
+    def __init__(self, blocks=(), **children):
+        super().__init__()
+        for i, b in enumerate(blocks):
+            self.add_module(str(i), b)
+        for name, m in children.items():
+            self.add_module(name, m)
+
+    def __len__(self):
+        return len(self._modules)
+
+    def blocks(self):
+        return list(self._modules.values())
+
+    children_list = blocks  # (the name the RegNet stages' callers use)
+
+
+class Dropout(nn.Module):
+    """The reference's nn.Dropout in a classifier head: no state; `p` may be set by the user.  The owner draws the mask (classifier.py)."""
+
+    def __init__(self, p):
+        super().__init__()
+        self.p = float(p)
+
+
 class ConvLayer(SgxBlock):
     """Convolution parameters + the three conv kernels.  Not a block by itself: owners call conv()/wgrad()/dgrad()."""
 
@@ -100,6 +134,21 @@ class ConvLayer(SgxBlock):
             return K.conv2d_bwd_data_wt(dy, self._w, self._wt, x_shape, stride=self.stride, pad=self.padding, addend=addend, out=out, accumulate=accumulate,
                                         reqs=reqs if self._net.fuse_bn_reduce else None)
         return K.conv2d_bwd_data(dy, self._w, x_shape, stride=self.stride, pad=self.padding, addend=addend, out=out, accumulate=accumulate)
+
+
+def widen_conv_input(old: ConvLayer, in_channels: int, compute_new_weights_fn=None) -> ConvLayer:
+    """The reference's replace_conv2d_input_channels (modules/weight_replacement_utils.py:24-65): the new first convolution keeps the weights
+    of the channels the old one has; extra channels are drawn from a normal distribution with the old weights' mean / std."""
+    if compute_new_weights_fn is not None:
+        return compute_new_weights_fn(old, in_channels)
+    new = ConvLayer(in_channels, old.out_channels, old.kernel_size, old.stride, old.padding, bias=old.bias is not None)
+    w = old.weight.data
+    if in_channels <= old.in_channels:
+        new.weight.data = w[:, :in_channels].clone()
+    else:
+        new.weight.data[:, : old.in_channels] = w
+        torch.nn.init.normal_(new.weight.data[:, old.in_channels:], mean=float(w.mean()), std=float(w.std()))
+    return new
 
 
 class DepthwiseConvLayer(SgxBlock):
@@ -376,3 +425,17 @@ class LinearLayer(SgxBlock):
                    accumulate=True)
             self.bias.grad.add_(gb[: self.out_features])
         return K.conv2d_bwd_data(dy, w, tuple(x.shape)).view(n, self.in_features)
+
+
+def init_normal_fan_out(net: nn.Module, conv_types):
+    """The initialisation the reference's MobileNets and RegNet share: conv weights N(0, sqrt(2 / (k * k * out_channels))), BatchNorm 1 / 0,
+    linear N(0, 0.01) with zero bias - drawn in net.modules() order.  `conv_types`: the layer classes that count as nn.Conv2d."""
+    for m in net.modules():
+        if isinstance(m, conv_types):
+            m.weight.data.normal_(0, math.sqrt(2.0 / (m.kernel_size * m.kernel_size * m.out_channels)))
+        elif isinstance(m, BatchNorm):
+            m.weight.data.fill_(1)
+            m.bias.data.zero_()
+        elif isinstance(m, LinearLayer):
+            m.weight.data.normal_(0, 0.01)
+            m.bias.data.zero_()

@@ -30,14 +30,14 @@ replace_head(new_head=...), widths or head widths that are not multiples of 4, h
 one, use_rel_pos_bias together with use_shared_rel_pos_bias; supports_half_inference() is False.
 """
 import math
-from typing import Dict
 
 import torch
 from torch import nn
 
 from .... import kernels as K
 from ....common.registry import register_model
-from ....modules.engine import SgxBlock, SgxNetwork
+from ....modules.classifier import SgxClassifier
+from ....modules.engine import SgxBlock
 from ....modules.layers import LinearLayer
 from ...utils.utils import HpmStruct
 from .vit import FeedForward, LayerNorm, PatchEmbed, TokenLinear
@@ -211,7 +211,9 @@ class Block(SgxBlock):
         return self.norm1.bwd(self.attn.bwd(dt1), addend=d_mid, dx_out=dx_out)
 
 
-class Beit(SgxNetwork):
+class Beit(SgxClassifier):
+    _head_path = _finetune_key = "head"
+
     def __init__(self, image_size=(224, 224), patch_size=16, in_chans=3, num_classes=1000, global_pool="avg", embed_dim=768, depth=12, num_heads=12,
                  mlp_ratio=4.0, qkv_bias=True, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, init_values=None, use_abs_pos_emb=True,
                  use_rel_pos_bias=False, use_shared_rel_pos_bias=False, head_init_scale=0.001, **kwargs):
@@ -292,14 +294,12 @@ class Beit(SgxNetwork):
 
     # ---- forward / backward --------------------------------------------------------------------------------------
     def _fwd(self, img):
-        cin = self.get_input_channels()
-        if img.dim() != 4 or img.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(img.shape)}")
+        xh = self._input_nhwc(img)
         if tuple(img.shape[2:]) != self.image_size:
             _not_built(f"the model was built for {self.image_size} images and received {tuple(img.shape[2:])}")
         if self.training and self.drop_rate > 0:
             _not_built(f"drop_rate = {self.drop_rate} in training mode (the recipes use 0; eval is the identity and works)")
-        x = K.token_assemble_fwd(self.patch_embed.fwd(K.input_to_nhwc(img)), self.cls_token, self.pos_embed)
+        x = K.token_assemble_fwd(self.patch_embed.fwd(xh), self.cls_token, self.pos_embed)
         shared = self.rel_pos_bias.relative_position_bias_table if self.rel_pos_bias is not None else None
         grid = self.patch_embed.grid_size
         for blk in self.blocks:
@@ -343,9 +343,6 @@ class Beit(SgxNetwork):
                (["rel_pos_bias."] if self.rel_pos_bias is not None else []) + [f"blocks.{i}." for i in range(len(self.blocks))] + \
                ["fc_norm." if self.fc_norm is not None else "norm.", "head."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     def prep_model_for_conversion(self, input_size=None, **kwargs):
         """Nothing folds: no BatchNorm, no re-parameterised branch."""
         return self
@@ -366,14 +363,8 @@ class Beit(SgxNetwork):
     def get_classifier(self):
         return self.head
 
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            _not_built("replace_head(new_head=...) is not available; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.head = LinearLayer(self.head.in_features, new_num_classes)  # (nn.Linear's default distribution, as the reference's replacement)
+    def _new_head(self, new_num_classes):
+        super()._new_head(new_num_classes)  # (nn.Linear's default distribution, as the reference's replacement)
         self.num_classes = new_num_classes
 
     def replace_input_channels(self, in_channels: int, compute_new_weights_fn=None):
@@ -385,9 +376,6 @@ class Beit(SgxNetwork):
 
     def get_input_channels(self) -> int:
         return self.patch_embed.get_input_channels()
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"head": lr, "default": 0.0}
 
 
 def _variant(name, cls_name, **defaults):

@@ -26,22 +26,16 @@ norm1's backward ADDED into the prefix (sgx_dense_bn_bwd_apply).
 Not built (each raises NotImplementedError): growth_rate, num_init_features, bn_size * growth_rate or a transition's halved width that is
 not a multiple of 4 (16-byte channel groups); replace_head(new_head=...); half-precision inference.
 """
-from typing import Dict
-
 import torch
 from torch import nn
 
 from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import ConvBNView
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.engine import SgxBlock
+from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool, need_mult4
 from ...utils.utils import get_param
-
-
-def _need_mult4(what, n):
-    if n % 4:
-        raise NotImplementedError(f"DenseNet on the HIP path: {what} must be a multiple of 4 (16-byte channel groups), got {n}")
 
 
 class _Record:
@@ -72,9 +66,9 @@ class DenseLayer(SgxBlock):
 
     def __init__(self, num_input_features, growth_rate, bn_size, drop_rate):
         super().__init__()
-        _need_mult4("a dense layer's input width", num_input_features)
-        _need_mult4("growth_rate", growth_rate)
-        _need_mult4("bn_size * growth_rate", bn_size * growth_rate)
+        need_mult4("DenseNet", "a dense layer's input width", num_input_features)
+        need_mult4("DenseNet", "growth_rate", growth_rate)
+        need_mult4("DenseNet", "bn_size * growth_rate", bn_size * growth_rate)
         self.norm1 = BatchNorm(num_input_features)
         self.conv1 = ConvLayer(num_input_features, bn_size * growth_rate, 1, 1, 0, bias=False)
         self.norm2 = BatchNorm(bn_size * growth_rate)
@@ -216,8 +210,8 @@ class Transition(SgxBlock):
 
     def __init__(self, num_input_features, num_output_features):
         super().__init__()
-        _need_mult4("a transition's input width", num_input_features)
-        _need_mult4("a transition's output width (half its input)", num_output_features)
+        need_mult4("DenseNet", "a transition's input width", num_input_features)
+        need_mult4("DenseNet", "a transition's output width (half its input)", num_output_features)
         self.norm = BatchNorm(num_input_features)
         self.conv = ConvLayer(num_input_features, num_output_features, 1, 1, 0, bias=False)
 
@@ -254,11 +248,13 @@ class _Features(nn.Module):
     """Namespace with the child names of the reference's nn.Sequential `features`."""
 
 
-class DenseNet(SgxNetwork):
+class DenseNet(SgxClassifier):
+    _head_path = _finetune_key = "classifier"
+
     def __init__(self, growth_rate: int, structure: list, num_init_features: int, bn_size: int, drop_rate: float, num_classes: int, in_channels: int = 3):
         super().__init__()
-        _need_mult4("num_init_features", num_init_features)
-        _need_mult4("growth_rate", growth_rate)
+        need_mult4("DenseNet", "num_init_features", num_init_features)
+        need_mult4("DenseNet", "growth_rate", growth_rate)
         f = self.features = _Features()
         f.add_module("conv0", ConvLayer(in_channels, num_init_features, 7, 2, 3, bias=False))
         f.add_module("norm0", BatchNorm(num_init_features))
@@ -288,11 +284,8 @@ class DenseNet(SgxNetwork):
                 nn.init.constant_(m.bias, 0)
 
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
         f = self.features._modules
-        a = self.stem.fwd(K.input_to_nhwc(x))
+        a = self.stem.fwd(self._input_nhwc(x))
         # every block's input is written into the first slice of its concat buffer by its producer, whose statistics open the record
         n, h, w = a.shape[0], (a.shape[1] - 1) // 2 + 1, (a.shape[2] - 1) // 2 + 1  # (the 3x3 / 2 max-pool with padding 1)
         blk = f[self._order[0][1]]
@@ -317,15 +310,13 @@ class DenseNet(SgxNetwork):
         n5 = f["norm5"]
         sc, sh, mean, invstd = n5.scale_shift_record(rec, self.num_features, self.training)
         self._tail = (buf, sc, sh, mean, invstd) if self.training else None
-        pooled = K.avgpool_fwd(K.affine_act(buf, sc, sh, act="relu"))  # (F.relu, then adaptive_avg_pool2d(1))
-        return (self.classifier.fwd(pooled).contiguous(),)
+        return (self._pool_head_fwd(K.affine_act(buf, sc, sh, act="relu"), self.classifier),)  # (F.relu, then adaptive_avg_pool2d(1))
 
     def _bwd(self, d_logits):
         f = self.features._modules
         ready = self._bucket_ready
         (buf, sc, sh, mean, invstd), self._tail = self._tail, None
-        d = self.classifier.bwd(d_logits.contiguous())
-        d = K.avgpool_bwd(d.contiguous(), tuple(buf.shape))
+        d = self._pool_head_bwd(d_logits, self.classifier)
         ready("classifier.")
         # norm5's backward writes the last block's whole gradient buffer
         dbuf = f["norm5"].backward(d, buf, sc, sh, mean, invstd, "relu")
@@ -345,29 +336,13 @@ class DenseNet(SgxNetwork):
         """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
         return ["features.conv0.", "features.norm0."] + [f"features.{name}." for _, name in self._order] + ["features.norm5.", "classifier."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
     def get_input_channels(self) -> int:
         return self.features._modules["conv0"].in_channels
 
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.classifier = LinearLayer(self.num_features, new_num_classes)
+    def _new_head(self, new_num_classes):
+        super()._new_head(new_num_classes)
         nn.init.constant_(self.classifier.bias, 0)
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"classifier": lr, "default": 0.0}
-
-
-def _nc(arch_params, num_classes):
-    return num_classes or get_param(arch_params, "num_classes")
 
 
 @register_model("custom_densenet")
@@ -375,12 +350,12 @@ class CustomizedDensnet(DenseNet):  # (the reference's spelling)
     def __init__(self, arch_params, num_classes=None):
         super().__init__(growth_rate=get_param(arch_params, "growth_rate", 32), structure=get_param(arch_params, "structure", [6, 12, 24, 16]),
                          num_init_features=get_param(arch_params, "num_init_features", 64), bn_size=get_param(arch_params, "bn_size", 4),
-                         drop_rate=get_param(arch_params, "drop_rate", 0), num_classes=_nc(arch_params, num_classes))
+                         drop_rate=get_param(arch_params, "drop_rate", 0), num_classes=num_classes_of(arch_params, num_classes))
 
 
 def _densenet(name, growth_rate, structure, num_init_features):
     def init(self, arch_params, num_classes=None):
-        DenseNet.__init__(self, growth_rate, structure, num_init_features, 4, 0, _nc(arch_params, num_classes))
+        DenseNet.__init__(self, growth_rate, structure, num_init_features, 4, 0, num_classes_of(arch_params, num_classes))
 
     return register_model(name)(type(name.replace("densenet", "DenseNet"), (DenseNet,), {"__init__": init}))
 

@@ -42,7 +42,7 @@ import collections
 import math
 import re
 from collections import OrderedDict
-from typing import Dict, List
+from typing import List
 
 import torch
 from torch import nn
@@ -50,8 +50,9 @@ from torch import nn
 from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import ConvBNView
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, LinearLayer
+from ....modules.classifier import SgxClassifier
+from ....modules.engine import SgxBlock
+from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, Dropout, LinearLayer, need_mult4, widen_conv_input
 from ....modules.se_blocks import MBConvSE, _SEConv
 from ...utils.utils import HpmStruct, get_param
 
@@ -123,11 +124,6 @@ class BlockDecoder(object):
         return [BlockDecoder._encode_block_string(b) for b in blocks_args]
 
 
-def _need_mult4(what, n):
-    if n % 4:
-        raise NotImplementedError(f"EfficientNet on the HIP path: {what} must be a multiple of 4 (16-byte channel groups), got {n}")
-
-
 def _int_stride(stride):
     return stride if isinstance(stride, int) else stride[0]
 
@@ -174,9 +170,9 @@ class MBConvBlock(SgxBlock):
         k, s = block_args.kernel_size, _int_stride(block_args.stride)
         if k not in (3, 5):
             raise NotImplementedError(f"EfficientNet on the HIP path: depthwise kernel size 3 or 5, got {k}")
-        _need_mult4("block input width", inp)
-        _need_mult4("expanded width", oup)
-        _need_mult4("block output width", final_oup)
+        need_mult4("EfficientNet", "block input width", inp)
+        need_mult4("EfficientNet", "expanded width", oup)
+        need_mult4("EfficientNet", "block output width", final_oup)
         self._pad = _SamePad(f"{name}._depthwise_conv", k, s, image_size)
         bn = lambda c: BatchNorm(c, eps=self._bn_eps, momentum=self._bn_mom)  # noqa: E731
         self._pw = None
@@ -253,15 +249,9 @@ class MBConvBlock(SgxBlock):
         return self._pw.bwd(d, dx_out=dx_out, accumulate=accumulate, addend=res, need_dx=need_dx)
 
 
-class _Dropout(nn.Module):
-    """The reference's nn.Dropout at _dropout: no state; `p` may be set by the user."""
+class EfficientNet(SgxClassifier):
+    _head_path = _finetune_key = "_fc"
 
-    def __init__(self, p):
-        super().__init__()
-        self.p = float(p)
-
-
-class EfficientNet(SgxNetwork):
     def __init__(self, width_coefficient, depth_coefficient, image_size, dropout_rate, num_classes, batch_norm_momentum=0.99, batch_norm_epsilon=1e-3,
                  drop_connect_rate=0.2, depth_divisor=8, min_depth=None, backbone_mode=False, blocks_args=None):
         super().__init__()
@@ -274,7 +264,7 @@ class EfficientNet(SgxNetwork):
         rf = lambda f: round_filters(f, width_coefficient, depth_divisor, min_depth)  # noqa: E731
 
         out_channels = rf(32)
-        _need_mult4("the stem width", out_channels)
+        need_mult4("EfficientNet", "the stem width", out_channels)
         self._stem_pad = _SamePad("_conv_stem", 3, 2, image_size)
         self._conv_stem = ConvLayer(3, out_channels, 3, 2, 1, bias=False)
         self._bn0 = BatchNorm(out_channels, eps=bn_eps, momentum=bn_mom)
@@ -294,23 +284,21 @@ class EfficientNet(SgxNetwork):
 
         in_channels = block_args.output_filters
         out_channels = rf(1280)
-        _need_mult4("the head width", out_channels)
+        need_mult4("EfficientNet", "the head width", out_channels)
         self._conv_head = ConvLayer(in_channels, out_channels, 1, 1, 0, bias=False)
         self._bn1 = BatchNorm(out_channels, eps=bn_eps, momentum=bn_mom)
         self._head_channels = out_channels
         if not self.backbone_mode:
-            self._dropout = _Dropout(dropout_rate)
+            self._dropout = Dropout(dropout_rate)
             self._fc = LinearLayer(out_channels, num_classes)
         self._stem = ConvBNView(self._conv_stem, self._bn0, "silu")
         self._head = ConvBNView(self._conv_head, self._bn1, "silu")
 
     # ---- forward / backward --------------------------------------------------------------------------------------
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
+        xh = self._input_nhwc(x)
         self._stem_pad.check(x.shape[2], x.shape[3])
-        a = self._stem.fwd(K.input_to_nhwc(x))
+        a = self._stem.fwd(xh)
         nb = len(self._blocks)
         for idx, blk in enumerate(self._blocks):
             rate = self.drop_connect_rate
@@ -320,26 +308,14 @@ class EfficientNet(SgxNetwork):
         a = self._head.fwd(a)
         if self.backbone_mode:
             return (K.nhwc_to_nchw(a),)
-        self._feat_shape = tuple(a.shape)
-        pooled = K.avgpool_fwd(a)
-        p = float(self._dropout.p)
-        self._drop = None
-        if self.training and p > 0:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's default generator: torch.manual_seed repeats a step
-            self._drop = (seed, p)
-            pooled = K.dropout(pooled, p, seed)
-        return (self._fc.fwd(pooled).contiguous(),)
+        return (self._pool_head_fwd(a, self._fc, self._dropout.p),)
 
     def _bwd(self, d_out):
         ready = self._bucket_ready
         if self.backbone_mode:
             d = K.nchw_to_nhwc(d_out)
         else:
-            d = self._fc.bwd(d_out.contiguous()).contiguous()
-            if self._drop is not None:
-                (seed, p), self._drop = self._drop, None
-                d = K.dropout(d, p, seed, out=d)  # the same mask, regenerated
-            d = K.avgpool_bwd(d, self._feat_shape)
+            d = self._pool_head_bwd(d_out, self._fc)
             ready("_fc.")
         d = self._head.bwd(d)
         ready("_bn1.")
@@ -355,36 +331,13 @@ class EfficientNet(SgxNetwork):
         """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
         return ["_conv_stem.", "_bn0."] + [f"_blocks.{i}." for i in range(len(self._blocks))] + ["_conv_head.", "_bn1.", "_fc."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self._fc = LinearLayer(self._fc.in_features, new_num_classes)
-
     def replace_input_channels(self, in_channels: int, compute_new_weights_fn=None):
         """Reference :542-545 with modules/weight_replacement_utils.py: the stem keeps the weights of the channels it already has; extra
         channels are drawn from a normal distribution with the old weights' mean / std.  Before materialisation only."""
         if self._materialized:
             raise RuntimeError("replace_input_channels must be called before the model is materialized in HBM (before the first forward)")
-        old = self._conv_stem
-        if compute_new_weights_fn is not None:
-            new = compute_new_weights_fn(old, in_channels)
-        else:
-            new = ConvLayer(in_channels, old.out_channels, old.kernel_size, old.stride, old.padding, bias=False)
-            w = old.weight.data
-            if in_channels <= old.in_channels:
-                new.weight.data = w[:, :in_channels].clone()
-            else:
-                new.weight.data[:, : old.in_channels] = w
-                torch.nn.init.normal_(new.weight.data[:, old.in_channels:], mean=float(w.mean()), std=float(w.std()))
-        self._conv_stem = new
+        self._conv_stem = widen_conv_input(self._conv_stem, in_channels, compute_new_weights_fn)
         self._stem = ConvBNView(self._conv_stem, self._bn0, "silu")
 
     def get_input_channels(self) -> int:
@@ -400,9 +353,6 @@ class EfficientNet(SgxNetwork):
             sd.popitem()
             sd = OrderedDict((name.split("module.")[1], v) for name, v in sd.items())
         return super().load_state_dict(sd, strict, **kw)
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"_fc": lr, "default": 0.0}
 
 
 BLOCK_STRINGS = ["r1_k3_s11_e1_i32_o16_se0.25", "r2_k3_s22_e6_i16_o24_se0.25", "r2_k5_s22_e6_i24_o40_se0.25", "r3_k3_s22_e6_i40_o80_se0.25",

@@ -18,15 +18,12 @@ that are not multiples of 4 (16-byte channel groups); dropout > 0 in training mo
 replace_head(new_head=...).
 """
 import math
-from typing import Dict
 
-from torch import nn
-
-from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import ConvBNSeq, ConvBNView
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, LinearLayer
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.engine import SgxBlock
+from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, LinearLayer, Numbered, init_normal_fan_out, need_mult4
 from ...utils.utils import get_param
 
 DEFAULT_STRUCTURE = [
@@ -45,23 +42,6 @@ def make_divisible(x, divisible_by=8):
     return int(math.ceil(x * 1.0 / divisible_by) * divisible_by)
 
 
-class _Numbered(nn.Module):
-    """Namespace with the numeric child names of a reference nn.Sequential."""
-
-    def __init__(self, **children):
-        super().__init__()
-        for name, m in children.items():
-            self.add_module(name, m)
-
-    def blocks(self):
-        return list(self._modules.values())
-
-
-def _need_mult4(what, n):
-    if n % 4:
-        raise NotImplementedError(f"MobileNetV2 on the HIP path: {what} must be a multiple of 4 (16-byte channel groups), got {n}")
-
-
 class InvertedResidual(SgxBlock):
     """Reference InvertedResidual: [1x1 expand, BN, ReLU6,] depthwise 3x3, BN, ReLU6, 1x1 project, BN - keys conv.{0..7} ({0..4} for t == 1)."""
 
@@ -71,9 +51,9 @@ class InvertedResidual(SgxBlock):
         if grouped_conv_size != 1:
             raise NotImplementedError("MobileNetV2 on the HIP path: grouped_conv_size=1 (depthwise); grouped convolutions are not built")
         hidden = int(inp * expand_ratio)
-        _need_mult4("block input width", inp)
-        _need_mult4("hidden width", hidden)
-        _need_mult4("block output width", oup)
+        need_mult4("MobileNetV2", "block input width", inp)
+        need_mult4("MobileNetV2", "hidden width", hidden)
+        need_mult4("MobileNetV2", "block output width", oup)
         self.stride = stride
         self.use_res_connect = stride == 1 and inp == oup
         if expand_ratio == 1:
@@ -83,7 +63,7 @@ class InvertedResidual(SgxBlock):
             layers = {"0": ConvLayer(inp, hidden, 1, 1, 0), "1": BatchNorm(hidden), "3": DepthwiseConvLayer(hidden, stride), "4": BatchNorm(hidden),
                       "6": ConvLayer(hidden, oup, 1, 1, 0), "7": BatchNorm(oup)}
             pw, dw, pwl = ("0", "1"), ("3", "4"), ("6", "7")
-        self.conv = _Numbered(**layers)
+        self.conv = Numbered(**layers)
         # the conv -> BatchNorm -> activation sequences over those layers (they own no parameter: nothing is added to the state)
         self.pw = ConvBNView(layers[pw[0]], layers[pw[1]], "relu6") if pw else None
         self.dw = ConvBNView(layers[dw[0]], layers[dw[1]], "relu6")
@@ -108,7 +88,9 @@ class InvertedResidual(SgxBlock):
         return first.bwd(d, dx_out=dx_out, accumulate=accumulate, addend=res, need_dx=need_dx)
 
 
-class MobileNetV2(SgxNetwork):
+class MobileNetV2(SgxClassifier):
+    _head_path, _finetune_key = "classifier.1", "classifier"
+
     def __init__(self, num_classes, dropout: float, width_mult=1.0, structure=None, backbone_mode: bool = False, grouped_conv_size=1, in_channels=3):
         super().__init__()
         if backbone_mode:
@@ -126,41 +108,22 @@ class MobileNetV2(SgxNetwork):
             for i in range(n):
                 feats.append(InvertedResidual(curr, oup, s if i == 0 else 1, expand_ratio=t, grouped_conv_size=grouped_conv_size))
                 curr = oup
-        _need_mult4("the last block's width", curr)
+        need_mult4("MobileNetV2", "the last block's width", curr)
         feats.append(ConvBNSeq(curr, self.last_channel, 1, stride=1, padding=0, activation_type="relu6"))
-        self.features = _Numbered(**{str(i): f for i, f in enumerate(feats)})
-        self.classifier = _Numbered(**{"1": LinearLayer(self.last_channel, num_classes)})  # ("0" is the reference's nn.Dropout: no state)
-        self._initialize_weights()
-
-    def _initialize_weights(self):
-        """Reference :180-193: conv weights N(0, sqrt(2 / (k * k * out_channels))), BatchNorm 1 / 0, linear N(0, 0.01) with zero bias."""
-        for m in self.modules():
-            if isinstance(m, (ConvLayer, DepthwiseConvLayer)):
-                m.weight.data.normal_(0, math.sqrt(2.0 / (m.kernel_size * m.kernel_size * m.out_channels)))
-            elif isinstance(m, BatchNorm):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
-            elif isinstance(m, LinearLayer):
-                m.weight.data.normal_(0, 0.01)
-                m.bias.data.zero_()
+        self.features = Numbered(feats)
+        self.classifier = Numbered(**{"1": LinearLayer(self.last_channel, num_classes)})  # ("0" is the reference's nn.Dropout: no state)
+        init_normal_fan_out(self, (ConvLayer, DepthwiseConvLayer))  # (reference :180-193)
 
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
+        a = self._input_nhwc(x)
         if self.training and self.dropout > 0:
             raise NotImplementedError("MobileNetV2 on the HIP path: dropout > 0 is not built for training (eval mode is the identity and works)")
-        a = K.input_to_nhwc(x)
         for f in self.features.blocks():
             a = f.fwd(a)
-        self._feat_shape = tuple(a.shape)
-        pooled = K.avgpool_fwd(a)  # (the reference's x.mean(3).mean(2))
-        logits = self.classifier._modules["1"].fwd(pooled)
-        return (logits.contiguous(),)
+        return (self._pool_head_fwd(a, self.classifier._modules["1"]),)  # (the pool: the reference's x.mean(3).mean(2))
 
     def _bwd(self, d_logits):
-        d = self.classifier._modules["1"].bwd(d_logits.contiguous())
-        d = K.avgpool_bwd(d.contiguous(), self._feat_shape)
+        d = self._pool_head_bwd(d_logits, self.classifier._modules["1"])
         ready = self._bucket_ready
         ready("classifier.")
         feats = self.features.blocks()
@@ -174,43 +137,28 @@ class MobileNetV2(SgxNetwork):
         """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
         return [f"features.{i}." for i in range(len(self.features.blocks()))] + ["classifier."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
     def get_input_channels(self) -> int:
         return self.features._modules["0"]._modules["0"].in_channels
-
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.classifier.add_module("1", LinearLayer(self.last_channel, new_num_classes))
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"classifier": lr, "default": 0.0}
 
 
 @register_model("mobilenet_v2")
 class MobileNetV2Base(MobileNetV2):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(num_classes=num_classes or get_param(arch_params, "num_classes"), width_mult=1.0, structure=None,
+        super().__init__(num_classes=num_classes_of(arch_params, num_classes), width_mult=1.0, structure=None,
                          dropout=get_param(arch_params, "dropout", 0.0), in_channels=get_param(arch_params, "in_channels", 3))
 
 
 @register_model("mobile_net_v2_135")
 class MobileNetV2_135(MobileNetV2):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(num_classes=num_classes or get_param(arch_params, "num_classes"), width_mult=1.35, structure=None,
+        super().__init__(num_classes=num_classes_of(arch_params, num_classes), width_mult=1.35, structure=None,
                          dropout=get_param(arch_params, "dropout", 0.0), in_channels=get_param(arch_params, "in_channels", 3))
 
 
 @register_model("custom_mobilenet_v2")
 class CustomMobileNetV2(MobileNetV2):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(num_classes=num_classes or get_param(arch_params, "num_classes"), width_mult=get_param(arch_params, "width_mult"),
+        super().__init__(num_classes=num_classes_of(arch_params, num_classes), width_mult=get_param(arch_params, "width_mult"),
                          structure=get_param(arch_params, "structure"), dropout=get_param(arch_params, "dropout", 0.0),
                          in_channels=get_param(arch_params, "in_channels", 3))

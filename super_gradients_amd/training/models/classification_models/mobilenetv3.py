@@ -19,20 +19,17 @@ followed by the gate sweep without scale / shift.
 
 Not built (each raises NotImplementedError): widths that are not multiples of 4; kernel sizes other than 3 / 5; replace_head(new_head=...).
 """
-import math
-from typing import Dict
-
 import torch
-from torch import nn
 
 from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import ConvBNSeq, ConvBNView
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, LinearLayer
+from ....modules.classifier import SgxClassifier, dropout_seed, num_classes_of
+from ....modules.engine import SgxBlock
+from ....modules.layers import (BatchNorm, ConvLayer, DepthwiseConvLayer, Dropout, LinearLayer, Numbered, init_normal_fan_out,
+                                 need_mult4)
 from ....modules.se_blocks import SELayer, _make_divisible
 from ...utils.utils import get_param
-from .mobilenetv2 import _Numbered
 
 LARGE_CFGS = [
     # k, t, c, SE, HS, s
@@ -46,11 +43,6 @@ SMALL_CFGS = [
 ]
 
 
-def _need_mult4(what, n):
-    if n % 4:
-        raise NotImplementedError(f"MobileNetV3 on the HIP path: {what} must be a multiple of 4 (16-byte channel groups), got {n}")
-
-
 class InvertedResidual(SgxBlock):
     """Reference InvertedResidual, both layouts: inp == hidden_dim: dw, BN, act, SE, 1x1, BN (keys conv.{0,1,3,4,5}); otherwise 1x1, BN, act,
     dw, BN, SE, act, 1x1, BN (keys conv.{0,1,3,4,5,7,8})."""
@@ -60,9 +52,9 @@ class InvertedResidual(SgxBlock):
         assert stride in (1, 2)
         if kernel_size not in (3, 5):
             raise NotImplementedError(f"MobileNetV3 on the HIP path: depthwise kernel size 3 or 5, got {kernel_size}")
-        _need_mult4("block input width", inp)
-        _need_mult4("hidden width", hidden_dim)
-        _need_mult4("block output width", oup)
+        need_mult4("MobileNetV3", "block input width", inp)
+        need_mult4("MobileNetV3", "hidden width", hidden_dim)
+        need_mult4("MobileNetV3", "block output width", oup)
         self.stride = stride
         self.identity = stride == 1 and inp == oup
         act = "hswish" if use_hs else "relu"
@@ -72,7 +64,7 @@ class InvertedResidual(SgxBlock):
             layers = {"0": dw, "1": BatchNorm(hidden_dim), "4": ConvLayer(hidden_dim, oup, 1, 1, 0), "5": BatchNorm(oup)}
             if se is not None:
                 layers["3"] = se
-            self.conv = _Numbered(**{k: layers[k] for k in sorted(layers)})
+            self.conv = Numbered(**{k: layers[k] for k in sorted(layers)})
             self.pw = None
             self.dw = ConvBNView(layers["0"], layers["1"], act)
             self.se_after = se
@@ -82,7 +74,7 @@ class InvertedResidual(SgxBlock):
                       "7": ConvLayer(hidden_dim, oup, 1, 1, 0), "8": BatchNorm(oup)}
             if se is not None:
                 layers["5"] = se
-            self.conv = _Numbered(**{k: layers[k] for k in sorted(layers)})
+            self.conv = Numbered(**{k: layers[k] for k in sorted(layers)})
             self.pw = ConvBNView(layers["0"], layers["1"], act)
             self.dw = ConvBNView(layers["3"], layers["4"], act, gate=se)
             self.se_after = None
@@ -117,15 +109,9 @@ class InvertedResidual(SgxBlock):
         return first.bwd(d, dx_out=dx_out, accumulate=accumulate, addend=res, need_dx=need_dx)
 
 
-class _Dropout(nn.Module):
-    """The reference's nn.Dropout(0.2) at classifier.2: no state; `p` may be set by the user."""
+class MobileNetV3(SgxClassifier):
+    _head_path, _finetune_key = "classifier.3", "classifier"
 
-    def __init__(self, p):
-        super().__init__()
-        self.p = float(p)
-
-
-class MobileNetV3(SgxNetwork):
     def __init__(self, cfgs, mode, num_classes=1000, width_mult=1.0, in_channels: int = 3):
         super().__init__()
         self.cfgs = cfgs
@@ -138,32 +124,17 @@ class MobileNetV3(SgxNetwork):
             exp_size = _make_divisible(curr * t, 8)
             feats.append(InvertedResidual(curr, exp_size, oup, k, s, use_se, use_hs))
             curr = oup
-        _need_mult4("the last block's width", curr)
-        self.features = _Numbered(**{str(i): f for i, f in enumerate(feats)})
+        need_mult4("MobileNetV3", "the last block's width", curr)
+        self.features = Numbered(feats)
         self.conv = ConvBNSeq(curr, exp_size, 1, stride=1, padding=0, activation_type="hswish")
         last = {"large": 1280, "small": 1024}[mode]
         self.last_channel = _make_divisible(last * width_mult, 8) if width_mult > 1.0 else last
         self.exp_size = exp_size
-        self.classifier = _Numbered(**{"0": LinearLayer(exp_size, self.last_channel), "2": _Dropout(0.2), "3": LinearLayer(self.last_channel, num_classes)})
-        self._initialize_weights()
-
-    def _initialize_weights(self):
-        """Reference :161-174: conv weights N(0, sqrt(2 / (k * k * out_channels))), BatchNorm 1 / 0, linear N(0, 0.01) with zero bias."""
-        for m in self.modules():
-            if isinstance(m, (ConvLayer, DepthwiseConvLayer)):
-                m.weight.data.normal_(0, math.sqrt(2.0 / (m.kernel_size * m.kernel_size * m.out_channels)))
-            elif isinstance(m, BatchNorm):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
-            elif isinstance(m, LinearLayer):
-                m.weight.data.normal_(0, 0.01)
-                m.bias.data.zero_()
+        self.classifier = Numbered(**{"0": LinearLayer(exp_size, self.last_channel), "2": Dropout(0.2), "3": LinearLayer(self.last_channel, num_classes)})
+        init_normal_fan_out(self, (ConvLayer, DepthwiseConvLayer))  # (reference :161-174)
 
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
-        a = K.input_to_nhwc(x)
+        a = self._input_nhwc(x)
         for f in self.features.blocks():
             a = f.fwd(a)
         a = self.conv.fwd(a)
@@ -174,12 +145,10 @@ class MobileNetV3(SgxNetwork):
         h = cls["0"].fwd(pooled).contiguous().view(n, 1, 1, self.last_channel)
         a = K.affine_act(h, act="hswish")
         p = float(cls["2"].p)
-        self._cls = None
-        if self.training:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else None  # torch's default generator: torch.manual_seed repeats a step
-            self._cls = (h, seed, p)
-            if seed is not None:
-                a = K.dropout(a, p, seed)
+        seed = dropout_seed(self.training, p)
+        self._cls = (h, seed, p) if self.training else None
+        if seed is not None:
+            a = K.dropout(a, p, seed)
         logits = cls["3"].fwd(a.view(n, self.last_channel))
         return (logits.contiguous(),)
 
@@ -210,37 +179,22 @@ class MobileNetV3(SgxNetwork):
         """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
         return [f"features.{i}." for i in range(len(self.features.blocks()))] + ["conv.", "classifier."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
     def get_input_channels(self) -> int:
         return self.features._modules["0"]._modules["0"].in_channels
-
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.classifier.add_module("3", LinearLayer(self.last_channel, new_num_classes))
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"classifier": lr, "default": 0.0}
 
 
 @register_model("mobilenet_v3_large")
 class mobilenetv3_large(MobileNetV3):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__([list(r) for r in LARGE_CFGS], mode="large", num_classes=num_classes or get_param(arch_params, "num_classes"),
+        super().__init__([list(r) for r in LARGE_CFGS], mode="large", num_classes=num_classes_of(arch_params, num_classes),
                          width_mult=get_param(arch_params, "width_mult", 1.0), in_channels=get_param(arch_params, "in_channels", 3))
 
 
 @register_model("mobilenet_v3_small")
 class mobilenetv3_small(MobileNetV3):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__([list(r) for r in SMALL_CFGS], mode="small", num_classes=num_classes or get_param(arch_params, "num_classes"),
+        super().__init__([list(r) for r in SMALL_CFGS], mode="small", num_classes=num_classes_of(arch_params, num_classes),
                          width_mult=get_param(arch_params, "width_mult", 1.0), in_channels=get_param(arch_params, "in_channels", 3))
 
 
@@ -248,5 +202,5 @@ class mobilenetv3_small(MobileNetV3):
 class mobilenetv3_custom(MobileNetV3):
     def __init__(self, arch_params, num_classes=None):
         super().__init__(cfgs=get_param(arch_params, "structure"), mode=get_param(arch_params, "mode"),
-                         num_classes=num_classes or get_param(arch_params, "num_classes"), width_mult=get_param(arch_params, "width_mult"),
+                         num_classes=num_classes_of(arch_params, num_classes), width_mult=get_param(arch_params, "width_mult"),
                          in_channels=get_param(arch_params, "in_channels", 3))

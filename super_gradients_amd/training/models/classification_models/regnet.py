@@ -20,27 +20,18 @@ act(gconv + bias) launch, the last 1x1 takes the shortcut as its addend and the 
 Not built (each raises NotImplementedError): droppath_prob > 0 (DropPath), replace_head(new_head=...), grouped layers whose channels per
 group are outside the kernels' set.
 """
-from math import sqrt
-from typing import Dict
-
 import numpy as np
-import torch
 from torch import nn
 
 from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import Conv, ConvBNSeq
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, GroupedConvLayer, LinearLayer
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.engine import SgxBlock
+from ....modules.layers import (ConvLayer, DepthwiseConvLayer, Dropout, GroupedConvLayer, LinearLayer, Numbered, init_normal_fan_out,
+                                 widen_conv_input)
 from ....modules.se_blocks import ConvSqueezeExcite, _SEConv
 from ...utils.utils import get_param
-
-
-class _Named(nn.Module):
-    """Namespace whose children carry the reference's names (net.stem, net.stage_0, blocks.block_0 ...)."""
-
-    def children_list(self):
-        return list(self._modules.values())
 
 
 class SqueezeExcite(ConvSqueezeExcite):
@@ -124,18 +115,10 @@ class XBlock(SgxBlock):
 class Stage(nn.Module):
     def __init__(self, num_blocks, in_channels, out_channels, bottleneck_ratio, group_width, stride, se_ratio, droppath_prob):
         super().__init__()
-        self.blocks = _Named()
+        self.blocks = Numbered()
         self.blocks.add_module("block_0", XBlock(in_channels, out_channels, bottleneck_ratio, group_width, stride, se_ratio, droppath_prob))
         for i in range(1, num_blocks):
             self.blocks.add_module("block_{}".format(i), XBlock(out_channels, out_channels, bottleneck_ratio, group_width, 1, se_ratio, droppath_prob))
-
-
-class _Dropout(nn.Module):
-    """The reference's nn.Dropout at head.dropout: no state."""
-
-    def __init__(self, p):
-        super().__init__()
-        self.p = float(p)
 
 
 class Head(nn.Module):
@@ -143,18 +126,20 @@ class Head(nn.Module):
 
     def __init__(self, num_channels, num_classes, dropout_prob):
         super().__init__()
-        self.dropout = _Dropout(dropout_prob)
+        self.dropout = Dropout(dropout_prob)
         self.fc = LinearLayer(num_channels, num_classes)
 
 
-class AnyNetX(SgxNetwork):
+class AnyNetX(SgxClassifier):
+    _head_path, _finetune_key = "net.head.fc", "net.head"
+
     def __init__(self, ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width, stride, num_classes, se_ratio, backbone_mode,
                  dropout_prob=0.0, droppath_prob=0.0, input_channels=3):
         super().__init__()
         if droppath_prob:
             raise NotImplementedError("DropPath (droppath_prob > 0) is not on the HIP path")
         verify_correctness_of_parameters(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width)
-        self.net = _Named()
+        self.net = Numbered()  # (children carry the reference's names: net.stem, net.stage_0 ..., net.head)
         self.backbone_mode = backbone_mode
         prev_block_width = 32
         self.net.add_module("stem", Stem(in_channels=input_channels, out_channels=prev_block_width))
@@ -171,49 +156,26 @@ class AnyNetX(SgxNetwork):
     def initialize_weight(self):
         """Reference :157-167: conv weights N(0, sqrt(2 / (k * k * out_channels))), BatchNorm 1 / 0, linear N(0, 0.01) with zero bias.
         (The SE convolutions are nn.Conv2d too: the same normal draw; their biases keep nn.Conv2d's default.)"""
-        for m in self.modules():
-            if isinstance(m, (ConvLayer, DepthwiseConvLayer, GroupedConvLayer, _SEConv)):
-                m.weight.data.normal_(mean=0.0, std=sqrt(2.0 / (m.kernel_size * m.kernel_size * m.out_channels)))
-            elif isinstance(m, BatchNorm):
-                m.weight.data.fill_(1.0)
-                m.bias.data.zero_()
-            elif isinstance(m, LinearLayer):
-                m.weight.data.normal_(mean=0.0, std=0.01)
-                m.bias.data.zero_()
+        init_normal_fan_out(self, (ConvLayer, DepthwiseConvLayer, GroupedConvLayer, _SEConv))
 
     def _blocks(self):
         return [(f"net.{sname}.", blk) for sname, st in self.net._modules.items() if isinstance(st, Stage) for blk in st.blocks.children_list()]
 
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
-        a = self.net.stem.fwd(K.input_to_nhwc(x))
+        a = self.net.stem.fwd(self._input_nhwc(x))
         for _, blk in self._blocks():
             a = blk.fwd(a)
         if self.backbone_mode:
             return (K.nhwc_to_nchw(a),)
-        self._feat_shape = tuple(a.shape)
-        pooled = K.avgpool_fwd(a)
         head = self.net.head
-        p = float(head.dropout.p)
-        self._drop = None
-        if self.training and p > 0:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's default generator: torch.manual_seed repeats a step
-            self._drop = (seed, p)
-            pooled = K.dropout(pooled, p, seed)
-        return (head.fc.fwd(pooled).contiguous(),)
+        return (self._pool_head_fwd(a, head.fc, head.dropout.p),)
 
     def _bwd(self, d_out):
         ready = self._bucket_ready
         if self.backbone_mode:
             d = K.nchw_to_nhwc(d_out)
         else:
-            d = self.net.head.fc.bwd(d_out.contiguous()).contiguous()
-            if self._drop is not None:
-                (seed, p), self._drop = self._drop, None
-                d = K.dropout(d, p, seed, out=d)  # the same mask, regenerated
-            d = K.avgpool_bwd(d, self._feat_shape)
+            d = self._pool_head_bwd(d_out, self.net.head.fc)
             ready("net.head.")
         blocks = self._blocks()
         for i in range(len(blocks) - 1, -1, -1):
@@ -228,17 +190,8 @@ class AnyNetX(SgxNetwork):
         """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
         return [f"net.{name}." for name in self.net._modules]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
+    def _new_head(self, new_num_classes):
         head = Head(self.ls_block_width[-1], new_num_classes, self.dropout_prob)
         head.fc.weight.data.normal_(mean=0.0, std=0.01)
         head.fc.bias.data.zero_()
@@ -249,24 +202,10 @@ class AnyNetX(SgxNetwork):
         has; extra channels are drawn from a normal distribution with the old weights' mean / std.  Before materialisation only."""
         if self._materialized:
             raise RuntimeError("replace_input_channels must be called before the model is materialized in HBM (before the first forward)")
-        old = self.net.stem.conv
-        if compute_new_weights_fn is not None:
-            self.net.stem.conv = compute_new_weights_fn(old, in_channels)
-            return
-        new = ConvLayer(in_channels, old.out_channels, old.kernel_size, old.stride, old.padding, bias=False)
-        w = old.weight.data
-        if in_channels <= old.in_channels:
-            new.weight.data = w[:, :in_channels].clone()
-        else:
-            new.weight.data[:, : old.in_channels] = w
-            torch.nn.init.normal_(new.weight.data[:, old.in_channels:], mean=float(w.mean()), std=float(w.std()))
-        self.net.stem.conv = new
+        self.net.stem.conv = widen_conv_input(self.net.stem.conv, in_channels, compute_new_weights_fn)
 
     def get_input_channels(self) -> int:
         return self.net.stem.get_input_channels()
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"net.head": lr, "default": 0}
 
 
 def regnet_params_to_blocks(initial_width, slope, quantized_param, network_depth, bottleneck_ratio, group_width):
@@ -301,7 +240,7 @@ class RegNetX(AnyNetX):
                  input_channels=3, num_classes=None):
         ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width = regnet_params_to_blocks(initial_width, slope, quantized_param, network_depth,
                                                                                                     bottleneck_ratio, group_width)
-        super().__init__(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width, stride, num_classes or get_param(arch_params, "num_classes"), se_ratio,
+        super().__init__(ls_num_blocks, ls_block_width, ls_bottleneck_ratio, ls_group_width, stride, num_classes_of(arch_params, num_classes), se_ratio,
                          get_param(arch_params, "backbone_mode", False), get_param(arch_params, "dropout_prob", 0.0), get_param(arch_params, "droppath_prob", 0.0),
                          input_channels)
 
@@ -331,7 +270,7 @@ class CustomAnyNet(AnyNetX):
         """All parameters must be provided in arch_params other than SE"""
         g = lambda k: get_param(arch_params, k)  # noqa: E731
         super().__init__(ls_num_blocks=g("ls_num_blocks"), ls_block_width=g("ls_block_width"), ls_bottleneck_ratio=g("ls_bottleneck_ratio"),
-                         ls_group_width=g("ls_group_width"), stride=g("stride"), num_classes=num_classes or get_param(arch_params, "num_classes"),
+                         ls_group_width=g("ls_group_width"), stride=g("stride"), num_classes=num_classes_of(arch_params, num_classes),
                          se_ratio=get_param(arch_params, "se_ratio", None), backbone_mode=get_param(arch_params, "backbone_mode", False),
                          dropout_prob=get_param(arch_params, "dropout_prob", 0), droppath_prob=get_param(arch_params, "droppath_prob", 0),
                          input_channels=get_param(arch_params, "input_channels", 3))

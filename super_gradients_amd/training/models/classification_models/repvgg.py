@@ -14,14 +14,11 @@ so its forward fails as soon as a stage changes width; no named variant enables 
 False, and is built without SE exactly as the reference builds it); backbone_mode=True (as for ResNet); stage widths that are not
 multiples of 4 (the sweeps move 16-byte channel groups; every named variant's widths are).
 """
-from typing import Dict
-
 from torch import nn
 
-from .... import kernels as K
 from ....common.registry import register_model
-from ....modules.engine import SgxNetwork
-from ....modules.layers import LinearLayer
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.layers import LinearLayer, Numbered
 from ....modules.repvgg_block import RepVGGBlock, fuse_repvgg_blocks_residual_branches
 from ...utils.utils import get_param
 
@@ -32,19 +29,9 @@ def _training_form_key(key: str) -> bool:
     return any(b in key for b in _BRANCH_KEYS) or key.endswith(".alpha")
 
 
-class _Stage(nn.Module):
-    """nn.Sequential of blocks (keys stage{i}.{j}.*)."""
+class RepVGG(SgxClassifier):
+    _head_path = _finetune_key = "linear"
 
-    def __init__(self, blocks):
-        super().__init__()
-        for i, b in enumerate(blocks):
-            self.add_module(str(i), b)
-
-    def blocks(self):
-        return list(self._modules.values())
-
-
-class RepVGG(SgxNetwork):
     def __init__(self, struct, num_classes=1000, width_multiplier=None, build_residual_branches=True, use_se=False, backbone_mode=False, in_channels=3):
         """
         :param struct: number of blocks per stage
@@ -84,16 +71,13 @@ class RepVGG(SgxNetwork):
             blocks.append(RepVGGBlock(self.in_planes, planes, stride=s, groups=1, build_residual_branches=self.build_residual_branches,
                                       activation_type=nn.ReLU))
             self.in_planes = planes
-        return _Stage(blocks)
+        return Numbered(blocks)  # (keys stage{i}.{j}.*)
 
     def _blocks(self):
         return [self.stem] + [b for s in (self.stage1, self.stage2, self.stage3, self.stage4) for b in s.blocks()]
 
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
-        a = K.input_to_nhwc(x)
+        a = self._input_nhwc(x)
         blocks = self._blocks()
         stats = None
         for blk, nxt in zip(blocks, blocks[1:] + [None]):
@@ -101,14 +85,10 @@ class RepVGG(SgxNetwork):
             want = self.training and nxt is not None and getattr(nxt, "no_conv_branch", None) is not None
             a = blk.fwd(a, x_stats=stats, want_stats=want)
             stats = blk.take_stats() if want else None
-        self._feat_shape = tuple(a.shape)
-        pooled = K.avgpool_fwd(a)
-        logits = self.linear.fwd(pooled)
-        return (logits.contiguous(),)
+        return (self._pool_head_fwd(a, self.linear),)
 
     def _bwd(self, d_logits):
-        d = self.linear.bwd(d_logits.contiguous())
-        d = K.avgpool_bwd(d.contiguous(), self._feat_shape)
+        d = self._pool_head_bwd(d_logits, self.linear)
         ready = self._bucket_ready
         ready("linear.")
         for name in ("stage4", "stage3", "stage2", "stage1"):
@@ -159,23 +139,11 @@ class RepVGG(SgxNetwork):
             raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing keys {missing}, unexpected keys {list(out.unexpected_keys)}")
         return out
 
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.linear = LinearLayer(int(512 * self.final_width_mult), new_num_classes)
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"linear": lr, "default": 0}
-
 
 @register_model("repvgg_custom")
 class RepVggCustom(RepVGG):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(struct=get_param(arch_params, "struct"), num_classes=num_classes or get_param(arch_params, "num_classes"),
+        super().__init__(struct=get_param(arch_params, "struct"), num_classes=num_classes_of(arch_params, num_classes),
                          width_multiplier=get_param(arch_params, "width_multiplier"),
                          build_residual_branches=get_param(arch_params, "build_residual_branches", True), use_se=get_param(arch_params, "use_se", False),
                          backbone_mode=get_param(arch_params, "backbone_mode", False), in_channels=get_param(arch_params, "in_channels", 3))

@@ -13,27 +13,16 @@ Backward: g = dy * [out > 0] (sgx_relu_bwd: the ReLU follows the residual add, s
 backward sweeps / weight gradients / data gradients of the branch, the shortcut gradient folded into the data-gradient
 epilogue (identity) or produced by the shortcut conv's own backward.
 """
-from typing import Dict
-
-import torch
-from torch import nn
-
 from .... import kernels as K
 from ....common.registry import register_model
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.engine import SgxBlock
+from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool, Numbered, widen_conv_input
 from ...utils.utils import get_param
 
 
 def width_multiplier(original, factor, to_int=True):
     return int(original * factor) if to_int else original * factor
-
-
-class _Seq(nn.Module):
-    """Namespace so that the shortcut's keys read shortcut.0.weight / shortcut.1.* like the reference's nn.Sequential."""
-
-    def __len__(self):
-        return len(self._modules)
 
 
 class _ConvBN:
@@ -49,9 +38,7 @@ class _ConvBN:
         return (t,) + tuple(bn.scale_shift(None, 0, False))
 
 
-
-
-class _ResBlock(SgxBlock):
+class ResBlock(SgxBlock):
     """out = [relu]( bn_n(conv_n(... relu(bn_1(conv_1(x))) ...)) + shortcut(x) )
     Eval folds: a subclass may set `_folded = {branch index: (filter, bias)}` for layers whose conv has `conv_with` (resnext.py's
     GroupedConvBlock does in prep_model_for_conversion); eval-mode fwd() then runs relu(conv_with(...)) for those layers.  Only layers
@@ -66,7 +53,7 @@ class _ResBlock(SgxBlock):
         pass
 
     def _init_shortcut(self, in_planes, out_planes, stride):
-        self.shortcut = _Seq()
+        self.shortcut = Numbered()  # (keys shortcut.0.weight / shortcut.1.*; empty: the identity)
         if stride != 1 or in_planes != out_planes:
             self.shortcut.add_module("0", ConvLayer(in_planes, out_planes, 1, stride, 0, bias=False))
             self.shortcut.add_module("1", BatchNorm(out_planes))
@@ -177,7 +164,7 @@ class _ResBlock(SgxBlock):
         return dx
 
 
-class BasicResNetBlock(_ResBlock):
+class BasicResNetBlock(ResBlock):
     def __init__(self, in_planes, planes, stride=1, expansion=1, final_relu=True, droppath_prob=0.0):
         super().__init__()
         if droppath_prob:
@@ -193,7 +180,7 @@ class BasicResNetBlock(_ResBlock):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2)]
 
 
-class Bottleneck(_ResBlock):
+class Bottleneck(ResBlock):
     def __init__(self, in_planes, planes, stride=1, expansion=4, final_relu=True, droppath_prob=0.0):
         super().__init__()
         if droppath_prob:
@@ -211,22 +198,10 @@ class Bottleneck(_ResBlock):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
 
 
-class _Layer(nn.Module):
-    """nn.Sequential of blocks (keys layer{i}.{j}.*)."""
-
-    def __init__(self, blocks):
-        super().__init__()
-        for i, b in enumerate(blocks):
-            self.add_module(str(i), b)
-
-    def blocks(self):
-        return list(self._modules.values())
-
-
-class _ResNetBase(SgxNetwork):
+class ResNetBase(SgxClassifier):
     """Shared driver: stem -> layer1..4 -> global average pool -> linear, and its backward."""
 
-    _head = "linear"  # the classifier's attribute name (ResNeXt: fc)
+    _head_path = _finetune_key = "linear"  # the classifier's attribute name (ResNeXt: fc)
 
     def _make_layer(self, block, planes, num_blocks, stride):
         if num_blocks == 0:
@@ -235,7 +210,7 @@ class _ResNetBase(SgxNetwork):
         for s in [stride] + [1] * (num_blocks - 1):
             blocks.append(block(self.in_planes, planes, s, self.expansion) if block is Bottleneck else block(self.in_planes, planes, s, self.expansion))
             self.in_planes = planes * self.expansion
-        return _Layer(blocks)
+        return Numbered(blocks)  # (keys layer{i}.{j}.*)
 
     def _stem_fwd(self, xh):
         raise NotImplementedError
@@ -244,22 +219,16 @@ class _ResNetBase(SgxNetwork):
         raise NotImplementedError
 
     def _fwd(self, x):
-        if x.dim() != 4 or x.shape[1] != self.conv1.in_channels:
-            raise ValueError(f"expected an NCHW batch with {self.conv1.in_channels} channels, got {tuple(x.shape)}")
-        a = self._stem_fwd(K.input_to_nhwc(x))
+        a = self._stem_fwd(self._input_nhwc(x))
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer.blocks():
                 a = blk.fwd(a)
-        self._feat_shape = tuple(a.shape)
-        pooled = K.avgpool_fwd(a)
-        logits = getattr(self, self._head).fwd(pooled)
-        return (logits.contiguous(),)
+        return (self._pool_head_fwd(a, getattr(self, self._head_path)),)
 
     def _bwd(self, d_logits):
-        d = getattr(self, self._head).bwd(d_logits.contiguous())
-        d = K.avgpool_bwd(d.contiguous(), self._feat_shape)
+        d = self._pool_head_bwd(d_logits, getattr(self, self._head_path))
         ready = self._bucket_ready
-        ready(f"{self._head}.")
+        ready(f"{self._head_path}.")
         for name in ("layer4", "layer3", "layer2", "layer1"):
             for blk in reversed(getattr(self, name).blocks()):
                 d = blk.bwd(d)
@@ -270,7 +239,7 @@ class _ResNetBase(SgxNetwork):
 
     def gradient_buckets(self):
         """Arena ranges in parameter order; `stem` covers conv1/bn1 (GradientAllReducer matches by name prefix)."""
-        return ["conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", f"{self._head}."]
+        return ["conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", f"{self._head_path}."]
 
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
     def get_input_channels(self) -> int:
@@ -281,24 +250,10 @@ class _ResNetBase(SgxNetwork):
         already has; extra channels are drawn from a normal distribution with the old weights' mean / std.  Before materialisation only."""
         if self._materialized:
             raise RuntimeError("replace_input_channels must be called before the model is materialized in HBM (before the first forward)")
-        old = self.conv1
-        if compute_new_weights_fn is not None:
-            self.conv1 = compute_new_weights_fn(old, in_channels)
-            return
-        new = ConvLayer(in_channels, old.out_channels, old.kernel_size, old.stride, old.padding, bias=old.bias is not None)
-        w = old.weight.data
-        if in_channels <= old.in_channels:
-            new.weight.data = w[:, :in_channels].clone()
-        else:
-            new.weight.data[:, : old.in_channels] = w
-            torch.nn.init.normal_(new.weight.data[:, old.in_channels:], mean=float(w.mean()), std=float(w.std()))
-        self.conv1 = new
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"linear": lr, "default": 0}
+        self.conv1 = widen_conv_input(self.conv1, in_channels, compute_new_weights_fn)
 
 
-class CifarResNet(_ResNetBase):
+class CifarResNet(ResNetBase):
     def __init__(self, block, num_blocks, num_classes=10, width_mult=1, expansion=1, in_channels: int = 3):
         super().__init__()
         self.expansion = expansion
@@ -324,7 +279,7 @@ class CifarResNet(_ResNetBase):
         self.conv1.wgrad(xh, dt)
 
 
-class ResNet(_ResNetBase):
+class ResNet(ResNetBase):
     def __init__(self, block, num_blocks: list, num_classes: int = 10, width_mult: float = 1, expansion: int = 1, droppath_prob=0.0,
                  input_batchnorm: bool = False, backbone_mode: bool = False, in_channels: int = 3):
         super().__init__()
@@ -354,23 +309,10 @@ class ResNet(_ResNetBase):
         dt = self.bn1.backward(d, t, sc, sh, mean, invstd, "relu", dx_out=t)
         self.conv1.wgrad(xh, dt)
 
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.linear = LinearLayer(width_multiplier(512, self.width_mult) * self.expansion, new_num_classes)
-
-
-def _nc(arch_params, num_classes):
-    return num_classes or get_param(arch_params, "num_classes")
-
 
 def _resnet(name, block, layers, expansion=1):
     def init(self, arch_params, num_classes=None):
-        ResNet.__init__(self, block, layers, num_classes=_nc(arch_params, num_classes), expansion=expansion,
+        ResNet.__init__(self, block, layers, num_classes=num_classes_of(arch_params, num_classes), expansion=expansion,
                         droppath_prob=get_param(arch_params, "droppath_prob", 0), backbone_mode=get_param(arch_params, "backbone_mode", False))
 
     return register_model(name)(type(name.title().replace("_", ""), (ResNet,), {"__init__": init}))
@@ -386,11 +328,11 @@ ResNet152 = _resnet("resnet152", Bottleneck, [3, 8, 36, 3], expansion=4)
 @register_model("resnet18_cifar")
 class ResNet18Cifar(CifarResNet):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(BasicResNetBlock, [2, 2, 2, 2], num_classes=_nc(arch_params, num_classes))
+        super().__init__(BasicResNetBlock, [2, 2, 2, 2], num_classes=num_classes_of(arch_params, num_classes))
 
 
 @register_model("resnet50_3343")
 class ResNet50_3343(ResNet):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(Bottleneck, [3, 3, 4, 3], num_classes=_nc(arch_params, num_classes), expansion=4,
+        super().__init__(Bottleneck, [3, 3, 4, 3], num_classes=num_classes_of(arch_params, num_classes), expansion=4,
                          droppath_prob=get_param(arch_params, "droppath_prob", 0), backbone_mode=get_param(arch_params, "backbone_mode", False))

@@ -11,12 +11,12 @@ import torch
 from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import _conv_layer
-from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool
-from ...utils.utils import get_param
-from .resnet import ResNet, _Layer, _ResBlock, _ResNetBase, _Seq
+from ....modules.classifier import num_classes_of
+from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool, Numbered
+from .resnet import ResBlock, ResNet, ResNetBase
 
 
-class GroupedConvBlock(_ResBlock):
+class GroupedConvBlock(ResBlock):
     """Reference GroupedConvBlock: 1x1 -> grouped 3x3 (stride) -> 1x1, each with BatchNorm, ReLU after the first two and after the add."""
 
     expansion = 4
@@ -33,7 +33,7 @@ class GroupedConvBlock(_ResBlock):
         self.bn2 = BatchNorm(width)
         self.conv3 = ConvLayer(width, planes * self.expansion, 1, 1, 0, bias=False)
         self.bn3 = BatchNorm(planes * self.expansion)
-        self.downsample = _Seq()  # (the reference's None: an empty namespace adds no key)
+        self.downsample = Numbered()  # (the reference's None: an empty namespace adds no key)
         if stride != 1 or inplanes != planes * self.expansion:
             self.downsample.add_module("0", ConvLayer(inplanes, planes * self.expansion, 1, stride, 0, bias=False))
             self.downsample.add_module("1", BatchNorm(planes * self.expansion))
@@ -61,7 +61,7 @@ class GroupedConvBlock(_ResBlock):
         return super().train(mode)
 
     @property
-    def shortcut(self):  # _ResBlock's name for it
+    def shortcut(self):  # ResBlock's name for it
         return self.downsample
 
     def _branch(self):
@@ -69,10 +69,10 @@ class GroupedConvBlock(_ResBlock):
 
 
 class ResNeXt(ResNet):
-    _head = "fc"
+    _head_path = _finetune_key = "fc"
 
     def __init__(self, layers, cardinality, bottleneck_width, num_classes=10, replace_stride_with_dilation=None, in_channels: int = 3):
-        _ResNetBase.__init__(self)
+        ResNetBase.__init__(self)
         if replace_stride_with_dilation is None:
             replace_stride_with_dilation = [False, False, False]
         if len(replace_stride_with_dilation) != 3:
@@ -97,28 +97,16 @@ class ResNeXt(ResNet):
         for s in [stride] + [1] * (blocks - 1):
             out.append(GroupedConvBlock(self.inplanes, planes, s, self.cardinality, self.base_width))
             self.inplanes = planes * GroupedConvBlock.expansion
-        return _Layer(out)
-
-    def get_finetune_lr_dict(self, lr: float):
-        return {"fc": lr, "default": 0}
-
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.fc = LinearLayer(512 * GroupedConvBlock.expansion, new_num_classes)
+        return Numbered(out)
 
 
 @register_model("resnext50")
 class ResNeXt50(ResNeXt):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(layers=[3, 4, 6, 3], cardinality=32, bottleneck_width=4, num_classes=num_classes or get_param(arch_params, "num_classes"))
+        super().__init__(layers=[3, 4, 6, 3], cardinality=32, bottleneck_width=4, num_classes=num_classes_of(arch_params, num_classes))
 
 
 @register_model("resnext101")
 class ResNeXt101(ResNeXt):
     def __init__(self, arch_params, num_classes=None):
-        super().__init__(layers=[3, 4, 23, 3], cardinality=32, bottleneck_width=8, num_classes=num_classes or get_param(arch_params, "num_classes"))
+        super().__init__(layers=[3, 4, 23, 3], cardinality=32, bottleneck_width=8, num_classes=num_classes_of(arch_params, num_classes))

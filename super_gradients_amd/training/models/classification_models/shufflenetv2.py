@@ -32,23 +32,18 @@ padded behind the parameters' backs.
 Not built (each raises NotImplementedError where reachable): backbone_mode=True; block stride 3; x1_0 / x2_0 (above);
 replace_head(new_head=...); half-precision inference.
 """
-from typing import Dict
-
 import torch
 
 from .... import kernels as K
 from ....common.registry import register_model
 from ....modules.conv_bn_act_block import ConvBNSeq, ConvBNView
-from ....modules.engine import SgxBlock, SgxNetwork
-from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, LinearLayer, MaxPool
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.engine import SgxBlock
+from ....modules.layers import BatchNorm, ConvLayer, DepthwiseConvLayer, LinearLayer, MaxPool, Numbered, need_mult4
 from ...utils.utils import get_param
-from .mobilenetv2 import _Numbered
 
 
-def _need_mult4(what, n):
-    if n % 4:
-        raise NotImplementedError(f"ShuffleNetV2 on the HIP path: {what} must be a multiple of 4 (every sweep and convolution moves 16-byte channel "
-                                  f"groups, and the block's halves are channel slices that must start on one), got {n}")
+_WHY_MULT4 = "every sweep and convolution moves 16-byte channel groups, and the block's halves are channel slices that must start on one"
 
 
 class ChannelShuffleInvertedResidual(SgxBlock):
@@ -61,19 +56,19 @@ class ChannelShuffleInvertedResidual(SgxBlock):
         if stride == 3:
             raise NotImplementedError("ShuffleNetV2 on the HIP path: block stride 1 or 2 (the depthwise kernels have no stride 3)")
         h = out // 2
-        _need_mult4(f"the half width of a block ({inp} -> {out} channels)", h)
-        _need_mult4("a stride-2 block's input width", inp if stride > 1 else 0)
+        need_mult4("ShuffleNetV2", f"the half width of a block ({inp} -> {out} channels)", h, why=_WHY_MULT4)
+        need_mult4("ShuffleNetV2", "a stride-2 block's input width", inp if stride > 1 else 0, why=_WHY_MULT4)
         if out != 2 * h:
             raise NotImplementedError(f"ShuffleNetV2 on the HIP path: an even block width, got {out}")
         self.stride, self.h = stride, h
         if stride > 1:
             b1 = {"0": DepthwiseConvLayer(inp, stride), "1": BatchNorm(inp), "2": ConvLayer(inp, h, 1, 1, 0), "3": BatchNorm(h)}
-            self.branch1 = _Numbered(**b1)
+            self.branch1 = Numbered(**b1)
         else:
             self.branch1 = None  # (the reference's nn.Identity: no state)
         b2 = {"0": ConvLayer(inp if stride > 1 else inp // 2, h, 1, 1, 0), "1": BatchNorm(h), "3": DepthwiseConvLayer(h, stride), "4": BatchNorm(h),
               "5": ConvLayer(h, h, 1, 1, 0), "6": BatchNorm(h)}
-        self.branch2 = _Numbered(**b2)
+        self.branch2 = Numbered(**b2)
         # the conv -> BatchNorm (-> ReLU) sequences over those layers (they own no parameter: nothing is added to the state); the last one of
         # a branch stops before its affine sweep (fwd_raw): the merge sweep is that sweep
         self.pw = ConvBNView(b2["0"], b2["1"], "relu")
@@ -130,7 +125,9 @@ class ChannelShuffleInvertedResidual(SgxBlock):
         return dx
 
 
-class ShuffleNetV2Base(SgxNetwork):
+class ShuffleNetV2Base(SgxClassifier):
+    _head_path = _finetune_key = "fc"
+
     def __init__(self, structure, stages_out_channels, backbone_mode: bool = False, num_classes: int = 1000, block=ChannelShuffleInvertedResidual,
                  in_channels: int = 3):
         super().__init__()
@@ -144,37 +141,31 @@ class ShuffleNetV2Base(SgxNetwork):
         self.structure = structure
         self.out_channels = stages_out_channels
         c = self.out_channels
-        _need_mult4("the stem's width", c[0])
+        need_mult4("ShuffleNetV2", "the stem's width", c[0], why=_WHY_MULT4)
         self.conv1 = ConvBNSeq(in_channels, c[0], 3, stride=2, padding=1, activation_type="relu")
         self.maxpool = MaxPool(3, 2, 1)
         self.layer2 = self._make_layer(block, c[0], c[1], structure[0])
         self.layer3 = self._make_layer(block, c[1], c[2], structure[1])
         self.layer4 = self._make_layer(block, c[2], c[3], structure[2])
-        _need_mult4("conv5's width", c[4])
+        need_mult4("ShuffleNetV2", "conv5's width", c[4], why=_WHY_MULT4)
         self.conv5 = ConvBNSeq(c[3], c[4], 1, stride=1, padding=0, activation_type="relu")
         self.fc = LinearLayer(c[4], num_classes)
 
     @staticmethod
     def _make_layer(block, input_channels, output_channels, repeats):
         seq = [block(input_channels, output_channels, 2)] + [block(output_channels, output_channels, 1) for _ in range(repeats - 1)]
-        return _Numbered(**{str(i): b for i, b in enumerate(seq)})
+        return Numbered(seq)
 
     def _fwd(self, x):
-        cin = self.get_input_channels()
-        if x.dim() != 4 or x.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(x.shape)}")
-        a = self.maxpool.fwd(self.conv1.fwd(K.input_to_nhwc(x)))
+        a = self.maxpool.fwd(self.conv1.fwd(self._input_nhwc(x)))
         for layer in (self.layer2, self.layer3, self.layer4):
             for blk in layer.blocks():
                 a = blk.fwd(a)
-        a = self.conv5.fwd(a)
-        self._feat_shape = tuple(a.shape)
-        return (self.fc.fwd(K.avgpool_fwd(a)).contiguous(),)
+        return (self._pool_head_fwd(self.conv5.fwd(a), self.fc),)
 
     def _bwd(self, d_logits):
         ready = self._bucket_ready
-        d = self.fc.bwd(d_logits.contiguous())
-        d = K.avgpool_bwd(d.contiguous(), self._feat_shape)
+        d = self._pool_head_bwd(d_logits, self.fc)
         ready("fc.")
         d = self.conv5.bwd(d)
         ready("conv5.")
@@ -189,35 +180,14 @@ class ShuffleNetV2Base(SgxNetwork):
         """Arena ranges in parameter order (GradientAllReducer matches by name prefix)."""
         return ["conv1.", "layer2.", "layer3.", "layer4.", "conv5.", "fc."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
     def get_input_channels(self) -> int:
         return self.conv1._modules["0"].in_channels
 
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            raise NotImplementedError("replace_head(new_head=...) is not on the HIP path; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.fc = LinearLayer(self.out_channels[-1], new_num_classes)
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"fc": lr, "default": 0.0}
-
-
-def _nc(arch_params, num_classes):
-    """The reference's `num_classes or arch_params.num_classes`.  Its registered classes default num_classes to 1000, which hides
-    arch_params.num_classes - the only place models.get() puts the caller's value; here the default is None, as in the other families."""
-    return num_classes or get_param(arch_params, "num_classes")
-
 
 def _shufflenet(name, cls_name, stages_out_channels):
     def init(self, arch_params, num_classes: int = None, backbone_mode: bool = False):
-        ShuffleNetV2Base.__init__(self, [4, 8, 4], stages_out_channels, backbone_mode=backbone_mode, num_classes=_nc(arch_params, num_classes))
+        ShuffleNetV2Base.__init__(self, [4, 8, 4], stages_out_channels, backbone_mode=backbone_mode, num_classes=num_classes_of(arch_params, num_classes))
 
     return register_model(name)(type(cls_name, (ShuffleNetV2Base,), {"__init__": init}))
 
@@ -232,4 +202,4 @@ ShufflenetV2_x2_0 = _shufflenet("shufflenet_v2_x2_0", "ShufflenetV2_x2_0", [24, 
 class CustomizedShuffleNetV2(ShuffleNetV2Base):
     def __init__(self, arch_params, num_classes: int = None, backbone_mode: bool = False):
         super().__init__(get_param(arch_params, "structure"), get_param(arch_params, "stages_out_channels"), backbone_mode=backbone_mode,
-                         num_classes=_nc(arch_params, num_classes))
+                         num_classes=num_classes_of(arch_params, num_classes))

@@ -29,14 +29,14 @@ hidden_dim or hidden_dim / heads not a multiple of 4, in_channels neither 1..4 n
 constructed image_size (the reference slices pos_embedding); supports_half_inference() is False.
 """
 import math
-from typing import Dict
 
 import torch
 from torch import nn
 
 from .... import kernels as K
 from ....common.registry import register_model
-from ....modules.engine import SgxBlock, SgxNetwork
+from ....modules.classifier import SgxClassifier, num_classes_of
+from ....modules.engine import SgxBlock
 from ....modules.layers import ConvLayer, LinearLayer
 from ...utils.utils import get_param
 
@@ -243,7 +243,9 @@ class Transformer(SgxBlock):
         pass
 
 
-class ViT(SgxNetwork):
+class ViT(SgxClassifier):
+    _head_path = _finetune_key = "head"
+
     def __init__(self, image_size: tuple, patch_size: tuple, num_classes: int, hidden_dim: int, depth: int, heads: int, mlp_dim: int, in_channels=3,
                  dropout_prob=0.0, emb_dropout_prob=0.0, backbone_mode=False):
         super().__init__()
@@ -273,14 +275,12 @@ class ViT(SgxNetwork):
 
     # ---- forward / backward --------------------------------------------------------------------------------------
     def _fwd(self, img):
-        cin = self.get_input_channels()
-        if img.dim() != 4 or img.shape[1] != cin:
-            raise ValueError(f"expected an NCHW batch with {cin} channels, got {tuple(img.shape)}")
+        xh = self._input_nhwc(img)
         if tuple(img.shape[2:]) != self.image_size:
             _not_built(f"the model was built for {self.image_size} images and received {tuple(img.shape[2:])} (the reference slices pos_embedding; no recipe needs it)")
         if self.training and self.emb_dropout_prob > 0:
             _not_built(f"emb_dropout_prob = {self.emb_dropout_prob} in training mode (the recipes use 0; eval is the identity and works)")
-        x = K.token_assemble_fwd(self.patch_embedding.fwd(K.input_to_nhwc(img)), self.cls_token, self.pos_embedding)
+        x = K.token_assemble_fwd(self.patch_embedding.fwd(xh), self.cls_token, self.pos_embedding)
         for blk in self.transformer.blocks:
             x = blk.fwd(x)
         self._stream_shape = tuple(x.shape)
@@ -317,26 +317,11 @@ class ViT(SgxNetwork):
         return ["cls_token", "pos_embedding", "patch_embedding."] + [f"transformer.blocks.{i}." for i in range(len(self.transformer.blocks))] + \
                ["pre_head_norm.", "head."]
 
-    def supports_half_inference(self) -> bool:
-        return False
-
     def prep_model_for_conversion(self, input_size=None, **kwargs):
         """Nothing folds: no BatchNorm, no re-parameterised branch."""
         return self
 
     # ---- SgModule-style helpers the reference exposes -------------------------------------------------------------
-    def replace_head(self, new_num_classes=None, new_head=None):
-        if new_num_classes is None and new_head is None:
-            raise ValueError("At least one of new_num_classes, new_head must be given to replace output layer.")
-        if new_head is not None:
-            _not_built("replace_head(new_head=...) is not available; pass new_num_classes")
-        if self._materialized:
-            raise RuntimeError("replace_head must be called before the model is materialized in HBM")
-        self.head = LinearLayer(self.head.in_features, new_num_classes)
-
-    def get_finetune_lr_dict(self, lr: float) -> Dict[str, float]:
-        return {"head": lr, "default": 0}
-
     def get_input_channels(self) -> int:
         return self.patch_embedding.get_input_channels()
 
@@ -344,7 +329,7 @@ class ViT(SgxNetwork):
 def _variant(name, cls_name, hidden_dim, depth, heads, mlp_dim):
     def init(self, arch_params, num_classes=None, backbone_mode=None):
         ViT.__init__(self, image_size=get_param(arch_params, "image_size", (224, 224)), patch_size=get_param(arch_params, "patch_size", (16, 16)),
-                     num_classes=num_classes or get_param(arch_params, "num_classes"), hidden_dim=hidden_dim, depth=depth, heads=heads, mlp_dim=mlp_dim,
+                     num_classes=num_classes_of(arch_params, num_classes), hidden_dim=hidden_dim, depth=depth, heads=heads, mlp_dim=mlp_dim,
                      in_channels=get_param(arch_params, "in_channels", 3), dropout_prob=get_param(arch_params, "dropout_prob", 0),
                      emb_dropout_prob=get_param(arch_params, "emb_dropout_prob", 0), backbone_mode=backbone_mode)
 
