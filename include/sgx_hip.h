@@ -543,6 +543,15 @@ int32_t sgx_maxpool_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, i
 int32_t sgx_maxpool_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad,
                         const int32_t* argmax, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dx,
                         int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
+/* The same two with nn.MaxPool2d(ceil_mode=True) extents (GoogLeNet's 3/2/0 and 2/2/0 pools): per axis ceil((in + 2 pad - k) / stride) + 1,
+ * less one when the last window would start beyond in + pad - 1; windows are clipped at the bottom and right edge.  y / argmax / dy have
+ * those extents.  Always the direct kernels.                                                                                     */
+int32_t sgx_maxpool_ceil_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad,
+                             const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y, int64_t y_ld_pix,
+                             int64_t y_ld_img, int32_t* argmax, void* stream);
+int32_t sgx_maxpool_ceil_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, int32_t pad,
+                             const int32_t* argmax, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dx,
+                             int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
 /* The kernel sgx_maxpool_fwd (backward == 0) or sgx_maxpool_bwd (backward != 0) launches for this problem: 0 the direct kernel, 1 the
  * LDS-tile kernel, 2 the LDS-scatter kernel (backward only).  The launch code asks the same predicates; launches nothing itself.
  * (tests pin every case to the kernel it is meant to reach)                                                                     */
@@ -607,6 +616,28 @@ int32_t sgx_gconv3x3_bwd_data(const sgx_conv_desc* d, int32_t groups, const floa
 int64_t sgx_gconv3x3_bwd_weight_workspace(const sgx_conv_desc* d, int32_t groups);
 int32_t sgx_gconv3x3_bwd_weight(const sgx_conv_desc* d, int32_t groups, const float* x, const float* dy, float* dw, void* ws,
                                 int64_t ws_bytes, void* stream);
+
+/* GoogLeNet's pool-projection branch (training/models/classification_models/googlenet.py: Inception.branch4):
+ *   nn.MaxPool2d(3, stride=1, padding=1) -> nn.Conv2d(Ci, Co, 1, bias=False), and its backward, with P(x), its arg-max map and d P(x)
+ *   never stored (csrc/inception.h).  x / dx [N,H,W,Ci], y / dy [N,H,W,Co], filter [Co][1][1][Ci]; Ci % 4 == 0 and Co % 4 == 0; every
+ *   operand may be a channel slice (pixel / image strides in floats, multiples of 4).  Anything else: SGX_ERR_BAD_ARG, nothing launched.
+ * P follows ATen: -inf padding, the first maximum in row-major window order is selected, a NaN replaces the running maximum.
+ * fp32 matrix pipe; deterministic: no atomics, fixed orders.
+ * fwd: y = act(W * P(x) + bias), act none / relu / silu; with stat_partials ([2][sgx_pool3_conv1x1_stat_blocks][Co], no bias / activation)
+ *   the sum / sum-of-squares rows sgx_bn_finalize consumes.
+ * bwd_data: dx (+)= P'_x(dy * W): a gather - every dx pixel adds the d_pooled values of the windows that selected it, recomputed from x.
+ * bwd_weight: dw += dy' * P(x); partial filters in ws (sgx_pool3_conv1x1_bwd_weight_workspace bytes, 16-byte aligned), then the fp64 fold. */
+int32_t sgx_pool3_conv1x1_stat_blocks(int32_t N, int32_t H, int32_t W);
+int32_t sgx_pool3_conv1x1_fwd(int32_t N, int32_t H, int32_t W, int32_t Ci, int32_t Co, const float* x, int64_t x_ld_pix, int64_t x_ld_img,
+                              const float* w, const float* bias, float* y, int64_t y_ld_pix, int64_t y_ld_img, int32_t act,
+                              float* stat_partials, void* stream);
+int32_t sgx_pool3_conv1x1_bwd_data(int32_t N, int32_t H, int32_t W, int32_t Ci, int32_t Co, const float* dy, int64_t dy_ld_pix,
+                                   int64_t dy_ld_img, const float* w, const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* dx,
+                                   int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
+int64_t sgx_pool3_conv1x1_bwd_weight_workspace(int32_t N, int32_t H, int32_t W, int32_t Ci, int32_t Co);
+int32_t sgx_pool3_conv1x1_bwd_weight(int32_t N, int32_t H, int32_t W, int32_t Ci, int32_t Co, const float* x, int64_t x_ld_pix,
+                                     int64_t x_ld_img, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dw, void* ws,
+                                     int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Squeeze-excitation gates and nearest up-sampling of PP-YOLOE:

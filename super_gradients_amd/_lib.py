@@ -206,6 +206,13 @@ PROTOTYPES = {
     "sgx_gconv3x3_bwd_data": (_i32, [_CD, _i32, _P, _P, _P, _i32, _P, _i64, _P]),
     "sgx_gconv3x3_bwd_weight_workspace": (_i64, [_CD, _i32]),
     "sgx_gconv3x3_bwd_weight": (_i32, [_CD, _i32, _P, _P, _P, _P, _i64, _P]),
+    "sgx_pool3_conv1x1_stat_blocks": (_i32, [_i32] * 3),
+    "sgx_pool3_conv1x1_fwd": (_i32, [_i32] * 5 + [_P, _i64, _i64, _P, _P, _P, _i64, _i64, _i32, _P, _P]),
+    "sgx_pool3_conv1x1_bwd_data": (_i32, [_i32] * 5 + [_P, _i64, _i64, _P, _P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_pool3_conv1x1_bwd_weight_workspace": (_i64, [_i32] * 5),
+    "sgx_pool3_conv1x1_bwd_weight": (_i32, [_i32] * 5 + [_P, _i64, _i64, _P, _i64, _i64, _P, _P, _i64, _P]),
+    "sgx_maxpool_ceil_fwd": (_i32, [_i32] * 7 + [_P, _i64, _i64, _P, _i64, _i64, _P, _P]),
+    "sgx_maxpool_ceil_bwd": (_i32, [_i32] * 7 + [_P, _P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
     "sgx_bn_gate_act_fwd": (_i32, [_P, _i64, _P, _P, _P, _i32, _P, _i64, _i32, _i32, _i32, _i32, _P]),
     "sgx_bn_gate_act_bwd_gate_workspace": (_i64, [_i32] * 3),
     "sgx_bn_gate_act_bwd_gate": (_i32, [_P, _i64, _P, _i64, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _P, _i64, _P]),

@@ -663,6 +663,68 @@ def gconv3x3_bwd_weight(x, dy, dw, groups, stride=1):
     check(lib().sgx_gconv3x3_bwd_weight(d.ref, groups, ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel(), stream()), "sgx_gconv3x3_bwd_weight")
 
 
+# --------------------------------------------------------------------------------------------- max-pool 3x3 / 1 / 1 inside a 1x1 convolution
+def _chk_pw(w: torch.Tensor, ci):
+    co = w.shape[0]
+    _chk_w(w, co, 1, 1, ci)
+    return co
+
+
+def pool3_conv1x1_fwd(x, w, bias=None, out=None, act=None, stat_partials=False):
+    """y = act(conv1x1(max_pool2d(x, 3, 1, 1), w) + bias), w logical [Co, Ci, 1, 1]; the pooled map is never stored (csrc/inception.h).
+    stat_partials: also the BatchNorm statistics rows of y (then no bias / activation)."""
+    n, h, wd, ci = x.shape
+    co = _chk_pw(w, ci)
+    if out is None:
+        out = torch.empty(n, h, wd, co, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, h, wd, co):
+        raise _lib.SgxError(f"pool3_conv1x1_fwd: output shape {tuple(out.shape)} != {(n, h, wd, co)}")
+    parts = None
+    if stat_partials:
+        parts = torch.empty(2, lib().sgx_pool3_conv1x1_stat_blocks(n, h, wd), co, device=x.device, dtype=torch.float32)
+    xl, xi = nhwc_strides(x)
+    yl, yi = nhwc_strides(out)
+    check(lib().sgx_pool3_conv1x1_fwd(n, h, wd, ci, co, ptr(x), xl, xi, ptr(w), ptr(bias), ptr(out), yl, yi, ACT[act], ptr(parts), stream()),
+          "sgx_pool3_conv1x1_fwd")
+    return (out, parts) if stat_partials else out
+
+
+def pool3_conv1x1_bwd_data(dy, w, x, out=None, accumulate=False):
+    """dx (+)= the gradient of x: every pooled pixel's gradient goes to the arg-max of its window, recomputed from x."""
+    n, h, wd, ci = x.shape
+    co = _chk_pw(w, ci)
+    if tuple(dy.shape) != (n, h, wd, co):
+        raise _lib.SgxError(f"pool3_conv1x1_bwd_data: dy shape {tuple(dy.shape)} != {(n, h, wd, co)}")
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("pool3_conv1x1_bwd_data: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(n, h, wd, ci, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise _lib.SgxError(f"pool3_conv1x1_bwd_data: dx shape {tuple(out.shape)} != {tuple(x.shape)}")
+    dl, di = nhwc_strides(dy)
+    xl, xi = nhwc_strides(x)
+    ol, oi = nhwc_strides(out)
+    check(lib().sgx_pool3_conv1x1_bwd_data(n, h, wd, ci, co, ptr(dy), dl, di, ptr(w), ptr(x), xl, xi, ptr(out), ol, oi, int(accumulate), stream()),
+          "sgx_pool3_conv1x1_bwd_data")
+    return out
+
+
+def pool3_conv1x1_bwd_weight(x, dy, dw):
+    """dw (logical [Co, Ci, 1, 1]) += grad."""
+    n, h, wd, ci = x.shape
+    co = _chk_pw(dw, ci)
+    if tuple(dy.shape) != (n, h, wd, co):
+        raise _lib.SgxError(f"pool3_conv1x1_bwd_weight: dy shape {tuple(dy.shape)} != {(n, h, wd, co)}")
+    need = lib().sgx_pool3_conv1x1_bwd_weight_workspace(n, h, wd, ci, co)
+    if need <= 0:
+        check(-1, "sgx_pool3_conv1x1_bwd_weight_workspace")
+    ws = WORKSPACE.get(need, x.device)
+    xl, xi = nhwc_strides(x)
+    dl, di = nhwc_strides(dy)
+    check(lib().sgx_pool3_conv1x1_bwd_weight(n, h, wd, ci, co, ptr(x), xl, xi, ptr(dy), dl, di, ptr(dw), ptr(ws), ws.numel(), stream()),
+          "sgx_pool3_conv1x1_bwd_weight")
+
+
 _TICKETS = {}
 
 
@@ -1598,10 +1660,20 @@ def token_mean_bwd(dy, tokens, out=None):
 
 
 # --------------------------------------------------------------------------------------------- pooling
-def maxpool_fwd(x, k, stride, pad, out=None, want_argmax=True):
+def maxpool_out(n, k, stride, pad, ceil_mode=False):
+    """Output extent of nn.MaxPool2d along one axis; ceil_mode: the last window must still start inside the map or its leading padding."""
+    if not ceil_mode:
+        return (n + 2 * pad - k) // stride + 1
+    o = -((n + 2 * pad - k) // -stride) + 1
+    return o - 1 if (o - 1) * stride >= n + pad else o
+
+
+def maxpool_fwd(x, k, stride, pad, out=None, want_argmax=True, ceil_mode=False):
     n, h, w, c = x.shape
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ho, wo = maxpool_out(h, k, stride, pad, ceil_mode), maxpool_out(w, k, stride, pad, ceil_mode)
     if x.dtype == HALF:
+        if ceil_mode:
+            raise _lib.SgxError("maxpool_fwd on bf16: no ceil-mode form")
         if want_argmax:
             raise _lib.SgxError("maxpool_fwd on bf16: inference only (no arg-max)")
         if out is None:
@@ -1615,16 +1687,26 @@ def maxpool_fwd(x, k, stride, pad, out=None, want_argmax=True):
     am = torch.empty(n, ho, wo, c, device=x.device, dtype=torch.int32) if want_argmax else None
     xl, xi = nhwc_strides(x)
     yl, yi = nhwc_strides(out)
+    if ceil_mode:
+        if tuple(out.shape) != (n, ho, wo, c):
+            raise _lib.SgxError(f"maxpool_fwd: output shape {tuple(out.shape)} != {(n, ho, wo, c)}")
+        check(lib().sgx_maxpool_ceil_fwd(n, h, w, c, k, stride, pad, ptr(x), xl, xi, ptr(out), yl, yi, ptr(am), stream()), "sgx_maxpool_ceil_fwd")
+        return out, am
     check(lib().sgx_maxpool_fwd(n, h, w, c, k, stride, pad, ptr(x), xl, xi, ptr(out), yl, yi, ptr(am), stream()), "sgx_maxpool_fwd")
     return out, am
 
 
-def maxpool_bwd(dy, argmax, x_shape, k, stride, pad, out=None, accumulate=False):
+def maxpool_bwd(dy, argmax, x_shape, k, stride, pad, out=None, accumulate=False, ceil_mode=False):
     n, h, w, c = x_shape
     if out is None:
         out = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
     dl, di = nhwc_strides(dy)
     xl, xi = nhwc_strides(out)
+    if ceil_mode:
+        if tuple(dy.shape) != (n, maxpool_out(h, k, stride, pad, True), maxpool_out(w, k, stride, pad, True), c) or tuple(argmax.shape) != tuple(dy.shape):
+            raise _lib.SgxError(f"maxpool_bwd: dy {tuple(dy.shape)} / argmax {tuple(argmax.shape)} do not have the ceil-mode extents of {tuple(x_shape)}")
+        check(lib().sgx_maxpool_ceil_bwd(n, h, w, c, k, stride, pad, ptr(argmax), ptr(dy), dl, di, ptr(out), xl, xi, int(accumulate), stream()), "sgx_maxpool_ceil_bwd")
+        return out
     check(lib().sgx_maxpool_bwd(n, h, w, c, k, stride, pad, ptr(argmax), ptr(dy), dl, di, ptr(out), xl, xi, int(accumulate), stream()), "sgx_maxpool_bwd")
     return out
 

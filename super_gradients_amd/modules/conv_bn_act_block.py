@@ -98,6 +98,8 @@ class _ConvBN(SgxBlock):
                 raise RuntimeError("half-precision inference runs the folded deployment form: call prep_model_for_conversion() in eval mode first")
             if conv.grouped:
                 raise NotImplementedError("the grouped convolution has no half-precision kernel")
+            if getattr(conv, "pooled", False):
+                raise NotImplementedError("the pool projection (max-pool inside the 1x1 convolution) has no half-precision kernel")
             return K.conv2d_fwd(x, folded[0], bias=folded[1], out=out, act=self.act, stride=conv.stride, pad=conv.padding,
                                 post_add=post_add, post_scale=post_scale)
         if post_scale is not None:
@@ -126,7 +128,7 @@ class _ConvBN(SgxBlock):
         if self._folded is not None and post_add is None:
             if conv.depthwise and residual is None:
                 return conv.conv_with(x, self._folded[0], self._folded[1], out=out, act=self.act)
-            if conv.grouped:  # act(gconv(x, w) + bias) in one launch; ReLU6 / hard-swish and a residual take the sweep after it
+            if conv.grouped or getattr(conv, "pooled", False):  # act(gconv(x, w) + bias) in one launch (conv_with); ReLU6 / hard-swish and a residual take the sweep after it
                 own = self.act not in ("relu6", "hswish") and residual is None
                 t = conv.conv_with(x, self._folded[0], self._folded[1], out=out if own else None, act=self.act if own else None)
                 return t if own else K.affine_act(t, r1=residual, act=self.act, out=out if out is not None else t)
@@ -147,7 +149,7 @@ class _ConvBN(SgxBlock):
         scale / shift and no mean / invstd; after prep_model_for_conversion() t is the finished output (bias and activation in the
         convolution's epilogue) and scale / shift are None.  Training keeps what bwd_from_dt() needs."""
         conv, bn = self._parts()
-        if self._gate is not None or x.dtype == K.HALF or conv.depthwise or conv.grouped or self.act in ("relu6", "hswish"):
+        if self._gate is not None or x.dtype == K.HALF or conv.depthwise or conv.grouped or getattr(conv, "pooled", False) or self.act in ("relu6", "hswish"):
             raise NotImplementedError("fwd_raw: a plain fp32 convolution -> BatchNorm [-> ReLU / SiLU] layer")
         if self.training:
             self._folded = self._folded_half = None

@@ -357,21 +357,21 @@ class ConvTranspose2x2(SgxBlock):
 
 
 class MaxPool(SgxBlock):
-    def __init__(self, kernel_size, stride, padding):
+    def __init__(self, kernel_size, stride, padding, ceil_mode=False):
         super().__init__()
-        self.k, self.s, self.p = kernel_size, stride, padding
+        self.k, self.s, self.p, self.ceil_mode = kernel_size, stride, padding, bool(ceil_mode)
 
     def on_materialize(self):
         pass
 
     def fwd(self, x, out=None):
-        y, am = K.maxpool_fwd(x, self.k, self.s, self.p, out=out, want_argmax=self.training)
+        y, am = K.maxpool_fwd(x, self.k, self.s, self.p, out=out, want_argmax=self.training, ceil_mode=self.ceil_mode)
         self._ctx = (am, tuple(x.shape))
         return y
 
     def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
         (am, shape), self._ctx = self._ctx, None
-        return K.maxpool_bwd(dy, am, shape, self.k, self.s, self.p, out=dx_out, accumulate=accumulate)
+        return K.maxpool_bwd(dy, am, shape, self.k, self.s, self.p, out=dx_out, accumulate=accumulate, ceil_mode=self.ceil_mode)
 
 
 class LinearLayer(SgxBlock):
