@@ -617,6 +617,32 @@ int64_t sgx_gconv3x3_bwd_weight_workspace(const sgx_conv_desc* d, int32_t groups
 int32_t sgx_gconv3x3_bwd_weight(const sgx_conv_desc* d, int32_t groups, const float* x, const float* dy, float* dw, void* ws,
                                 int64_t ws_bytes, void* stream);
 
+/* Split-dilation grouped 3x3 convolution, stride 1 (csrc/dilated.h): the C channels are cut into nsplit equal splits, split i is
+ *   nn.Conv2d(C / nsplit, C / nsplit, 3, 1, padding=dil[i], dilation=dil[i], groups=(C / nsplit) / cg, bias=False), the outputs are
+ *   concatenated - RegSeg's DBlock (one split: its single-dilation convolution) - and its backward.  ONE launch over all splits: x / y are
+ *   whole [N,H,W,C] tensors or channel slices, no split or concat pass.
+ * d: the descriptor sgx_gconv3x3_* takes at stride 1 (K == C, R == S == 3, pad 1 standing for "same" extents: a split pads by its own
+ *   dilation); 1 <= nsplit <= 4, C % nsplit == 0, (C / nsplit) % cg == 0, cg == 16, every dil[i] >= 1 (dil: nsplit HOST integers).
+ *   Anything else: SGX_ERR_BAD_ARG, nothing launched.  Dilation [1] alone belongs to sgx_gconv3x3_*.
+ * w / dw: nsplit HOST pointers to device filters, each stored [C / nsplit][3][3][cg] (the reference's [C / nsplit, cg, 3, 3] as a view).
+ * fp32 matrix pipe, gconv's tiles.  Per split the host picks how the dilated taps reach LDS: the halo patch while it has at most 561
+ *   pixels, else one band per filter row, else (d above the tile width) the band's three tiles alone - every d fits.  Taps whose shifted
+ *   tile lies outside the map are skipped.  Deterministic: no atomics, fixed fold orders.
+ * fwd: y = act(conv + bias), act none / relu / silu; stat_partials as in sgx_gconv3x3_fwd with sgx_dgconv3x3_stat_blocks rows.
+ * bwd_data: dx (+)= the data gradient, a gather: the same kernel over dy with reversed taps and the filter read transposed.
+ * bwd_weight: dw[i] += ...; per-workgroup partial filters in ws (sgx_dgconv3x3_bwd_weight_workspace bytes, 16-byte aligned), then one
+ *   fp64 fold per split.
+ * sgx_debug_dgconv3x3_form: the staging of split `split`: 0 halo, 1 band, 2 band as three tiles (the launches ask the same predicate). */
+int32_t sgx_dgconv3x3_stat_blocks(const sgx_conv_desc* d, int32_t cg, int32_t nsplit, const int32_t* dil);
+int32_t sgx_dgconv3x3_fwd(const sgx_conv_desc* d, int32_t cg, int32_t nsplit, const int32_t* dil, const float* const* w,
+                          const float* x, const float* bias, float* y, int32_t act, float* stat_partials, void* stream);
+int32_t sgx_dgconv3x3_bwd_data(const sgx_conv_desc* d, int32_t cg, int32_t nsplit, const int32_t* dil, const float* dy,
+                               const float* const* w, float* dx, int32_t accumulate, void* stream);
+int64_t sgx_dgconv3x3_bwd_weight_workspace(const sgx_conv_desc* d, int32_t cg, int32_t nsplit, const int32_t* dil);
+int32_t sgx_dgconv3x3_bwd_weight(const sgx_conv_desc* d, int32_t cg, int32_t nsplit, const int32_t* dil, const float* x,
+                                 const float* dy, float* const* dw, void* ws, int64_t ws_bytes, void* stream);
+int32_t sgx_debug_dgconv3x3_form(const sgx_conv_desc* d, int32_t cg, int32_t nsplit, const int32_t* dil, int32_t split);
+
 /* GoogLeNet's pool-projection branch (training/models/classification_models/googlenet.py: Inception.branch4):
  *   nn.MaxPool2d(3, stride=1, padding=1) -> nn.Conv2d(Ci, Co, 1, bias=False), and its backward, with P(x), its arg-max map and d P(x)
  *   never stored (csrc/inception.h).  x / dx [N,H,W,Ci], y / dy [N,H,W,Co], filter [Co][1][1][Ci]; Ci % 4 == 0 and Co % 4 == 0; every
@@ -668,6 +694,33 @@ int32_t sgx_upsample2x_fwd(int32_t N, int32_t H, int32_t W, int32_t C, const flo
                            int64_t y_ld_pix, int64_t y_ld_img, void* stream);
 int32_t sgx_upsample2x_bwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img,
                            float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
+
+/* Bilinear interpolation by integer factors sh x sw (csrc/bilinear.h): ATen's upsample_bilinear2d for both align_corners settings, source
+ * coordinates and weights computed in float the way ATen computes them.  Deterministic: the backward kernels are gathers (every dx element
+ * sums, in ascending order, the dy rows / columns whose two-tap footprint contains it, found through the inverse map with a one-pixel
+ * guard) - no atomics.  N, H, W, C describe x; y / dy are [N, sh H, sw W, C].
+ * sgx_bilinear_fwd: NHWC -> NHWC, y = bilinear(x) (+ addend, may be NULL: RegSeg's decoder sum in one pass); operands may be channel slices
+ *   (its concat without a concat pass): C, strides multiples of 4 floats, 16-byte aligned addresses.
+ * sgx_bilinear_bwd: dx (+)= A^T dy.
+ * sgx_bilinear_nchw_fwd: the segmentation head - x the NHWC logits (ANY C, pixel stride x_ld_pix >= C), y the contiguous NCHW
+ *   [N, C, sh H, sw W]; lanes run along the output row (16-byte stores when sw W % 4 == 0).  _bwd reads the NCHW dy and writes (not adds) the
+ *   NHWC logit gradient.                                                                                                        */
+int32_t sgx_bilinear_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t sh, int32_t sw, int32_t align_corners, const float* x,
+                         int64_t x_ld_pix, int64_t x_ld_img, const float* addend, int64_t a_ld_pix, int64_t a_ld_img, float* y,
+                         int64_t y_ld_pix, int64_t y_ld_img, void* stream);
+int32_t sgx_bilinear_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t sh, int32_t sw, int32_t align_corners, const float* dy,
+                         int64_t dy_ld_pix, int64_t dy_ld_img, float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate,
+                         void* stream);
+int32_t sgx_bilinear_nchw_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t sh, int32_t sw, int32_t align_corners, const float* x,
+                              int64_t x_ld_pix, int64_t x_ld_img, float* y, void* stream);
+int32_t sgx_bilinear_nchw_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t sh, int32_t sw, int32_t align_corners, const float* dy,
+                              float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, void* stream);
+/* nn.AvgPool2d(2, 2, ceil_mode=True) (RegSeg's shortcut): y [N, ceil(H/2), ceil(W/2), C]; the bottom / right windows are clipped and divide
+ * by their in-bounds count (ATen with pad 0).  N, H, W, C describe x; bwd: dx (+)= dy of the pixel's window / that count.     */
+int32_t sgx_avgpool2_ceil_fwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* x, int64_t x_ld_pix, int64_t x_ld_img, float* y,
+                              int64_t y_ld_pix, int64_t y_ld_img, void* stream);
+int32_t sgx_avgpool2_ceil_bwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dx,
+                              int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
 
 /* BatchNorm -> squeeze-excitation gate -> activation as fused sweeps (MobileNetV3's expanded InvertedResidual: dw -> BN -> SELayer -> act,
  * classification_models/mobilenetv3.py:103-108).  z = scale[c] * x + shift[c] (scale == shift == NULL: z = x, the folded eval form),

@@ -206,6 +206,12 @@ PROTOTYPES = {
     "sgx_gconv3x3_bwd_data": (_i32, [_CD, _i32, _P, _P, _P, _i32, _P, _i64, _P]),
     "sgx_gconv3x3_bwd_weight_workspace": (_i64, [_CD, _i32]),
     "sgx_gconv3x3_bwd_weight": (_i32, [_CD, _i32, _P, _P, _P, _P, _i64, _P]),
+    "sgx_dgconv3x3_stat_blocks": (_i32, [_CD, _i32, _i32, _P]),
+    "sgx_dgconv3x3_fwd": (_i32, [_CD, _i32, _i32, _P, _P, _P, _P, _P, _i32, _P, _P]),
+    "sgx_dgconv3x3_bwd_data": (_i32, [_CD, _i32, _i32, _P, _P, _P, _P, _i32, _P]),
+    "sgx_dgconv3x3_bwd_weight_workspace": (_i64, [_CD, _i32, _i32, _P]),
+    "sgx_dgconv3x3_bwd_weight": (_i32, [_CD, _i32, _i32, _P, _P, _P, _P, _P, _i64, _P]),
+    "sgx_debug_dgconv3x3_form": (_i32, [_CD, _i32, _i32, _P, _i32]),
     "sgx_pool3_conv1x1_stat_blocks": (_i32, [_i32] * 3),
     "sgx_pool3_conv1x1_fwd": (_i32, [_i32] * 5 + [_P, _i64, _i64, _P, _P, _P, _i64, _i64, _i32, _P, _P]),
     "sgx_pool3_conv1x1_bwd_data": (_i32, [_i32] * 5 + [_P, _i64, _i64, _P, _P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
@@ -256,6 +262,12 @@ PROTOTYPES = {
     "sgx_channel_gate": (_i32, [_i32] * 3 + [_P, _i64, _i64, _P, _i32, _P, _f, _P, _i64, _i64, _i32, _P]),
     "sgx_upsample2x_fwd": (_i32, [_i32] * 4 + [_P, _i64, _i64, _P, _i64, _i64, _P]),
     "sgx_upsample2x_bwd": (_i32, [_i32] * 4 + [_P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_bilinear_fwd": (_i32, [_i32] * 7 + [_P, _i64, _i64, _P, _i64, _i64, _P, _i64, _i64, _P]),
+    "sgx_bilinear_bwd": (_i32, [_i32] * 7 + [_P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_bilinear_nchw_fwd": (_i32, [_i32] * 7 + [_P, _i64, _i64, _P, _P]),
+    "sgx_bilinear_nchw_bwd": (_i32, [_i32] * 7 + [_P, _P, _i64, _i64, _P]),
+    "sgx_avgpool2_ceil_fwd": (_i32, [_i32] * 4 + [_P, _i64, _i64, _P, _i64, _i64, _P]),
+    "sgx_avgpool2_ceil_bwd": (_i32, [_i32] * 4 + [_P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
     "sgx_dfl_decode": (_i32, [_i32] * 4 + [_P] * 6 + [_P]),
     "sgx_targets_index": (_i32, [_P, _i32, _i32, _i32, _P, _P, _P, _P]),
     "sgx_ppyoloe_loss_workspace": (_i64, [_LD]),

@@ -1137,4 +1137,5 @@ extern "C" int32_t sgx_dwconv5x5_bwd_weight(const sgx_conv_desc* d, const float*
 
 // Grouped 3x3 convolution (1 < groups < C): MFMA tiles over an LDS patch; shares dw_check and the weight-gradient fold above.
 #include "gconv.h"
+#include "dilated.h"  // split-dilation grouped 3x3 (RegSeg): gconv's tiles, three ways of staging the dilated taps
 #include "inception.h"

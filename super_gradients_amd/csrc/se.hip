@@ -263,6 +263,9 @@ extern "C" int32_t sgx_upsample2x_bwd(int32_t N, int32_t H, int32_t W, int32_t C
     return SGX_OK;
 }
 
+// Bilinear interpolation (NHWC and the NCHW segmentation head) and the 2x2 ceil-mode average pool.
+#include "bilinear.h"
+
 // ---------------------------------------------------------------------------------------------
 // BatchNorm -> squeeze-excitation gate -> activation as fused sweeps (MobileNetV3's expanded block: dw -> BN -> SE -> act,
 // classification_models/mobilenetv3.py:103-108).  z = scale[c] * x + shift[c] (NULL scale / shift: z = x, the folded eval form),

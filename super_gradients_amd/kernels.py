@@ -663,6 +663,73 @@ def gconv3x3_bwd_weight(x, dy, dw, groups, stride=1):
     check(lib().sgx_gconv3x3_bwd_weight(d.ref, groups, ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel(), stream()), "sgx_gconv3x3_bwd_weight")
 
 
+# --------------------------------------------------------------------------------------------- split-dilation grouped 3x3 convolution
+def _dg_args(ws, C, cg, dilations):
+    """(nsplit, the int32 dilation list, the filter pointer list) of a launch; ws: one filter per split, logical [C / nsplit, cg, 3, 3] OHWI."""
+    ns = len(dilations)
+    if len(ws) != ns or ns == 0 or C % ns:
+        raise _lib.SgxError(f"dilated grouped convolution: {len(ws)} filters for {ns} dilations over C={C}")
+    for w in ws:
+        _chk_w(w, C // ns, 3, 3, cg)
+    return ns, (ctypes.c_int32 * ns)(*[int(v) for v in dilations]), (ctypes.c_void_p * ns)(*[ptr(w) for w in ws])
+
+
+def dgconv3x3_fwd(x, ws, cg, dilations, bias=None, out=None, act=None, stat_partials=False):
+    """y = act(cat_i(gconv(x_i, ws[i], dilation = padding = dilations[i])) + bias) in ONE launch: x_i the i-th of len(dilations) equal
+    channel splits of x, group width cg; stat_partials: also the BatchNorm statistics rows of y (then no bias / activation)."""
+    C = x.shape[3]
+    ns, dil, wp = _dg_args(ws, C, cg, dilations)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    d = conv_desc(x, C, 3, 3, 1, 1, out)
+    parts = None
+    if stat_partials:
+        nblk = lib().sgx_dgconv3x3_stat_blocks(d.ref, cg, ns, dil)
+        if nblk <= 0:
+            check(-1, "sgx_dgconv3x3_stat_blocks")
+        parts = torch.empty(2, nblk, C, device=x.device, dtype=torch.float32)
+    check(lib().sgx_dgconv3x3_fwd(d.ref, cg, ns, dil, wp, ptr(x), ptr(bias), ptr(out), ACT[act], ptr(parts), stream()), "sgx_dgconv3x3_fwd")
+    return (out, parts) if stat_partials else out
+
+
+def dgconv3x3_bwd_data(dy, ws, cg, dilations, out=None, accumulate=False):
+    C = dy.shape[3]
+    ns, dil, wp = _dg_args(ws, C, cg, dilations)
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("dgconv3x3_bwd_data: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(dy.shape, device=dy.device, dtype=torch.float32)
+    d = conv_desc(out, C, 3, 3, 1, 1, dy)
+    check(lib().sgx_dgconv3x3_bwd_data(d.ref, cg, ns, dil, ptr(dy), wp, ptr(out), int(accumulate), stream()), "sgx_dgconv3x3_bwd_data")
+    return out
+
+
+def dgconv3x3_bwd_weight(x, dy, dws, cg, dilations):
+    """dws[i] (logical [C / nsplit, cg, 3, 3], OHWI memory) += grad of split i."""
+    C = x.shape[3]
+    ns, dil, dp = _dg_args(dws, C, cg, dilations)
+    d = conv_desc(x, C, 3, 3, 1, 1, dy)
+    size = lib().sgx_dgconv3x3_bwd_weight_workspace(d.ref, cg, ns, dil)
+    if size <= 0:
+        check(-1, "sgx_dgconv3x3_bwd_weight_workspace")
+    ws = WORKSPACE.get(size, x.device)
+    check(lib().sgx_dgconv3x3_bwd_weight(d.ref, cg, ns, dil, ptr(x), ptr(dy), dp, ptr(ws), ws.numel(), stream()), "sgx_dgconv3x3_bwd_weight")
+
+
+def dgconv3x3_form(x_shape, cg, dilations, split):
+    """How split `split` stages its dilated taps on an [N,H,W,C] map: "halo", "band" or "tiles" (sgx_debug_dgconv3x3_form)."""
+    n, h, w, c = x_shape
+    d = _lib.ConvDesc()
+    d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = n, h, w, c, c, 3, 3, 1, 1, h, w
+    d.x_ld_pix = d.y_ld_pix = c
+    d.x_ld_img = d.y_ld_img = h * w * c
+    ns = len(dilations)
+    form = lib().sgx_debug_dgconv3x3_form(ctypes.byref(d), cg, ns, (ctypes.c_int32 * ns)(*dilations), split)
+    if form < 0:
+        check(form, "sgx_debug_dgconv3x3_form")
+    return ("halo", "band", "tiles")[form]
+
+
 # --------------------------------------------------------------------------------------------- max-pool 3x3 / 1 / 1 inside a 1x1 convolution
 def _chk_pw(w: torch.Tensor, ci):
     co = w.shape[0]
@@ -1445,6 +1512,86 @@ def upsample2x_bwd(dy, out=None, accumulate=False):
     dl, di = nhwc_strides(dy)
     xl, xi = nhwc_strides(out)
     check(lib().sgx_upsample2x_bwd(n, h, w, c, ptr(dy), dl, di, ptr(out), xl, xi, int(accumulate), stream()), "sgx_upsample2x_bwd")
+    return out
+
+
+def _scale2(scale):
+    return (int(scale), int(scale)) if isinstance(scale, int) else (int(scale[0]), int(scale[1]))
+
+
+def bilinear_fwd(x, scale, align_corners=False, addend=None, out=None):
+    """y = F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=...) (+ addend) on NHWC tensors or channel slices."""
+    n, h, w, c = x.shape
+    sh, sw = _scale2(scale)
+    if out is None:
+        out = torch.empty(n, sh * h, sw * w, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (n, sh * h, sw * w, c) or (addend is not None and addend.shape != out.shape):
+        raise _lib.SgxError(f"bilinear_fwd: output / addend shape does not match {(n, sh * h, sw * w, c)}")
+    (xl, xi), (yl, yi) = nhwc_strides(x), nhwc_strides(out)
+    al, ai = nhwc_strides(addend) if addend is not None else (0, 0)
+    check(lib().sgx_bilinear_fwd(n, h, w, c, sh, sw, int(align_corners), ptr(x), xl, xi, ptr(addend), al, ai, ptr(out), yl, yi, stream()), "sgx_bilinear_fwd")
+    return out
+
+
+def bilinear_bwd(dy, scale, align_corners=False, out=None, accumulate=False):
+    n, oh, ow, c = dy.shape
+    sh, sw = _scale2(scale)
+    h, w = oh // sh, ow // sw
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("bilinear_bwd: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(n, h, w, c, device=dy.device, dtype=torch.float32)
+    if (h * sh, w * sw) != (oh, ow) or tuple(out.shape) != (n, h, w, c):
+        raise _lib.SgxError(f"bilinear_bwd: dy {tuple(dy.shape)} is not {sh} x {sw} times dx {tuple(out.shape)}")
+    (dl, di), (xl, xi) = nhwc_strides(dy), nhwc_strides(out)
+    check(lib().sgx_bilinear_bwd(n, h, w, c, sh, sw, int(align_corners), ptr(dy), dl, di, ptr(out), xl, xi, int(accumulate), stream()), "sgx_bilinear_bwd")
+    return out
+
+
+def bilinear_nchw_fwd(x, scale, align_corners=False):
+    """The segmentation head: NHWC logits x (any C, any pixel stride) -> contiguous NCHW [N, C, sh H, sw W]."""
+    n, h, w, c = x.shape
+    sh, sw = _scale2(scale)
+    out = torch.empty(n, c, sh * h, sw * w, device=x.device, dtype=torch.float32)
+    xl, xi = nhwc_strides(x)
+    check(lib().sgx_bilinear_nchw_fwd(n, h, w, c, sh, sw, int(align_corners), ptr(x), xl, xi, ptr(out), stream()), "sgx_bilinear_nchw_fwd")
+    return out
+
+
+def bilinear_nchw_bwd(dy, scale, align_corners=False, out=None):
+    """NCHW dy -> the NHWC logit gradient (written, not added)."""
+    n, c, oh, ow = dy.shape
+    sh, sw = _scale2(scale)
+    h, w = oh // sh, ow // sw
+    if not dy.is_contiguous() or (h * sh, w * sw) != (oh, ow):
+        raise _lib.SgxError(f"bilinear_nchw_bwd: dy must be contiguous NCHW with extents {sh} x {sw} times the input's, got {tuple(dy.shape)}")
+    if out is None:
+        out = torch.empty(n, h, w, c, device=dy.device, dtype=torch.float32)
+    xl, xi = nhwc_strides(out)
+    check(lib().sgx_bilinear_nchw_bwd(n, h, w, c, sh, sw, int(align_corners), ptr(dy), ptr(out), xl, xi, stream()), "sgx_bilinear_nchw_bwd")
+    return out
+
+
+def avgpool2_ceil_fwd(x, out=None):
+    """nn.AvgPool2d(2, 2, ceil_mode=True) on NHWC."""
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty(n, (h + 1) // 2, (w + 1) // 2, c, device=x.device, dtype=torch.float32)
+    (xl, xi), (yl, yi) = nhwc_strides(x), nhwc_strides(out)
+    check(lib().sgx_avgpool2_ceil_fwd(n, h, w, c, ptr(x), xl, xi, ptr(out), yl, yi, stream()), "sgx_avgpool2_ceil_fwd")
+    return out
+
+
+def avgpool2_ceil_bwd(dy, x_shape, out=None, accumulate=False):
+    n, h, w, c = x_shape
+    if tuple(dy.shape) != (n, (h + 1) // 2, (w + 1) // 2, c):
+        raise _lib.SgxError(f"avgpool2_ceil_bwd: dy {tuple(dy.shape)} is not the pooled {tuple(x_shape)}")
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("avgpool2_ceil_bwd: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
+    (dl, di), (xl, xi) = nhwc_strides(dy), nhwc_strides(out)
+    check(lib().sgx_avgpool2_ceil_bwd(n, h, w, c, ptr(dy), dl, di, ptr(out), xl, xi, int(accumulate), stream()), "sgx_avgpool2_ceil_bwd")
     return out
 
 

@@ -5,6 +5,7 @@ Every class keeps the reference's parameter names and logical shapes (state_dict
   ConvLayer        nn.Conv2d                         weight [K,C,R,S] (+ bias)      modules/conv_bn_act_block.py:88
   DepthwiseConvLayer nn.Conv2d(C, C, k, s, k // 2, groups=C) weight [C,1,k,k], k = 3 / 5  classification_models/mobilenetv2.py:73,87, mobilenetv3.py:88,104
   GroupedConvLayer nn.Conv2d(C, C, 3, s, 1, groups=G), 1 < G < C   weight [C,C/G,3,3]    classification_models/regnet.py (XBlock), resnext.py (conv2)
+  DilatedGroupedConvLayer  the split-dilation grouped 3x3 of segmentation_models/regseg.py:95-149   weight / convs.{i}.weight
   BatchNorm        nn.BatchNorm2d                    weight, bias, running_mean, running_var, num_batches_tracked
   ConvTranspose2x2 nn.ConvTranspose2d(k=2,s=2)       weight [C,K,2,2], bias          modules/sampling.py:72-73
   LinearLayer      nn.Linear                         weight [K,C], bias              classification_models/resnet.py:186
@@ -262,6 +263,124 @@ class GroupedConvLayer(SgxBlock):
                 out = K.axpy(addend, out=out)
             accumulate = True
         return K.gconv3x3_bwd_data(dy, self._w, self.groups, x_shape, stride=self.stride, out=out, accumulate=accumulate)
+
+
+class _DilatedSplit(SgxBlock):
+    """Parameters of one split's nn.Conv2d(c, c, 3, padding=d, dilation=d, groups=c / cg, bias=False): key convs.{i}.weight."""
+
+    _param_kinds = {"weight": "conv"}
+
+    def __init__(self, channels, cg):
+        super().__init__()
+        self.in_channels = self.out_channels = channels
+        self.kernel_size = 3
+        w = torch.empty(channels, cg, 3, 3)
+        nn.init.kaiming_uniform_(w, a=math.sqrt(5))  # nn.Conv2d default
+        self.weight = nn.Parameter(w)
+        self.register_parameter("bias", None)
+
+    def on_materialize(self):
+        pass
+
+
+class DilatedGroupedConvLayer(SgxBlock):
+    """Split-dilation grouped 3x3 convolution, stride 1, group width 16 (csrc/dilated.h), with ConvLayer's interface: ONE launch over all
+    splits, no split or concat pass.  Keys are the reference's two forms (segmentation_models/regseg.py:95-149): one dilation - `weight`
+    [C, cg, 3, 3] (DBlock's plain nn.Conv2d); several - `convs.{i}.weight` [C / n, cg, 3, 3] (SplitDilatedGroupConvBlock).  Filters are
+    stored [K][3][3][cg] in the arena.  The weight gradient is forked to the side stream like GroupedConvLayer's.  Dilation [1] alone is
+    GroupedConvLayer's."""
+
+    _param_kinds = {"weight": "conv"}
+    depthwise = False
+    grouped = True
+
+    def __init__(self, channels, dilations, group_width=16):
+        super().__init__()
+        dilations = [int(d) for d in dilations]
+        n = len(dilations)
+        if group_width != 16:
+            raise NotImplementedError(f"dilated grouped convolution on the HIP path: group width 16, got {group_width}")
+        if not 1 <= n <= 4 or channels % n or (channels // n) % group_width or min(dilations) < 1:
+            raise NotImplementedError(f"dilated grouped convolution on the HIP path: 1 - 4 equal splits of whole groups, dilations >= 1; got {channels} "
+                                      f"channels, dilations {dilations}")
+        self.in_channels = self.out_channels = channels
+        self.dilations, self.group_width = dilations, group_width
+        self.kernel_size, self.stride, self.padding = 3, 1, 1
+        if n == 1:
+            w = torch.empty(channels, group_width, 3, 3)
+            nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+            self.weight = nn.Parameter(w)
+            self.register_parameter("bias", None)
+        else:
+            self.convs = nn.ModuleList(_DilatedSplit(channels // n, group_width) for _ in dilations)
+        self._ws = self._gws = None
+
+    def _params(self):
+        return [self.weight] if len(self.dilations) == 1 else [c.weight for c in self.convs]
+
+    def on_materialize(self):
+        slots = {s.param: s for s in self._net.slots}
+        self._ws = [slots[p].kernel_view for p in self._params()]
+        self._gws = [slots[p].grad_kernel_view for p in self._params()]
+
+    def conv(self, x, out=None, act=None, addend=None, stats=False):
+        if addend is not None:
+            raise NotImplementedError("the dilated grouped convolution has no pre-activation addend")
+        return K.dgconv3x3_fwd(x, self._ws, self.group_width, self.dilations, out=out, act=act, stat_partials=stats)
+
+    def conv_with(self, x, ws, bias, out=None, act=None):
+        """act(conv(x, ws) + bias) with filters (one per split) that are not the parameters"""
+        return K.dgconv3x3_fwd(x, ws, self.group_width, self.dilations, bias=bias, out=out, act=act)
+
+    def wgrad(self, x, dy, bias_grad=True):
+        self._net.fork_side(lambda: K.dgconv3x3_bwd_weight(x, dy, self._gws, self.group_width, self.dilations), x, dy)
+
+    def dgrad(self, dy, x_shape, out=None, accumulate=False, addend=None, reqs=None):
+        if reqs:  # (the producing layer would skip its own reduce sweep and read rows nobody wrote)
+            raise NotImplementedError("the dilated grouped data gradient carries no BatchNorm-reduce requests")
+        if addend is not None:  # no addend operand in the kernel: the addend becomes the tensor the gradient is added to
+            if accumulate:
+                K.axpy(addend, out=out, accumulate=True)
+            else:
+                out = K.axpy(addend, out=out)
+            accumulate = True
+        return K.dgconv3x3_bwd_data(dy, self._ws, self.group_width, self.dilations, out=out, accumulate=accumulate)
+
+
+class BilinearUpsample(SgxBlock):
+    """nn.Upsample(scale_factor=s, mode="bilinear", align_corners=...) on NHWC maps (csrc/bilinear.h); no state.  fwd takes an optional
+    addend (y = up(x) + addend in the same pass) and may write into a channel slice; the addend's gradient is the caller's."""
+
+    def __init__(self, scale_factor, align_corners=False):
+        super().__init__()
+        self.scale_factor, self.align_corners = int(scale_factor), bool(align_corners)
+
+    def on_materialize(self):
+        pass
+
+    def fwd(self, x, out=None, addend=None):
+        return K.bilinear_fwd(x, self.scale_factor, self.align_corners, addend=addend, out=out)
+
+    def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
+        if addend is not None:
+            raise NotImplementedError("BilinearUpsample.bwd: no addend")
+        return K.bilinear_bwd(dy, self.scale_factor, self.align_corners, out=dx_out, accumulate=accumulate)
+
+
+class AvgPool2Ceil(SgxBlock):
+    """nn.AvgPool2d(2, 2, ceil_mode=True) on NHWC maps; no state."""
+
+    def on_materialize(self):
+        pass
+
+    def fwd(self, x, out=None):
+        self._shape = tuple(x.shape)
+        return K.avgpool2_ceil_fwd(x, out=out)
+
+    def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
+        if addend is not None:
+            raise NotImplementedError("AvgPool2Ceil.bwd: no addend")
+        return K.avgpool2_ceil_bwd(dy, self._shape, out=dx_out, accumulate=accumulate)
 
 
 class BatchNorm(SgxBlock):

@@ -16,3 +16,4 @@ from .classification_models import GoogleNetV1, GoogLeNet  # noqa: F401
 from .classification_models import ViT, ViTBase, ViTHuge, ViTLarge  # noqa: F401
 from .classification_models import Beit, BeitBasePatch16_224, BeitLargePatch16_224  # noqa: F401
 from .detection_models.pp_yolo_e.pp_yolo_e import PPYoloE, PPYoloE_L, PPYoloE_M, PPYoloE_S, PPYoloE_X  # noqa: F401
+from .segmentation_models import RegSeg, RegSeg48  # noqa: F401
