@@ -1021,6 +1021,30 @@ int32_t sgx_softmax_ce_fwd_bwd(int32_t B, int32_t K, const float* logits, const 
                                int32_t ignore_index, int32_t reduction_sum, float* loss, float* dlogits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Segmentation: per-pixel cross-entropy and confusion counts over the class planes of a contiguous NCHW map [N, C, P = H*W]
+ * (csrc/segloss.h).  Lanes run along the pixel axis; 16-byte accesses when P % 4 == 0 and the bases are 16-byte
+ * aligned, 4-byte accesses otherwise.  N <= 65535, P <= 2^30.
+ * ------------------------------------------------------------------------------------------- */
+/* Number of per-workgroup partial sums of a seg_ce launch on [N, C, P].                                                             */
+int32_t sgx_seg_ce_blocks(int32_t N, int32_t P);
+/* F.cross_entropy(logits [N,C,H,W], labels [N,H,W] int64, weight, ignore_index, "mean" | "sum"), forward and gradient in one launch.
+ * A pixel whose label is ignore_index (which may lie outside [0, C)), or is outside [0, C), contributes nothing and gets a zero gradient in
+ * every class plane.  "mean" = sum w[y] * nll / sum w[y] over the other pixels; none left: nan.  weight may be NULL.
+ * C <= 32: the class values of a pixel stay in registers (map read once, gradient written once); larger C: an online max / rescaled sum pass
+ * and a second pass over the planes (map read twice).  Per-workgroup partial sums are folded in a fixed order in fp64: results repeat bit
+ * for bit.  loss: 2 * (the block count above) + 2 floats; loss[0] = the loss, loss[1] = 1 / denominator; dlogits [N,C,P] = d(numerator) /
+ * d logits (multiply by loss[1] and the upstream gradient, as for the 2-D entry point).                                             */
+int32_t sgx_seg_ce_fwd_bwd(int32_t N, int32_t C, int32_t P, const float* logits, const int64_t* labels, const float* weight,
+                           int32_t ignore_index, int32_t reduction_sum, float* loss, float* dlogits, void* stream);
+/* counts [num_bins + 1][num_bins] int64 += the confusion counts of arg-max over C (lowest class wins a tie; NaN not handled) against the
+ * labels: row = label, column = prediction; row num_bins collects labels outside [0, num_bins).  Pixels whose label equals one of the first
+ * n_ignore (0..4) ignore values are skipped.  C <= num_bins <= 192 (a workgroup's private 32-bit matrix lives in LDS).  Integer atomics
+ * only: exact, order-independent.  The caller zeroes counts.                                                                        */
+int32_t sgx_seg_confusion(int32_t N, int32_t C, int32_t P, const float* logits, const int64_t* labels, int32_t num_bins,
+                          int32_t n_ignore, int64_t ignore0, int64_t ignore1, int64_t ignore2, int64_t ignore3, int64_t* counts,
+                          void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimizer / EMA over flat fp32 arenas (one launch per arena instead of ~500 tiny ATen kernels):
  * sg_trainer.py:639-644, training/utils/ema.py:126-141, optimizer_utils.py:32-59.
  * seg_end[nseg] (int64, ascending, device) splits the arena into segments with per-segment weight

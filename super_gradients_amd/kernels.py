@@ -2093,6 +2093,46 @@ def softmax_ce(logits, labels, smoothing=0.0, weight=None, ignore_index=-100, re
     return loss[0], dlogits, loss[1:2]
 
 
+def _seg_map(logits, labels, what):
+    """(N, C, P, logits, labels) of a contiguous fp32 NCHW map and its int64 [N, H, W] labels."""
+    if logits.dim() != 4 or labels.dim() != 3 or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise _lib.SgxError(f"{what}: logits [N, C, H, W] with integer labels [N, H, W]; got {tuple(logits.shape)} and {labels.dtype} {tuple(labels.shape)}")
+    N, C, H, W = logits.shape
+    if tuple(labels.shape) != (N, H, W) or logits.dtype != torch.float32 or labels.device != logits.device:
+        raise _lib.SgxError(f"{what}: fp32 logits {tuple(logits.shape)} need labels {(N, H, W)} on the same device; got {logits.dtype}, {tuple(labels.shape)} on {labels.device}")
+    return N, C, H * W, logits.contiguous(), labels.contiguous().long()
+
+
+def seg_ce(logits, labels, weight=None, ignore_index=-100, reduction="mean"):
+    """F.cross_entropy of an NCHW map [N, C, H, W] against labels [N, H, W] (sgx_seg_ce_fwd_bwd)
+    -> (loss scalar, dlogits [N, C, H, W] without the 1 / denominator factor, the device scalar 1 / denominator): softmax_ce's convention."""
+    N, C, P, logits, labels = _seg_map(logits, labels, "seg_ce")  # bound to names: alive until the launch is enqueued
+    loss = torch.empty(2 * lib().sgx_seg_ce_blocks(N, P) + 2, device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits)
+    weight = weight.contiguous().float() if weight is not None else None
+    if weight is not None and weight.numel() != C:
+        raise _lib.SgxError(f"seg_ce: {weight.numel()} class weights for {C} classes")
+    check(lib().sgx_seg_ce_fwd_bwd(N, C, P, ptr(logits), ptr(labels), ptr(weight), int(ignore_index), int(reduction == "sum"), ptr(loss), ptr(dlogits), stream()),
+          "sgx_seg_ce_fwd_bwd")
+    return loss[0], dlogits, loss[1:2]
+
+
+def seg_confusion(logits, labels, num_bins, ignore_labels=(), counts=None):
+    """counts int64 [num_bins + 1, num_bins] += confusion counts of argmax(logits, 1) against labels (row = label, column = prediction; the
+    last row: labels outside [0, num_bins)); pixels labelled with one of the up to 4 ignore_labels are skipped (sgx_seg_confusion).
+    counts=None starts a zeroed matrix.  One launch, nothing read back."""
+    N, C, P, logits, labels = _seg_map(logits, labels, "seg_confusion")
+    ig = [int(v) for v in ignore_labels]
+    if len(ig) > 4:
+        raise _lib.SgxError(f"seg_confusion: at most 4 ignore labels, got {len(ig)}")
+    if counts is None:
+        counts = torch.zeros(num_bins + 1, num_bins, device=logits.device, dtype=torch.int64)
+    elif tuple(counts.shape) != (num_bins + 1, num_bins) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != logits.device:
+        raise _lib.SgxError(f"seg_confusion: counts must be a contiguous int64 [{num_bins + 1}, {num_bins}] tensor on the logits' device")
+    check(lib().sgx_seg_confusion(N, C, P, ptr(logits), ptr(labels), int(num_bins), len(ig), *(ig + [0] * (4 - len(ig))), ptr(counts), stream()), "sgx_seg_confusion")
+    return counts
+
+
 # --------------------------------------------------------------------------------------------- optimizer
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, step, seg_end, seg_wd, grad_scale=None):
     check(lib().sgx_adamw_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, ptr(seg_end), ptr(seg_wd), seg_end.numel(),

@@ -25,8 +25,8 @@ head.head.0.seq.*, head.head.1.{weight,bias}):
 The stem's convolution has a bias in front of its BatchNorm, as the reference's: statistics are taken of conv + bias in the epilogue.
 
 Not built (each raises NotImplementedError): RegSeg53 (group width 24, unregistered in the reference); stride 2 together with a dilation above
-1 (RegSeg never combines them); head dropout > 0; half-precision inference; nearest / other interpolation modes; any segmentation loss,
-metric or Trainer recipe.
+1 (RegSeg never combines them); head dropout > 0; half-precision inference; nearest / other interpolation modes.
+Training: CrossEntropyLoss on the NCHW logits and the PixelAccuracy / IoU metrics run on csrc/segloss.h.
 """
 from typing import Dict
 
