@@ -1043,6 +1043,18 @@ int32_t sgx_seg_ce_fwd_bwd(int32_t N, int32_t C, int32_t P, const float* logits,
 int32_t sgx_seg_confusion(int32_t N, int32_t C, int32_t P, const float* logits, const int64_t* labels, int32_t num_bins,
                           int32_t n_ignore, int64_t ignore0, int64_t ignore1, int64_t ignore2, int64_t ignore3, int64_t* counts,
                           void* stream);
+/* Online hard example mining over the per-pixel cross-entropy (csrc/seg_ohem.h; the reference's OhemLoss.forward).
+ * l = the pixel's cross-entropy, 0 where the label is ignore_index.  The set: every pixel (exclude_ignored = 0; ignored ones take part
+ * with 0) or the pixels that are not ignored.  num_mining = min(int(mining_percent * |set|), |set| - 1), the product in fp64.
+ * More than num_mining losses above thresh: the mean of the l > thresh.  Otherwise the mean of the num_mining largest, found by a radix
+ * selection of that rank on the device (no sort, nothing read back); bit-equal losses at the rank share the remaining weight equally.
+ * num_mining = 0 there: nan, zero gradient.  Empty set: 0, zero gradient.  loss: one float; dlogits [N,C,P] = d loss / d logits, zero in
+ * every plane of a pixel that is not selected or is ignored.  Results repeat bit for bit.  ws: the byte count below, 16-byte aligned;
+ * the call zeroes what it needs zeroed.  N <= 65535, P <= 2^30.                                                                      */
+int64_t sgx_seg_ohem_ws_bytes(int32_t N, int32_t P);
+int32_t sgx_seg_ohem_ce_fwd_bwd(int32_t N, int32_t C, int32_t P, const float* logits, const int64_t* labels, int32_t ignore_index,
+                                float thresh, double mining_percent, int32_t exclude_ignored, void* ws, int64_t ws_bytes, float* loss,
+                                float* dlogits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimizer / EMA over flat fp32 arenas (one launch per arena instead of ~500 tiny ATen kernels):

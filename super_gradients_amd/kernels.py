@@ -2117,6 +2117,21 @@ def seg_ce(logits, labels, weight=None, ignore_index=-100, reduction="mean"):
     return loss[0], dlogits, loss[1:2]
 
 
+def seg_ohem_ce(logits, labels, threshold, mining_percent=0.1, ignore_index=-100, exclude_ignored=True):
+    """Online hard example mining over the per-pixel cross-entropy of an NCHW map (sgx_seg_ohem_ce_fwd_bwd; the reference's OhemCELoss):
+    the mean of the losses above -log(threshold) (taken in fp32, as the reference's `thresh`) when more than num_mining pixels exceed it, else the
+    mean of the num_mining largest -> (loss scalar, dlogits [N, C, H, W] = d loss / d logits).  Selection by rank on the device, nothing read back."""
+    N, C, P, logits, labels = _seg_map(logits, labels, "seg_ohem_ce")  # bound to names: alive until the launch is enqueued
+    threshold = -torch.log(torch.tensor(float(threshold), dtype=torch.float32))  # (a host tensor: no device read)
+    nbytes = lib().sgx_seg_ohem_ws_bytes(N, P)
+    ws = WORKSPACE.get(nbytes, logits.device)
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits)
+    check(lib().sgx_seg_ohem_ce_fwd_bwd(N, C, P, ptr(logits), ptr(labels), int(ignore_index), float(threshold), float(mining_percent), int(bool(exclude_ignored)),
+                                        ptr(ws), nbytes, ptr(loss), ptr(dlogits), stream()), "sgx_seg_ohem_ce_fwd_bwd")
+    return loss[0], dlogits
+
+
 def seg_confusion(logits, labels, num_bins, ignore_labels=(), counts=None):
     """counts int64 [num_bins + 1, num_bins] += confusion counts of argmax(logits, 1) against labels (row = label, column = prediction; the
     last row: labels outside [0, num_bins)); pixels labelled with one of the up to 4 ignore_labels are skipped (sgx_seg_confusion).
