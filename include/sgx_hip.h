@@ -1055,6 +1055,37 @@ int64_t sgx_seg_ohem_ws_bytes(int32_t N, int32_t P);
 int32_t sgx_seg_ohem_ce_fwd_bwd(int32_t N, int32_t C, int32_t P, const float* logits, const int64_t* labels, int32_t ignore_index,
                                 float thresh, double mining_percent, int32_t exclude_ignored, void* ws, int64_t ws_bytes, float* loss,
                                 float* dlogits, void* stream);
+/* Region losses: Dice, IoU, their generalized forms and BCE + Dice (csrc/seg_struct.h; the reference's structure_loss.py).
+ * p = act(x) over x [N,C,P] fp32.  target: int64 labels [N,P] (a label y lands in channel y - (y > ignore_index) when SGX_SEG_STRUCT_HAS_IGNORE
+ * is set, else in channel y; label == ignore_index or a channel outside [0, C): the pixel is invalid, masked out of every sum, zero gradient
+ * in every plane), or a dense [N,C,P] map of floats / int64 taken as it is (sigmoid and identity only; every pixel valid).
+ * Per (n, c): I = sum v t p, D = sum v p + sum t (- I with SGX_SEG_STRUCT_IOU), T = sum t; summed over n (groups = classes, G = C) or over
+ * c (SGX_SEG_STRUCT_OVER_BATCHES, G = N); SGX_SEG_STRUCT_GENERALIZED multiplies I and D by 1 / T^2 (inf -> 0);
+ * loss_g = 1 - (k I + smooth) / (D + eps + smooth), k = 2 (Dice) or 1 (IoU), times weight[g] (may be NULL; classes as groups only);
+ * result = w_dice * mean (default) | sum | none over g, + w_bce * mean BCE-with-logits(x, t) with SGX_SEG_STRUCT_BCE (dense, mean only).
+ * fwd: a moment pass (one row of partial sums per workgroup; integer counts; no float atomic) and a one-workgroup finalize that folds in
+ * fp64 in index order.  loss: one float, or G floats for none.  coef: 2 N C + 1 floats for bwd.  ws: the byte count below, 16-byte aligned.
+ * bwd: dx [N,C,P] = d result / d x times grad_out (device memory: one float, or G floats for none), written once.  Results repeat bit
+ * for bit.  N <= 65535, P <= 2^30; labels: C <= 1024; dense: N * C <= 65535.                                                             */
+#define SGX_SEG_STRUCT_SOFTMAX 0
+#define SGX_SEG_STRUCT_SIGMOID 1
+#define SGX_SEG_STRUCT_IDENTITY 2
+#define SGX_SEG_STRUCT_ACT_MASK 3
+#define SGX_SEG_STRUCT_DENSE_F32 4
+#define SGX_SEG_STRUCT_DENSE_I64 8
+#define SGX_SEG_STRUCT_HAS_IGNORE 16
+#define SGX_SEG_STRUCT_IOU 32
+#define SGX_SEG_STRUCT_OVER_BATCHES 64
+#define SGX_SEG_STRUCT_GENERALIZED 128
+#define SGX_SEG_STRUCT_SUM 256
+#define SGX_SEG_STRUCT_NONE 512
+#define SGX_SEG_STRUCT_BCE 1024
+int64_t sgx_seg_struct_ws_bytes(int32_t N, int32_t C, int32_t P, int32_t flags);
+int32_t sgx_seg_struct_fwd(int32_t N, int32_t C, int32_t P, const float* x, const void* target, int32_t flags, int32_t ignore_index,
+                           double smooth, double eps, double w_bce, double w_dice, const float* weight, void* ws, int64_t ws_bytes,
+                           float* loss, float* coef, void* stream);
+int32_t sgx_seg_struct_bwd(int32_t N, int32_t C, int32_t P, const float* x, const void* target, int32_t flags, int32_t ignore_index,
+                           const float* coef, const float* grad_out, float* dx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimizer / EMA over flat fp32 arenas (one launch per arena instead of ~500 tiny ATen kernels):

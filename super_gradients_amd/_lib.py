@@ -287,6 +287,9 @@ PROTOTYPES = {
     "sgx_seg_confusion": (_i32, [_i32, _i32, _i32, _P, _P, _i32, _i32, _i64, _i64, _i64, _i64, _P, _P]),
     "sgx_seg_ohem_ws_bytes": (_i64, [_i32, _i32]),
     "sgx_seg_ohem_ce_fwd_bwd": (_i32, [_i32, _i32, _i32, _P, _P, _i32, _f, _d, _i32, _P, _i64, _P, _P, _P]),
+    "sgx_seg_struct_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "sgx_seg_struct_fwd": (_i32, [_i32, _i32, _i32, _P, _P, _i32, _i32, _d, _d, _d, _d, _P, _P, _i64, _P, _P, _P]),
+    "sgx_seg_struct_bwd": (_i32, [_i32, _i32, _i32, _P, _P, _i32, _i32, _P, _P, _P, _P]),
     "sgx_adamw_step": (_i32, [_P, _P, _P, _P, _i64, _f, _f, _f, _f, _i32, _P, _P, _i32, _P, _P]),
     "sgx_sgd_step": (_i32, [_P, _P, _P, _i64, _f, _f, _f, _i32, _i32, _P, _P, _i32, _P]),
     "sgx_adam_step": (_i32, [_P, _P, _P, _P, _i64, _d, _d, _d, _d, _i32, _P, _P, _i32, _P, _P]),

@@ -847,3 +847,4 @@ extern "C" int32_t sgx_softmax_ce_fwd_bwd(int32_t B, int32_t K, const float* log
 
 #include "segloss.h"  // per-pixel cross-entropy and confusion counts over NCHW class planes (segmentation); folds through ce_reduce_kernel
 #include "seg_ohem.h"  // hard-pixel mining over that cross-entropy: radix selection by rank on the device, no sort, no read-back
+#include "seg_struct.h"  // Dice / IoU / BCE-Dice: per-class moments in one pass, a coefficient table, the gradient written once

@@ -2132,6 +2132,64 @@ def seg_ohem_ce(logits, labels, threshold, mining_percent=0.1, ignore_index=-100
     return loss[0], dlogits
 
 
+SEG_STRUCT_ACT = {"softmax": 0, "sigmoid": 1, "identity": 2}  # include/sgx_hip.h SGX_SEG_STRUCT_*
+SEG_STRUCT_DENSE_F32, SEG_STRUCT_DENSE_I64, SEG_STRUCT_HAS_IGNORE, SEG_STRUCT_IOU, SEG_STRUCT_OVER_BATCHES, SEG_STRUCT_GENERALIZED = 4, 8, 16, 32, 64, 128
+SEG_STRUCT_REDUCTION = {"mean": 0, "sum": 256, "none": 512}
+SEG_STRUCT_BCE = 1024
+
+
+def seg_struct_fwd(x, target, act="softmax", iou=False, reduce_over_batches=False, generalized=False, reduction="mean", ignore_index=None, smooth=1.0,
+                   eps=1e-5, weight=None, bce_weight=None, dice_weight=1.0):
+    """Dice (iou=False) or IoU loss of p = act(x), x [N, C, H, W] fp32, against integer labels [N, H, W] (one-hot on the device; a label y lands in
+    channel y - (y > ignore_index), pixels labelled ignore_index or outside the C channels are masked out) or a dense [N, C, H, W] target of floats or
+    integers (sigmoid / identity only) (sgx_seg_struct_fwd; the reference's DiceLoss / IoULoss and their Binary / Generalized forms).  Groups are the
+    classes over the batch, or the images over their classes; bce_weight adds bce_weight * mean BCE-with-logits(x, target) to dice_weight * the loss
+    (BCEDiceLoss) in the same pass over the map.
+    -> (loss: a scalar, or [G] for reduction "none"; ctx for seg_struct_bwd).  One moment pass and a one-workgroup finalize, nothing read back."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise _lib.SgxError(f"seg_struct: an fp32 map [N, C, H, W] is needed; got {x.dtype} {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    flags = SEG_STRUCT_ACT[act] | SEG_STRUCT_REDUCTION[reduction] | (SEG_STRUCT_IOU if iou else 0) | (SEG_STRUCT_OVER_BATCHES if reduce_over_batches else 0) | (
+        SEG_STRUCT_GENERALIZED if generalized else 0) | (SEG_STRUCT_BCE if bce_weight is not None else 0)
+    if tuple(target.shape) == (N, C, H, W):
+        if ignore_index is not None:
+            raise ValueError("seg_struct: a dense target has no ignore_index")
+        if act == "softmax":
+            raise NotImplementedError("seg_struct: softmax against a dense target is not built; pass labels [N, H, W] or probabilities with apply_softmax=False")
+        flags |= SEG_STRUCT_DENSE_F32 if target.is_floating_point() else SEG_STRUCT_DENSE_I64
+        target = target.float() if target.is_floating_point() else target.long()
+    elif tuple(target.shape) == (N, H, W) and not target.is_floating_point() and target.dtype != torch.bool:
+        flags |= SEG_STRUCT_HAS_IGNORE if ignore_index is not None else 0
+        target = target.long()
+    else:
+        raise _lib.SgxError(f"seg_struct: integer labels {(N, H, W)} or a dense target {(N, C, H, W)} are needed; got {target.dtype} {tuple(target.shape)}")
+    x, target = x.contiguous(), target.to(x.device).contiguous()  # bound to names: alive until the launch is enqueued
+    G = N if reduce_over_batches else C
+    if weight is not None:
+        if reduce_over_batches or generalized or weight.numel() != C:
+            raise ValueError(f"seg_struct: class weights need the {C} classes as groups")
+        weight = weight.to(x.device).contiguous().float()
+    nbytes = lib().sgx_seg_struct_ws_bytes(N, C, H * W, flags)
+    ws = WORKSPACE.get(nbytes, x.device)
+    loss = torch.empty(G if reduction == "none" else 1, device=x.device, dtype=torch.float32)
+    coef = torch.empty(2 * N * C + 1, device=x.device, dtype=torch.float32)
+    ig = 0 if ignore_index is None else int(ignore_index)
+    check(lib().sgx_seg_struct_fwd(N, C, H * W, ptr(x), ptr(target), flags, ig, float(smooth), float(eps), float(bce_weight or 0.0), float(dice_weight),
+                                   ptr(weight), ptr(ws), nbytes, ptr(loss), ptr(coef), stream()), "sgx_seg_struct_fwd")
+    return (loss if reduction == "none" else loss[0]), (x, target, flags, ig, coef)
+
+
+def seg_struct_bwd(ctx, grad_out):
+    """d result / d x of seg_struct_fwd times the upstream gradient (a device scalar, or [G] for reduction "none") (sgx_seg_struct_bwd): one pass that
+    reloads the map and the target, recomputes p and writes dx once, already scaled."""
+    x, target, flags, ig, coef = ctx
+    N, C, H, W = x.shape
+    grad_out = grad_out.reshape(-1).contiguous().float()  # bound to a name: alive until the launch is enqueued
+    dx = torch.empty_like(x)
+    check(lib().sgx_seg_struct_bwd(N, C, H * W, ptr(x), ptr(target), flags, ig, ptr(coef), ptr(grad_out), ptr(dx), stream()), "sgx_seg_struct_bwd")
+    return dx
+
+
 def seg_confusion(logits, labels, num_bins, ignore_labels=(), counts=None):
     """counts int64 [num_bins + 1, num_bins] += confusion counts of argmax(logits, 1) against labels (row = label, column = prediction; the
     last row: labels outside [0, num_bins)); pixels labelled with one of the up to 4 ignore_labels are skipped (sgx_seg_confusion).
