@@ -722,6 +722,38 @@ int32_t sgx_avgpool2_ceil_fwd(int32_t N, int32_t H, int32_t W, int32_t C, const 
 int32_t sgx_avgpool2_ceil_bwd(int32_t N, int32_t H, int32_t W, int32_t C, const float* dy, int64_t dy_ld_pix, int64_t dy_ld_img, float* dx,
                               int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
 
+/* DDRNet's DAPPM context module (segmentation_models/ddrnet.py: DAPPMBranch :44-105, DAPPM :108-137; kernels in csrc/dappm.h).  All maps
+ * NHWC fp32, C a multiple of 4, strides and addresses multiples of 16 bytes, N <= 65535 (SGX_ERR_BAD_ARG otherwise).  No atomics: two calls
+ * give the same bits.
+ * sgx_dappm_pool_fwd: every nn.AvgPool2d(k, s, padding=s) of the module and its nn.AdaptiveAvgPool2d(1) from ONE read of x, one launch.
+ *   levels: nlev <= 3 host triples (kernel, stride, padding) with 1 <= stride <= 8, 2 stride <= kernel <= 17, padding == stride (anything
+ *   else, a fourth level included: SGX_ERR_BAD_ARG); p0 .. p2: the contiguous pooled maps [N, Ho, Wo, C], Ho = (H + 2 p - k) / s + 1, the
+ *   divisor always k^2 (count_include_pad); has_global: pg [N, C] = the mean over H W.  x may be a channel slice.
+ *   partials (may be NULL): [T][2][N][C], T = 1 + nlev + has_global, tensor order x, the window levels, the global level - each [2][N][C]
+ *   block is the per-channel sum / sum of squares of that map in the row layout sgx_bn_finalize / sgx_bn_reduce_sums read (nblk = N: one
+ *   row per image).  x's rows serve every BatchNorm that normalises x itself (the stride-1 branch's and the shortcut's).
+ *   The plane is staged in LDS: (H W + sum_l H Wo_l) * 16 bytes must fit 78 KB (16 x 32 uses 15; SGX_ERR_UNSUPPORTED above - about 2500
+ *   pixels, a 3200 x 3200 image at 1/64; tiling the rows is not built).
+ * sgx_dappm_pool_bwd: dx (+)= sum_l (1 / k_l^2) sum over the windows of level l that cover the pixel of d_l + dg / (H W) + a1 + a2 - a
+ *   gather, dx written once.  d0 .. d2: contiguous [N, Ho, Wo, C]; dg [N, C] (NULL: no global level); a1, a2: optional addends shaped like x
+ *   (the gradients reaching x through the stride-1 branch and the shortcut).
+ * sgx_resize_bilinear_fwd: y [N, Ho, Wo, C] = F.interpolate(z [N, Hi, Wi, C], size=(Ho, Wo), mode="bilinear", align_corners=False) (+ addend),
+ *   any sizes (Hi = Wi = 1: a broadcast; Ho = Hi: a copy), ATen's float arithmetic: scale = in / out, src = max(0, (o + 0.5) scale - 0.5).
+ *   partials (may be NULL): [2][N * sgx_resize_bilinear_row_tiles(N, Hi, Wi, Ho, C)][C] sum / sum of squares of the y stored.  The source
+ *   map is staged in LDS (Hi Wi * 16 bytes <= 78 KB, SGX_ERR_UNSUPPORTED above).
+ * sgx_resize_bilinear_bwd: dz (+)= A^T dy, a separable gather (row sums in LDS: Ho Wi * 16 bytes <= 80 KB).                              */
+int32_t sgx_dappm_pool_fwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t nlev, const int32_t* levels, int32_t has_global, const float* x,
+                           int64_t x_ld_pix, int64_t x_ld_img, float* p0, float* p1, float* p2, float* pg, float* partials, void* stream);
+int32_t sgx_dappm_pool_bwd(int32_t N, int32_t H, int32_t W, int32_t C, int32_t nlev, const int32_t* levels, const float* d0, const float* d1,
+                           const float* d2, const float* dg, const float* a1, int64_t a1_ld_pix, int64_t a1_ld_img, const float* a2,
+                           int64_t a2_ld_pix, int64_t a2_ld_img, float* dx, int64_t dx_ld_pix, int64_t dx_ld_img, int32_t accumulate, void* stream);
+int32_t sgx_resize_bilinear_row_tiles(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t C);
+int32_t sgx_resize_bilinear_fwd(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t C, const float* z, int64_t z_ld_pix,
+                                int64_t z_ld_img, const float* addend, int64_t a_ld_pix, int64_t a_ld_img, float* y, int64_t y_ld_pix,
+                                int64_t y_ld_img, float* partials, void* stream);
+int32_t sgx_resize_bilinear_bwd(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t C, const float* dy, int64_t dy_ld_pix,
+                                int64_t dy_ld_img, float* dz, int64_t dz_ld_pix, int64_t dz_ld_img, int32_t accumulate, void* stream);
+
 /* BatchNorm -> squeeze-excitation gate -> activation as fused sweeps (MobileNetV3's expanded InvertedResidual: dw -> BN -> SELayer -> act,
  * classification_models/mobilenetv3.py:103-108).  z = scale[c] * x + shift[c] (scale == shift == NULL: z = x, the folded eval form),
  * s = f(pre[n][c]) (SGX_GATE_*), y = act(s * z) (any SGX_ACT_*).  Rows are the N * HW pixels, uniformly strided (x_ld ...); row r belongs

@@ -268,6 +268,11 @@ PROTOTYPES = {
     "sgx_bilinear_nchw_bwd": (_i32, [_i32] * 7 + [_P, _P, _i64, _i64, _P]),
     "sgx_avgpool2_ceil_fwd": (_i32, [_i32] * 4 + [_P, _i64, _i64, _P, _i64, _i64, _P]),
     "sgx_avgpool2_ceil_bwd": (_i32, [_i32] * 4 + [_P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_dappm_pool_fwd": (_i32, [_i32] * 5 + [_P, _i32, _P, _i64, _i64, _P, _P, _P, _P, _P, _P]),
+    "sgx_dappm_pool_bwd": (_i32, [_i32] * 5 + [_P] * 5 + [_P, _i64, _i64, _P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
+    "sgx_resize_bilinear_row_tiles": (_i32, [_i32] * 5),
+    "sgx_resize_bilinear_fwd": (_i32, [_i32] * 6 + [_P, _i64, _i64, _P, _i64, _i64, _P, _i64, _i64, _P, _P]),
+    "sgx_resize_bilinear_bwd": (_i32, [_i32] * 6 + [_P, _i64, _i64, _P, _i64, _i64, _i32, _P]),
     "sgx_dfl_decode": (_i32, [_i32] * 4 + [_P] * 6 + [_P]),
     "sgx_targets_index": (_i32, [_P, _i32, _i32, _i32, _P, _P, _P, _P]),
     "sgx_ppyoloe_loss_workspace": (_i64, [_LD]),

@@ -1139,3 +1139,4 @@ extern "C" int32_t sgx_dwconv5x5_bwd_weight(const sgx_conv_desc* d, const float*
 #include "gconv.h"
 #include "dilated.h"  // split-dilation grouped 3x3 (RegSeg): gconv's tiles, three ways of staging the dilated taps
 #include "inception.h"
+#include "dappm.h"  // DAPPM (DDRNet): the pooling pyramid in one launch per direction, size-based bilinear resize with moments

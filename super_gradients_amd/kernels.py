@@ -1595,6 +1595,98 @@ def avgpool2_ceil_bwd(dy, x_shape, out=None, accumulate=False):
     return out
 
 
+# --------------------------------------------------------------------------------------------- DAPPM (csrc/dappm.h)
+def _dappm_levels(levels):
+    """[(kernel, stride[, padding]), ...] -> the host triples the C side reads (padding defaults to the stride, as DAPPMBranch builds them)."""
+    flat = []
+    for lv in levels:
+        k, s = int(lv[0]), int(lv[1])
+        flat += [k, s, int(lv[2]) if len(lv) > 2 else s]
+    return (ctypes.c_int32 * max(len(flat), 1))(*flat)
+
+
+def dappm_pooled_shape(h, w, k, s):
+    return (h + 2 * s - k) // s + 1, (w + 2 * s - k) // s + 1
+
+
+def dappm_pool_fwd(x, levels, global_level=True, want_stats=True):
+    """Every nn.AvgPool2d(k, s, padding=s) of `levels` and (global_level) nn.AdaptiveAvgPool2d(1) of the NHWC map x, in one launch.
+    -> (pooled, parts): pooled = the window levels' maps in order, then the global [N,1,1,C]; parts (want_stats) = [2, nblk, C] partial rows
+    for bn_finalize / bn_finalize_sync of x itself, then of every pooled map in the same order (nblk = parts[i].shape[1])."""
+    n, h, w, c = x.shape
+    nlev = len(levels)
+    if nlev > 3:
+        raise _lib.SgxError(f"dappm_pool_fwd: {nlev} window levels (at most 3 in one launch)")
+    pooled = [torch.empty((n,) + dappm_pooled_shape(h, w, int(lv[0]), int(lv[1])) + (c,), device=x.device, dtype=torch.float32) for lv in levels]
+    pg = torch.empty(n, 1, 1, c, device=x.device, dtype=torch.float32) if global_level else None
+    tensors = 1 + nlev + int(bool(global_level))
+    parts = torch.empty(tensors, 2, n, c, device=x.device, dtype=torch.float32) if want_stats else None
+    xl, xi = nhwc_strides(x)
+    p = [ptr(t) for t in pooled] + [None] * (3 - nlev)
+    check(lib().sgx_dappm_pool_fwd(n, h, w, c, nlev, _dappm_levels(levels), int(bool(global_level)), ptr(x), xl, xi, p[0], p[1], p[2], ptr(pg), ptr(parts),
+                                   stream()), "sgx_dappm_pool_fwd")
+    return pooled + ([pg] if global_level else []), (list(parts.unbind(0)) if want_stats else None)
+
+
+def dappm_pool_bwd(d_pooled, levels, x_shape, d_global=None, addends=(), out=None, accumulate=False):
+    """dx (+)= the gradient of dappm_pool_fwd's outputs at x, plus up to two addends shaped like x; one launch, dx written once."""
+    n, h, w, c = x_shape
+    nlev = len(levels)
+    if len(d_pooled) != nlev or nlev > 3 or len(addends) > 2:
+        raise _lib.SgxError(f"dappm_pool_bwd: {len(d_pooled)} pooled gradients for {nlev} levels (at most 3), {len(addends)} addends (at most 2)")
+    for d, lv in zip(d_pooled, levels):
+        if tuple(d.shape) != (n,) + dappm_pooled_shape(h, w, int(lv[0]), int(lv[1])) + (c,) or not d.is_contiguous():
+            raise _lib.SgxError(f"dappm_pool_bwd: pooled gradient {tuple(d.shape)} is not the contiguous map of level {tuple(lv)}")
+    if d_global is not None and (d_global.numel() != n * c or not d_global.is_contiguous()):
+        raise _lib.SgxError(f"dappm_pool_bwd: global gradient {tuple(d_global.shape)} is not a contiguous [N,1,1,C]")
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("dappm_pool_bwd: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(x_shape, device=(d_pooled[0] if nlev else d_global).device, dtype=torch.float32)
+    if tuple(out.shape) != tuple(x_shape) or any(tuple(a.shape) != tuple(x_shape) for a in addends):
+        raise _lib.SgxError(f"dappm_pool_bwd: dx / addend shapes do not match {tuple(x_shape)}")
+    d = [ptr(t) for t in d_pooled] + [None] * (3 - nlev)
+    a = [(ptr(t),) + nhwc_strides(t) for t in addends] + [(None, 0, 0)] * (2 - len(addends))
+    xl, xi = nhwc_strides(out)
+    check(lib().sgx_dappm_pool_bwd(n, h, w, c, nlev, _dappm_levels(levels), d[0], d[1], d[2], ptr(d_global), *a[0], *a[1], ptr(out), xl, xi, int(accumulate),
+                                   stream()), "sgx_dappm_pool_bwd")
+    return out
+
+
+def resize_bilinear_fwd(z, size, addend=None, out=None, want_stats=False):
+    """y = F.interpolate(z, size=size, mode="bilinear", align_corners=False) (+ addend) on NHWC tensors or channel slices;
+    want_stats: -> (y, parts), parts = [2, nblk, C] partial rows of y for bn_finalize / bn_finalize_sync."""
+    n, hi, wi, c = z.shape
+    ho, wo = int(size[0]), int(size[1])
+    if out is None:
+        out = torch.empty(n, ho, wo, c, device=z.device, dtype=torch.float32)
+    if tuple(out.shape) != (n, ho, wo, c) or (addend is not None and addend.shape != out.shape):
+        raise _lib.SgxError(f"resize_bilinear_fwd: output / addend shape does not match {(n, ho, wo, c)}")
+    parts = None
+    if want_stats:
+        parts = torch.empty(2, n * max(lib().sgx_resize_bilinear_row_tiles(n, hi, wi, ho, c), 1), c, device=z.device, dtype=torch.float32)
+    (zl, zi), (yl, yi) = nhwc_strides(z), nhwc_strides(out)
+    al, ai = nhwc_strides(addend) if addend is not None else (0, 0)
+    check(lib().sgx_resize_bilinear_fwd(n, hi, wi, ho, wo, c, ptr(z), zl, zi, ptr(addend), al, ai, ptr(out), yl, yi, ptr(parts), stream()),
+          "sgx_resize_bilinear_fwd")
+    return (out, parts) if want_stats else out
+
+
+def resize_bilinear_bwd(dy, size_in, out=None, accumulate=False):
+    """dz (+)= the gradient of resize_bilinear_fwd at z [N, size_in[0], size_in[1], C]."""
+    n, ho, wo, c = dy.shape
+    hi, wi = int(size_in[0]), int(size_in[1])
+    if out is None:
+        if accumulate:
+            raise _lib.SgxError("resize_bilinear_bwd: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(n, hi, wi, c, device=dy.device, dtype=torch.float32)
+    if tuple(out.shape) != (n, hi, wi, c):
+        raise _lib.SgxError(f"resize_bilinear_bwd: dz {tuple(out.shape)} is not {(n, hi, wi, c)}")
+    (dl, di), (zl, zi) = nhwc_strides(dy), nhwc_strides(out)
+    check(lib().sgx_resize_bilinear_bwd(n, hi, wi, ho, wo, c, ptr(dy), dl, di, ptr(out), zl, zi, int(accumulate), stream()), "sgx_resize_bilinear_bwd")
+    return out
+
+
 def colsum(x, out, accumulate=True):
     ld_pix, ld_img = nhwc_strides(x)
     n, h, w, C = x.shape

@@ -430,6 +430,29 @@ class BatchNorm(SgxBlock):
                         sync=self._synced(), parts=parts)
 
 
+class StatsRecord:
+    """The statistics record of a concat buffer (DenseNet's dense blocks, DAPPM's branch outputs) and what its readers need to know about
+    it: count = elements per channel behind the sums (all ranks' when the BatchNorms are synchronised)."""
+
+    __slots__ = ("sums", "count", "sync")
+
+    def __init__(self, channels, rows, device, sync):
+        self.sums = K.dense_record(channels, device)
+        self.count, self.sync = rows, sync
+
+    def put(self, parts, c_off, rows):
+        world = K.dense_stats_reduce(parts, self.sums, c_off, sync=self.sync)
+        self.count = rows * world
+
+    @staticmethod
+    def of(x, sync):
+        """the record of a tensor nobody left statistics for (a block run on its own)"""
+        n, h, w, c = x.shape
+        rec = StatsRecord(c, n * h * w, x.device, sync)
+        rec.put(K.channel_stats_partial(x), 0, n * h * w)
+        return rec
+
+
 class ConvTranspose2x2(SgxBlock):
     _param_kinds = {"weight": "convT"}
 

@@ -34,31 +34,8 @@ from ....common.registry import register_model
 from ....modules.conv_bn_act_block import ConvBNView
 from ....modules.classifier import SgxClassifier, num_classes_of
 from ....modules.engine import SgxBlock
-from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool, need_mult4
+from ....modules.layers import BatchNorm, ConvLayer, LinearLayer, MaxPool, StatsRecord, need_mult4
 from ...utils.utils import get_param
-
-
-class _Record:
-    """A block's statistics record and what its readers need to know about it: count = elements per channel behind the sums (all ranks'
-    when the BatchNorms are synchronised)."""
-
-    __slots__ = ("sums", "count", "sync")
-
-    def __init__(self, channels, rows, device, sync):
-        self.sums = K.dense_record(channels, device)
-        self.count, self.sync = rows, sync
-
-    def put(self, parts, c_off, rows):
-        world = K.dense_stats_reduce(parts, self.sums, c_off, sync=self.sync)
-        self.count = rows * world
-
-    @staticmethod
-    def of(x, sync):
-        """the record of a tensor nobody left statistics for (a block run on its own)"""
-        n, h, w, c = x.shape
-        rec = _Record(c, n * h * w, x.device, sync)
-        rec.put(K.channel_stats_partial(x), 0, n * h * w)
-        return rec
 
 
 class DenseLayer(SgxBlock):
@@ -126,7 +103,7 @@ class DenseLayer(SgxBlock):
         self._buf = buf if self.training else None
         rec = None
         if self.training:
-            rec = _Record(self.cin + self.growth, n * h * w, x.device, self.norm1._synced())
+            rec = StatsRecord(self.cin + self.growth, n * h * w, x.device, self.norm1._synced())
             rec.put(K.channel_stats_partial(buf[..., :self.cin]), 0, n * h * w)
         self.run(buf, rec)
         return buf[..., self.cin:] if out is None else K.axpy(buf[..., self.cin:], out=out)
@@ -172,7 +149,7 @@ class DenseBlock(SgxBlock):
     def open(self, n, h, w, device):
         """-> (the concat buffer, its first slice - for the producer of the block's input to write, its record)"""
         buf = torch.empty(n, h, w, self.cout, device=device, dtype=torch.float32)
-        rec = _Record(self.cout, n * h * w, device, self._synced()) if self.training else None
+        rec = StatsRecord(self.cout, n * h * w, device, self._synced()) if self.training else None
         return buf, buf[..., :self.cin], rec
 
     def run(self, buf, rec):
@@ -236,7 +213,7 @@ class Transition(SgxBlock):
         return K.bn_act_avgpool2_bwd(dp, x, sc, sh, n.weight, mean, invstd, n.weight.grad, n.bias.grad, dx_out, act="relu", sync=n._synced())
 
     def fwd(self, x, out=None):
-        return self.run(x, _Record.of(x, self.norm._synced()) if self.training else None, out=out)
+        return self.run(x, StatsRecord.of(x, self.norm._synced()) if self.training else None, out=out)
 
     def bwd(self, dy, dx_out=None, accumulate=False, addend=None, need_dx=True):
         if accumulate or addend is not None:
